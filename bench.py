@@ -18,6 +18,13 @@ halo rows excluded) / wall time.  This build's primary rays (the reference raste
 are reported separately (`primary_mrays`), as is the primary-equivalent rate W*H*spp / t.
 `ms_per_step` is pipelined throughput (frame f's G-buffer overlaps frame f-1's light passes, its
 tail frame f+1's); `latency_ms` is one frame alone with frame pipelining off (median of 10).
+
+A plain run sets up, warms up, times the steps and prints the headline line (value, ms_per_step, ray
+rates, the configuration and the timed frames' per-kernel times).  --full adds what takes frames of its
+own after the timed region: `latency_ms`, every kernel alone (`isolated_kernel_ms`, `roofline`,
+`diagnostics`) and the CPU baseline (`cpu_baseline`, --cpu-budget seconds).  --dump-outputs DIR writes the
+displayed frame of the last timed step to DIR/<plane>.npy (float32; a fixed seeded pixel sample above
+64 MB), so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -258,13 +265,39 @@ def json_stdout():
     return os.fdopen(fd, "w")
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # all files of one --dump-outputs together
+DUMP_SAMPLE_SEED = 0x68696b61
+
+
+def dump_outputs(directory: Path, arrays: dict) -> None:
+    """--dump-outputs: each array as <directory>/<name>.npy in float32.  An array over its share of
+    DUMP_LIMIT_BYTES is written as a fixed sample of its pixels (rows of the (pixels, channels) view, drawn
+    once from DUMP_SAMPLE_SEED and kept in frame order), the same pixels in every run of the same arguments."""
+    directory.mkdir(parents=True, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            a = a.reshape(-1, a.shape[-1])
+            keep = share // (a.shape[1] * 4) // 2
+            a = a[np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(len(a), size=keep, replace=False))]
+        np.save(directory / f"{name}.npy", a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--config", default="cornell-1080p-nee", choices=sorted(CONFIGS))
-    ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU-baseline work (0 = skip)")
+    ap.add_argument("--cpu-budget", type=float, default=12.0,
+                    help="seconds of CPU-baseline work under --full (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what takes runs of its own: per-frame latency, every "
+                         "kernel alone (the roofline and its diagnostics) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the displayed frame of the last timed step to DIR/tone_mapped.npy (accumulated.npy "
+                         "for an accumulated frame) as float32")
     args = ap.parse_args()
     out = json_stdout()
 
@@ -599,14 +632,26 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     timing = r.kernel_timing()
-    # fraction of the rank's pixels with geometry (G-buffer depth > 0): background pixels take the
-    # passes' early exits and move different bytes (BYTES_PER_PIXEL); read after the timed region
-    depth = r.output(11).view(np.float32)
-    if tiles:  # the tile's columns + halo (the planes are full width; other columns are never computed)
-        hx = halo_rows(cfg["spatial"], cfg["denoise"])
-        depth = depth.reshape(rows, W, 4)[:, max(0, my_tile.x0 - hx): my_tile.x0 + my_tile.cols + hx]
-    depth = depth.reshape(-1, 4)[:, 3]
-    coverage = float((depth >= np.finfo(np.float32).eps).mean())
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after its last step: the displayed frame (the gathered whole
+        # frame on the collective path, else the context's plane), before any later frame overwrites it
+        k = (args.warmup + args.steps - 1) & 1
+        if dist_on and comm_mode == "full":
+            g = peer_t[k] if peer else frame_t[k] if reorder else full_t[k][:H]
+            frame = g.cpu().numpy()
+        else:
+            frame = r.output(shown)
+            frame = frame.view(np.float16 if frame.shape[-1] == 8 else np.float32)
+        dump_outputs(Path(args.dump_outputs), {"tone_mapped" if spp == 1 else "accumulated": frame})
+    if args.full:
+        # fraction of the rank's pixels with geometry (G-buffer depth > 0): background pixels take the
+        # passes' early exits and move different bytes (BYTES_PER_PIXEL); read after the timed region
+        depth = r.output(11).view(np.float32)
+        if tiles:  # the tile's columns + halo (the planes are full width; other columns are never computed)
+            hx = halo_rows(cfg["spatial"], cfg["denoise"])
+            depth = depth.reshape(rows, W, 4)[:, max(0, my_tile.x0 - hx): my_tile.x0 + my_tile.cols + hx]
+        depth = depth.reshape(-1, 4)[:, 3]
+        coverage = float((depth >= np.finfo(np.float32).eps).mean())
     c = r.counters()
     rays = c["traverse_top"] + c["traverse_emitter"]
     primary = c["primary"] - r.primary_reused()  # rays traced (G-buffer reuse skips static sub-frames)
@@ -620,7 +665,7 @@ def main():
 
     # per-frame latency: frames alone (frame pipelining off), each bracketed by a device sync
     latency = None
-    if world == 1 and not dynamic:
+    if args.full and world == 1 and not dynamic:
         saved = r.set_options({"gbuffer_pipeline": 0, "tail_pipeline": 0})
         r.enable_kernel_timing(False)
         f0 = args.warmup + args.steps
@@ -638,7 +683,7 @@ def main():
     # after the timed region: a few frames with every kernel alone on the GPU (no channel fork, no
     # frame pipelining), so the roofline can also quote the dominant kernel's isolated duration
     isolated = None
-    if world == 1 and spp == 1 and not dynamic:
+    if args.full and world == 1 and spp == 1 and not dynamic:
         saved = r.set_options({"channel_streams": 0, "gbuffer_pipeline": 0, "tail_pipeline": 0})
         r.set_kernel_timing_interval(1)
         r.enable_kernel_timing(True)
@@ -653,29 +698,7 @@ def main():
     if rank == 0:
         ms = elapsed / args.steps * 1e3
         mrays = rays / elapsed / 1e6
-        # Roofline of the dominant kernel, one definition: the kernel with the largest GPU
-        # time per frame when it runs alone (isolated frames; the timed region's overlapped durations
-        # when no isolated frames exist: bands, accumulation, dynamic scenes).
-        #   bytes_per_launch = SURVEY §8(d)'s reference-format bytes per pixel x the launch's pixels
-        #   achieved = bytes_per_launch / duration_ms, frac = achieved / 8 TB/s
-        #   traffic  = PMC-measured HBM bytes per launch (steady-state dispatches, profiles/pmc_traffic.json),
-        #              hbm_frac = traffic / duration_ms / 8 TB/s: the bandwidth the launch really draws
-        launches_per_frame = {"denoise": 4}
-        source = isolated if isolated else timing
-        per_frame = {k: v * launches_per_frame.get(k, 1) for k, v in source.items()}
-        dom = max(per_frame, key=per_frame.get)
-        pix = (depth.size // rows) * rows if tiles else W * rows
-        cov_px, bg_px = pix * coverage, pix * (1.0 - coverage)
-        # the reference kernel's algorithmic bytes for this frame: its covered pixels' streams plus its
-        # background pixels' constant stores (BYTES_PER_PIXEL (covered, background); e.g. indirect_lit_ambient
-        # 184 / 220 B).  Round 3 priced every pixel at the covered rate; that figure is kept in diagnostics.
-        ref_bytes = int(kernel_bytes(dom, cov_px, bg_px))
-        r03_bytes = int(BYTES_PER_PIXEL.get(dom, (0, 0))[0] * pix)
-        dur = source[dom]
-        achieved = ref_bytes / (dur * 1e-3) / 1e9
         elide = r.get_option("bg_elision") != 0
-        # the committed PMC numbers are per launch of a whole 1-GPU frame; a band launch differs
-        traffic = load_pmc_traffic(args.config, dom) if world == 1 else None
         result = {
             "metric": "Mrays/sec + ms/frame @1080p 1spp; cornell & city scenes, 1/2/4/8 GPU",
             "value": round(mrays, 2),
@@ -690,7 +713,6 @@ def main():
             "dtype": "f32",
             "data": "synthetic ({} camera; reference assets: cornell.glb, blue noise)".format(
                 "orbiting" if cfg.get("orbit") else "static"),
-            "latency_ms": None if latency is None else round(latency, 4),
             "primary_mrays": round(primary / elapsed / 1e6, 2),
             "primary_equivalent_mrays": round(W * H * spp * args.steps / elapsed / 1e6, 2),
             "config": {"workload": cfg["workload"], "resolution": [W, H], "spp": spp,
@@ -715,44 +737,73 @@ def main():
                        "band_bounds": None if bounds is None else [int(v) for v in bounds],
                        "tile_col_bounds": None if col_bounds is None else [[int(v) for v in c] for c in col_bounds],
                        "band_calibration": balance or None},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                         "hbm_frac": None if traffic is None else
-                         round(traffic / (dur * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                         "bytes_per_launch": ref_bytes, "bytes_per_pixel": list(BYTES_PER_PIXEL.get(dom, (0, 0))),
-                         "pixels_per_launch": pix, "covered_pixels": int(cov_px), "duration_ms": round(dur, 4),
-                         "duration": "isolated" if isolated else "in frame (overlapped)",
-                         # the traversal kernels' other bound: vector issue.  A wave64 VALU instruction holds its SIMD's
-                         # 32-lane ALU for 2 cycles (one wave alone issues one per 4), so the launch needs at least
-                         # valu x 2 / (1024 SIMDs x 2.4 GHz) of ALU time; valu_frac = that floor / the measured duration
-                         # (profiles/valu_issue.json: PMC SQ_INSTS_VALU per launch of the kernel alone)
-                         "valu_issue": valu_issue(args.config, dom, dur) if world == 1 else None},
             "kernel_ms": {k: round(v, 4) for k, v in timing.items()},
-            # each kernel alone on the GPU (the untimed isolated frames after the timed region)
-            "isolated_kernel_ms": None if not isolated else {k: round(v, 4) for k, v in isolated.items()},
-            # context for the roofline (not fractions of it): the bytes the build's launch must move
-            # (background store elision skips constant stores), the share of covered pixels, and all
-            # of a frame's compulsory bytes over the frame time
-            "diagnostics": {"coverage": round(coverage, 4),
-                            "moved_bytes_per_launch": int(kernel_bytes(dom, cov_px, bg_px, st if elide else None)),
-                            # round 3's roofline bytes (every pixel at the covered rate) and its fraction
-                            "r03_bytes_per_launch": r03_bytes,
-                            "r03_frac": round(r03_bytes / (dur * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                            "frame_compulsory_bytes": int(sum(kernel_bytes(k, cov_px, bg_px) *
-                                                              launches_per_frame.get(k, 1) for k in timing) * spp)},
         }
-        tb = load_traversal_bytes(args.config) if world == 1 and spp == 1 else None
-        if tb is not None:
-            # SURVEY §8d's second component: node / triangle / instance / hit_info bytes of the light
-            # passes, priced in reference record sizes (L1/L2/MALL traffic: the scene is cache resident)
-            result["diagnostics"]["frame_traversal_bytes"] = tb
-        lanes = load_lane_efficiency(args.config, wavefront)
-        if lanes is not None:
-            result["diagnostics"]["lane_efficiency"] = lanes
-        if world == 1 and args.cpu_budget > 0:
-            result["cpu_baseline"] = cpu_baseline(desc, camera_at, lights, st, W, H, args.cpu_budget)
-        else:
-            result["cpu_baseline"] = None
+        if args.full:
+            # what took frames of its own after the timed region (latency, every kernel alone) and what is
+            # derived from them; a plain run ends with the headline figures above
+            result["latency_ms"] = None if latency is None else round(latency, 4)
+            # Roofline of the dominant kernel, one definition: the kernel with the largest GPU
+            # time per frame when it runs alone (isolated frames; the timed region's overlapped durations
+            # when no isolated frames exist: bands, accumulation, dynamic scenes).
+            #   bytes_per_launch = SURVEY §8(d)'s reference-format bytes per pixel x the launch's pixels
+            #   achieved = bytes_per_launch / duration_ms, frac = achieved / 8 TB/s
+            #   traffic  = PMC-measured HBM bytes per launch (steady-state dispatches, profiles/pmc_traffic.json),
+            #              hbm_frac = traffic / duration_ms / 8 TB/s: the bandwidth the launch really draws
+            launches_per_frame = {"denoise": 4}
+            source = isolated if isolated else timing
+            per_frame = {k: v * launches_per_frame.get(k, 1) for k, v in source.items()}
+            dom = max(per_frame, key=per_frame.get)
+            pix = (depth.size // rows) * rows if tiles else W * rows
+            cov_px, bg_px = pix * coverage, pix * (1.0 - coverage)
+            # the reference kernel's algorithmic bytes for this frame: its covered pixels' streams plus its
+            # background pixels' constant stores (BYTES_PER_PIXEL (covered, background); e.g. indirect_lit_ambient
+            # 184 / 220 B).  Round 3 priced every pixel at the covered rate; that figure is kept in diagnostics.
+            ref_bytes = int(kernel_bytes(dom, cov_px, bg_px))
+            r03_bytes = int(BYTES_PER_PIXEL.get(dom, (0, 0))[0] * pix)
+            dur = source[dom]
+            achieved = ref_bytes / (dur * 1e-3) / 1e9
+            # the committed PMC numbers are per launch of a whole 1-GPU frame; a band launch differs
+            traffic = load_pmc_traffic(args.config, dom) if world == 1 else None
+            result.update({
+                "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                             "hbm_frac": None if traffic is None else
+                             round(traffic / (dur * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                             "bytes_per_launch": ref_bytes, "bytes_per_pixel": list(BYTES_PER_PIXEL.get(dom, (0, 0))),
+                             "pixels_per_launch": pix, "covered_pixels": int(cov_px), "duration_ms": round(dur, 4),
+                             "duration": "isolated" if isolated else "in frame (overlapped)",
+                             # the traversal kernels' other bound: vector issue.  A wave64 VALU instruction holds its
+                             # SIMD's 32-lane ALU for 2 cycles (one wave alone issues one per 4), so the launch needs at
+                             # least valu x 2 / (1024 SIMDs x 2.4 GHz) of ALU time; valu_frac = that floor / the measured
+                             # duration (profiles/valu_issue.json: PMC SQ_INSTS_VALU per launch of the kernel
+                             # alone)
+                             "valu_issue": valu_issue(args.config, dom, dur) if world == 1 else None},
+                # each kernel alone on the GPU (the untimed isolated frames after the timed region)
+                "isolated_kernel_ms": None if not isolated else {k: round(v, 4) for k, v in isolated.items()},
+                # context for the roofline (not fractions of it): the bytes the build's launch must move
+                # (background store elision skips constant stores), the share of covered pixels, and all
+                # of a frame's compulsory bytes over the frame time
+                "diagnostics": {"coverage": round(coverage, 4),
+                                "moved_bytes_per_launch": int(kernel_bytes(dom, cov_px, bg_px, st if elide else None)),
+                                # round 3's roofline bytes (every pixel at the covered rate) and its fraction
+                                "r03_bytes_per_launch": r03_bytes,
+                                "r03_frac": round(r03_bytes / (dur * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                "frame_compulsory_bytes": int(sum(kernel_bytes(k, cov_px, bg_px) *
+                                                                  launches_per_frame.get(k, 1) for k in timing) * spp)},
+            })
+            tb = load_traversal_bytes(args.config) if world == 1 and spp == 1 else None
+            if tb is not None:
+                # SURVEY §8d's second component: node / triangle / instance / hit_info bytes of the light
+                # passes, priced in reference record sizes (L1/L2/MALL traffic: the scene is cache resident)
+                result["diagnostics"]["frame_traversal_bytes"] = tb
+            lanes = load_lane_efficiency(args.config, wavefront)
+            if lanes is not None:
+                result["diagnostics"]["lane_efficiency"] = lanes
+            if world == 1 and args.cpu_budget > 0:
+                result["cpu_baseline"] = cpu_baseline(desc, camera_at, lights, st, W, H, args.cpu_budget)
+            else:
+                result["cpu_baseline"] = None
         print(json.dumps(result), file=out, flush=True)
     if dist_on:
         drain(-1)

@@ -16,7 +16,7 @@ for rep in $(seq 1 ${REPS:-2}); do
     [ -n "$envs" ] && IFS=',' read -ra ENVARGS <<< "$envs"
     [ "$lib" != "-" ] && ENVARGS+=("HK_LIB=$R/$lib")
     timeout -k 10 200 env "${ENVARGS[@]}" python -u $R/bench.py --config ${CONFIG:-cornell-1080p-nee} --steps ${STEPS:-60} \
-        --warmup 10 --cpu-budget 0 > $OUT/${name}_$rep.json 2> $OUT/${name}_$rep.log
+        --warmup 10 --full --cpu-budget 0 > $OUT/${name}_$rep.json 2> $OUT/${name}_$rep.log
     python - $OUT/${name}_$rep.json $name <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d.get("roofline", {})

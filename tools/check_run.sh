@@ -19,10 +19,10 @@ for spec in "$@"; do
   port=$((port+1))
   if [ "$mode" = "dist" ]; then
     timeout -k 10 300 env "${ENVARGS[@]}" HK_BENCH_DIST=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
-      --master-addr 127.0.0.1 --master-port $port bench.py --config $cfg --cpu-budget 0 $BENCH_ARGS \
+      --master-addr 127.0.0.1 --master-port $port bench.py --full --config $cfg --cpu-budget 0 $BENCH_ARGS \
       > $OUT/bench_$name.json 2> $OUT/bench_$name.err || { tail -20 $OUT/bench_$name.err; exit 1; }
   else
-    timeout -k 10 300 env "${ENVARGS[@]}" python bench.py --config $cfg --cpu-budget 0 $BENCH_ARGS \
+    timeout -k 10 300 env "${ENVARGS[@]}" python bench.py --full --config $cfg --cpu-budget 0 $BENCH_ARGS \
       > $OUT/bench_$name.json 2> $OUT/bench_$name.err || { tail -20 $OUT/bench_$name.err; exit 1; }
   fi
   python - $OUT/bench_$name.json $name <<'PY'

@@ -11,7 +11,7 @@ mkdir -p $OUT
 timeout -k 10 700 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread > $OUT/gpu_tests.log 2>&1
 tail -1 $OUT/gpu_tests.log
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
-timeout -k 10 300 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout -k 10 300 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 # the driver's own command (BENCH_rNN.json: --gpus 1 --steps 20 --warmup 5) beside the default 100 / 16 (VERDICT r05
 # item 3): its 20 frames are frames 5-24, heavier than the steady state (ReSTIR history filling)
 for i in 1 2; do
@@ -25,7 +25,7 @@ done
    --cpu-budget 0 > $R/$OUT/stats_isolated.log 2>&1)
 # the RCCL path itself at world size 1 (communicator, per-frame all-gather, reductions) on the one GPU
 HK_BENCH_DIST=1 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
-    --master-addr 127.0.0.1 --master-port 29534 bench.py --cpu-budget 0 > $OUT/rccl_world1.json 2> $OUT/rccl_world1.err
+    --master-addr 127.0.0.1 --master-port 29534 bench.py --full --cpu-budget 0 > $OUT/rccl_world1.json 2> $OUT/rccl_world1.err
 HK_BENCH_REHEARSAL=1 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
     --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 10 --warmup 3 > $OUT/rehearsal.log 2>&1
 echo final-done

@@ -19,7 +19,7 @@ for spec in "$@"; do
   IFS=: read -r name cfg envs <<< "$spec"
   ENVS=""
   [ -n "$envs" ] && ENVS=$(echo $envs | tr ',' ' ')
-  env $ENVS timeout -k 10 300 python bench.py --config $cfg $BENCH_ARGS > $OUT/bench_$name.json 2> $OUT/bench_$name.err || { tail -20 $OUT/bench_$name.err; exit 1; }
+  env $ENVS timeout -k 10 300 python bench.py --full --config $cfg $BENCH_ARGS > $OUT/bench_$name.json 2> $OUT/bench_$name.err || { tail -20 $OUT/bench_$name.err; exit 1; }
   echo "$name: $(python -c "import json;d=json.load(open('$OUT/bench_$name.json'));print(d['value'], d['ms_per_step'], d.get('latency_ms'), d['roofline']['kernel'], d['roofline']['frac'], d['roofline']['duration_ms'], d['kernel_ms'])")"
 done
 echo done

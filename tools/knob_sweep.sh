@@ -10,6 +10,6 @@ for spec in "$@"; do
   i=$((i+1))
   ENVS=""
   [ "$spec" != "-" ] && ENVS=$(echo $spec | tr ',' ' ')
-  env $ENVS timeout -k 10 200 python bench.py --config $CFG --steps 60 --warmup 10 --cpu-budget 0 > $OUT/k$i.json 2> $OUT/k$i.err
+  env $ENVS timeout -k 10 200 python bench.py --full --config $CFG --steps 60 --warmup 10 --cpu-budget 0 > $OUT/k$i.json 2> $OUT/k$i.err
   echo "$spec: $(python -c "import json;d=json.load(open('$OUT/k$i.json'));print(d['value'], d['ms_per_step'], d['latency_ms'])")"
 done
