@@ -15,6 +15,7 @@
 // sub-tile (the reference's workgroup footprint), so rays of one wave stay coherent.
 #include <stdlib.h>
 #include <mutex>
+#include <type_traits>
 
 #include "hk_device.h"
 #include "hk_launch.h"
@@ -2481,11 +2482,22 @@ __global__ __launch_bounds__(256) void k_trace(Scene sc, const float* rays, cons
 // ------------------------------------------------------------------ launchers
 static dim3 tiles(uint32_t width, int32_t rows) { return dim3((width + 15u) / 16u, ((uint32_t)rows + 15u) / 16u, 1); }
 // the pixels of the context's planes a launch-shape choice weighs: the band's rows, at a tile's window width
-static double plane_px(const Frame& F) { return (double)(F.win_cols > 0 ? (uint32_t)F.win_cols : F.s[0]) * (double)F.s_rows; }
+static double plane_px(const Frame& F) { return (double)launch_cols(F, F.s[0]) * (double)F.s_rows; }
 // the tile grid of a launch: its window's rows (Frame::win_rows), else the plane's
-static dim3 tiles(const Frame& F, uint32_t width, int32_t rows)
+static dim3 tiles(const Frame& F, uint32_t width, int32_t rows) { return tiles(launch_cols(F, width), launch_rows(F, rows)); }
+// Runtime flags -> template arguments: dispatch(f, b0, b1, ...) calls f(std::bool_constant<b0>{}, ...), whose
+// parameters convert to bool in constant expressions.  It instantiates f for every combination of its flags, so only
+// the regular 2^n kernel ladders go through it.
+template <typename F>
+static void dispatch(F&& f)
 {
-    return tiles(F.win_cols > 0 ? (uint32_t)F.win_cols : width, F.win_rows > 0 ? F.win_rows : rows);
+    f();
+}
+template <typename F, typename... Bs>
+static void dispatch(F&& f, bool b, Bs... bs)
+{
+    if (b) dispatch([&](auto... t) { f(std::true_type{}, t...); }, bs...);
+    else dispatch([&](auto... t) { f(std::false_type{}, t...); }, bs...);
 }
 
 // LDS staging is used when the kernel's scene arrays fit LDS_SCENE_MAX and the kernel gains from
@@ -2512,8 +2524,7 @@ void launch_gbuffer(const FrameArgs& A, const ViewArgs& V, uint2* albedo, uint32
     // A small frame (an 8- or 4-way stripe of 1080p: <= gbuffer_lds_max_px pixels, one dispatch round) is as long
     // as one wave's walk, a chain of dependent node loads: there the scene is staged in LDS with the stack after it
     // (cornell 8-way stripe ...).  A whole frame runs many rounds and stays on L2 node loads (round 1: even).
-    const bool small = (double)(A.F.win_cols > 0 ? (uint32_t)A.F.win_cols : A.F.S[0]) *
-                           (double)(A.F.win_rows > 0 ? A.F.win_rows : A.F.S_rows) <= A.opt.gbuffer_lds_max_px;
+    const bool small = (double)launch_cols(A.F, A.F.S[0]) * (double)launch_rows(A.F, A.F.S_rows) <= A.opt.gbuffer_lds_max_px;
     const uint32_t scene = lds_plan_bytes(A, PLAN_GBUFFER, small);
     // (scene + stack within the LDS budget of a staged kernel)
     if (scene && shallow && scene + levels * level_bytes <= LDS_SCENE_MAX + 16384u)
@@ -2536,12 +2547,6 @@ void launch_albedo(const FrameArgs& A, uint2* albedo, hipStream_t st)
 }
 // a validation frame of a direct-light pass: frame.number % interval == 0 (umod: interval 0 -> 0)
 static bool validation_frame(uint32_t number, uint32_t interval) { return interval == 0u || number % interval == 0u; }
-template <bool EL, bool RE, bool LDS>
-static void launch_direct_v(const FrameArgs& A, const ChannelArgs& C, bool val, dim3 g, uint32_t lds, hipStream_t st)
-{
-    if (val) hipLaunchKernelGGL((k_direct<EL, RE, LDS, true>), g, dim3(256), lds, st, A, C);
-    else hipLaunchKernelGGL((k_direct<EL, RE, LDS, false>), g, dim3(256), lds, st, A, C);
-}
 void launch_direct(const FrameArgs& A, const ChannelArgs& C, bool emissive_lit, hipStream_t st)
 {
     dim3 g = tiles(A.F, A.F.s[0], A.F.s_rows);
@@ -2550,23 +2555,14 @@ void launch_direct(const FrameArgs& A, const ChannelArgs& C, bool emissive_lit, 
     // c23); a 256x256 frame (256 workgroups) lost 3 % with it (c23)
     const bool big = plane_px(A.F) >= A.opt.direct_w4_min_px;
     const uint32_t lds = lds_plan_bytes(A, PLAN_LIGHT, big);
-    if (emissive_lit) {
-        const bool val = validation_frame(A.F.number, A.F.emissive_validate_interval);
-        if (lds) launch_direct_v<true, false, true>(A, C, val, g, lds, st);
-        else launch_direct_v<true, false, false>(A, C, val, g, 0, st);
-    } else {
-        const bool val = validation_frame(A.F.number, A.F.direct_validate_interval);
-        if (plane_px(A.F) >= A.opt.direct_w4_min_px) {
-            if (lds) {
-                if (val) hipLaunchKernelGGL((k_direct_lit_w4<true, true>), g, dim3(256), lds, st, A, C);
-                else hipLaunchKernelGGL((k_direct_lit_w4<true, false>), g, dim3(256), lds, st, A, C);
-            } else {
-                if (val) hipLaunchKernelGGL((k_direct_lit_w4<false, true>), g, dim3(256), 0, st, A, C);
-                else hipLaunchKernelGGL((k_direct_lit_w4<false, false>), g, dim3(256), 0, st, A, C);
-            }
-        } else if (lds) launch_direct_v<false, true, true>(A, C, val, g, lds, st);
-        else launch_direct_v<false, true, false>(A, C, val, g, 0, st);
-    }
+    const bool val = validation_frame(A.F.number, emissive_lit ? A.F.emissive_validate_interval : A.F.direct_validate_interval);
+    dispatch(
+        [&](auto LDS, auto VAL) {
+            if (emissive_lit) hipLaunchKernelGGL((k_direct<true, false, LDS, VAL>), g, dim3(256), lds, st, A, C);
+            else if (big) hipLaunchKernelGGL((k_direct_lit_w4<LDS, VAL>), g, dim3(256), lds, st, A, C);
+            else hipLaunchKernelGGL((k_direct<false, true, LDS, VAL>), g, dim3(256), lds, st, A, C);
+        },
+        lds != 0u, val);
 }
 template <bool LDS>
 static void launch_fused_v(const FrameArgs& A, const ChannelArgs& C0, const ChannelArgs& C1, bool vd, bool ve, dim3 g,
@@ -2575,11 +2571,8 @@ static void launch_fused_v(const FrameArgs& A, const ChannelArgs& C0, const Chan
     const bool w4 = A.opt.fused_w4 != 0;
     if (!LDS && w4 && !ve && (A.opt.compact_emitter || A.opt.compact_shadow)) {
         // (compact_shadow implies the emitter compaction: one kernel variant per shadow choice)
-        if (A.opt.compact_shadow) {
-            if (vd) hipLaunchKernelGGL((k_direct_fused_cw<true, true>), g, dim3(256), lds, st, A, C0, C1);
-            else hipLaunchKernelGGL((k_direct_fused_cw<false, true>), g, dim3(256), lds, st, A, C0, C1);
-        } else if (vd) hipLaunchKernelGGL((k_direct_fused_cw<true, false>), g, dim3(256), lds, st, A, C0, C1);
-        else hipLaunchKernelGGL((k_direct_fused_cw<false, false>), g, dim3(256), lds, st, A, C0, C1);
+        dispatch([&](auto VD, auto CS) { hipLaunchKernelGGL((k_direct_fused_cw<VD, CS>), g, dim3(256), lds, st, A, C0, C1); },
+                 vd, A.opt.compact_shadow != 0);
     } else if (!LDS && w4 && ve) {
         if (vd) hipLaunchKernelGGL((k_direct_fused_w4<LDS, true, true>), g, dim3(256), lds, st, A, C0, C1);
         else hipLaunchKernelGGL((k_direct_fused_w4<LDS, false, true>), g, dim3(256), lds, st, A, C0, C1);
@@ -2633,9 +2626,7 @@ static uint32_t persist_grid(const void* kernel, uint32_t lds, const Frame& F)
             if (cached < 32) cache[cached++] = Occ{dev, kernel, lds, per_cu, cus};
         }
     }
-    const int32_t rows = F.win_rows > 0 ? F.win_rows : F.s_rows;
-    const uint32_t cols = F.win_cols > 0 ? (uint32_t)F.win_cols : F.s[0];
-    const uint32_t tiles8 = ((cols + 7u) / 8u) * (((uint32_t)rows + 7u) / 8u);
+    const uint32_t tiles8 = ((launch_cols(F, F.s[0]) + 7u) / 8u) * (((uint32_t)launch_rows(F, F.s_rows) + 7u) / 8u);
     const uint32_t g = (uint32_t)(per_cu > 0 ? per_cu : 1) * (uint32_t)(cus > 0 ? cus : 1);
     const uint32_t need = (tiles8 + 3u) / 4u;
     return need < g ? (need > 0u ? need : 1u) : g;
@@ -2645,29 +2636,22 @@ void launch_indirect(const FrameArgs& A, const ChannelArgs& C, bool multi, hipSt
     dim3 g = tiles(A.F, A.F.s[0], A.F.s_rows);
     const uint32_t lds = lds_plan_bytes(A, PLAN_LIGHT, true);
     if (A.opt.persistent_indirect) {
-#define HK_PERSIST_LAUNCH(M_, L_)                                                                                    \
-    hipLaunchKernelGGL((k_indirect_persist<M_, L_>), dim3(persist_grid((const void*)k_indirect_persist<M_, L_>, lds, A.F)), \
-                       dim3(256), lds, st, A, C)
-        if (multi) {
-            if (lds) HK_PERSIST_LAUNCH(true, true);
-            else HK_PERSIST_LAUNCH(true, false);
-        } else {
-            if (lds) HK_PERSIST_LAUNCH(false, true);
-            else HK_PERSIST_LAUNCH(false, false);
-        }
-#undef HK_PERSIST_LAUNCH
+        dispatch(
+            [&](auto M, auto L) {
+                const dim3 pg(persist_grid((const void*)k_indirect_persist<M, L>, lds, A.F));
+                hipLaunchKernelGGL((k_indirect_persist<M, L>), pg, dim3(256), lds, st, A, C);
+            },
+            multi, lds != 0u);
         return;
     }
-    if (multi) {
-        if (lds) hipLaunchKernelGGL((k_indirect<true, true>), g, dim3(256), lds, st, A, C);
-        else hipLaunchKernelGGL((k_indirect<true, false>), g, dim3(256), 0, st, A, C);
-    } else if (A.opt.compact_shadow) {
-        if (lds) hipLaunchKernelGGL((k_indirect<false, true, true>), g, dim3(256), lds, st, A, C);
-        else hipLaunchKernelGGL((k_indirect<false, false, true>), g, dim3(256), 0, st, A, C);
-    } else {
-        if (lds) hipLaunchKernelGGL((k_indirect<false, true>), g, dim3(256), lds, st, A, C);
-        else hipLaunchKernelGGL((k_indirect<false, false>), g, dim3(256), 0, st, A, C);
-    }
+    // (only the staging flag goes through dispatch: there is no compacted multi-bounce kernel)
+    dispatch(
+        [&](auto L) {
+            if (multi) hipLaunchKernelGGL((k_indirect<true, L>), g, dim3(256), lds, st, A, C);
+            else if (A.opt.compact_shadow) hipLaunchKernelGGL((k_indirect<false, L, true>), g, dim3(256), lds, st, A, C);
+            else hipLaunchKernelGGL((k_indirect<false, L>), g, dim3(256), lds, st, A, C);
+        },
+        lds != 0u);
 }
 bool light_lds_direct(const FrameArgs& A) { return lds_plan_bytes(A, PLAN_LIGHT, false) != 0u; }
 void launch_light_merged(const FrameArgs& A, const ChannelArgs& C0, const ChannelArgs& C1, const ChannelArgs& C2,
@@ -2684,14 +2668,8 @@ void launch_light_merged(const FrameArgs& A, const ChannelArgs& C0, const Channe
     const uint32_t park = (vd || ve) ? (uint32_t)(PARK_WORDS * 256 * sizeof(float)) : 0u;
     const uint32_t ind = scene + (uint32_t)sizeof(IndStash);  // the indirect role: staged scene + stash
     const uint32_t lds = ind > park ? ind : park;
-#define HK_MERGED(VD_, VE_)                                                                                         \
-    if (scene) hipLaunchKernelGGL((k_light_merged<VD_, VE_, true>), g, dim3(256), lds, st, A, C0, C1, C2);          \
-    else hipLaunchKernelGGL((k_light_merged<VD_, VE_, false>), g, dim3(256), lds, st, A, C0, C1, C2);
-    if (vd && ve) { HK_MERGED(true, true) }
-    else if (vd) { HK_MERGED(true, false) }
-    else if (ve) { HK_MERGED(false, true) }
-    else { HK_MERGED(false, false) }
-#undef HK_MERGED
+    dispatch([&](auto VD, auto VE, auto S) { hipLaunchKernelGGL((k_light_merged<VD, VE, S>), g, dim3(256), lds, st, A, C0, C1, C2); },
+             vd, ve, scene != 0u);
 }
 void launch_indirect_wavefront(const FrameArgs& A, const ChannelArgs& C, const WfArgs& W, hipStream_t st)
 {
@@ -2713,50 +2691,43 @@ void launch_spatial(const FrameArgs& A, const ChannelArgs& C, bool emissive_lit,
     // the window assumes integrator pixels == deferred pixels (upscale ratio 1)
     const bool window = A.F.upscale_ratio == 1.0f && A.F.s[0] == A.F.S[0] && A.F.s[1] == A.F.S[1];
     // the view planes hold the indirect channel's records only (ChannelArgs::view)
-    if (emissive_lit) {
-        if (window) hipLaunchKernelGGL((k_spatial<true, false>), g, dim3(256), 0, st, A, C);
-        else hipLaunchKernelGGL((k_spatial_nowin<true, false>), g, dim3(256), 0, st, A, C);
-    } else if (C.view) {
-        if (window) hipLaunchKernelGGL((k_spatial<false, true>), g, dim3(256), 0, st, A, C);
-        else hipLaunchKernelGGL((k_spatial_nowin<false, true>), g, dim3(256), 0, st, A, C);
-    } else {
-        if (window) hipLaunchKernelGGL((k_spatial<false, false>), g, dim3(256), 0, st, A, C);
-        else hipLaunchKernelGGL((k_spatial_nowin<false, false>), g, dim3(256), 0, st, A, C);
-    }
+    auto launch = [&](auto EL, auto VIEW) {
+        if (window) hipLaunchKernelGGL((k_spatial<EL, VIEW>), g, dim3(256), 0, st, A, C);
+        else hipLaunchKernelGGL((k_spatial_nowin<EL, VIEW>), g, dim3(256), 0, st, A, C);
+    };
+    if (emissive_lit) launch(std::true_type{}, std::false_type{});
+    else dispatch([&](auto VIEW) { launch(std::false_type{}, VIEW); }, C.view != nullptr);
 }
 void launch_demod(const FrameArgs& A, const DenoiseArgs& D, hipStream_t st)
 {
     dim3 g = tiles(A.F, A.F.s[0], A.F.s_rows);
-    if (D.channels == 3) hipLaunchKernelGGL(k_demod3<3>, g, dim3(256), 0, st, A, D);
-    else hipLaunchKernelGGL(k_demod3<2>, g, dim3(256), 0, st, A, D);
+    dispatch([&](auto C3) { hipLaunchKernelGGL((k_demod3<C3 ? 3 : 2>), g, dim3(256), 0, st, A, D); }, D.channels == 3);
 }
 template <int C, int LEVEL>
 static void launch_level(const FrameArgs& A, const DenoiseArgs& D, hipStream_t st)
 {
-    const dim3 g = level_tiles<LEVEL>(A.F.win_cols > 0 ? (uint32_t)A.F.win_cols : A.F.s[0],
-                                      A.F.win_rows > 0 ? A.F.win_rows : A.F.s_rows);
+    const dim3 g = level_tiles<LEVEL>(launch_cols(A.F, A.F.s[0]), launch_rows(A.F, A.F.s_rows));
     hipLaunchKernelGGL((k_denoise3<C, LEVEL>), g, dim3(256), 0, st, A, D);
-}
-template <int C>
-static void launch_level(const FrameArgs& A, const DenoiseArgs& D, int level, hipStream_t st)
-{
-    switch (level) {
-    case 0: launch_level<C, 0>(A, D, st); break;
-    case 1: launch_level<C, 1>(A, D, st); break;
-    case 2: launch_level<C, 2>(A, D, st); break;
-    default: launch_level<C, 3>(A, D, st); break;
-    }
 }
 void launch_denoise(const FrameArgs& A, const DenoiseArgs& D, int level, hipStream_t st)
 {
-    if (D.channels == 3) launch_level<3>(A, D, level, st);
-    else launch_level<2>(A, D, level, st);
+    dispatch(
+        [&](auto C3) {
+            constexpr int C = C3 ? 3 : 2;
+            switch (level) {
+            case 0: launch_level<C, 0>(A, D, st); break;
+            case 1: launch_level<C, 1>(A, D, st); break;
+            case 2: launch_level<C, 2>(A, D, st); break;
+            default: launch_level<C, 3>(A, D, st); break;
+            }
+        },
+        D.channels == 3);
 }
 void launch_tone(const FrameArgs& A, const ToneArgs& T, hipStream_t st)
 {
     const Frame& F = A.F;
-    const int32_t ly0 = F.win_rows > 0 ? F.win_row0 : 0, rows = F.win_rows > 0 ? F.win_rows : F.s_rows;
-    const int32_t x0 = F.win_cols > 0 ? F.win_col0 : 0, cols = F.win_cols > 0 ? F.win_cols : (int32_t)F.s[0];
+    const int32_t ly0 = F.win_rows > 0 ? F.win_row0 : 0, rows = launch_rows(F, F.s_rows);
+    const int32_t x0 = F.win_cols > 0 ? F.win_col0 : 0, cols = (int32_t)launch_cols(F, F.s[0]);
     if (F.s[0] % (uint32_t)TONE_RUN == 0u && x0 % TONE_RUN == 0 && cols % TONE_RUN == 0 && rows > 0 && cols > 0) {
         const uint32_t runs = (uint32_t)cols / (uint32_t)TONE_RUN, n = runs * (uint32_t)rows;
         hipLaunchKernelGGL(k_tone_run, dim3((n + 255u) / 256u), dim3(256), 0, st, A, T, ly0, x0, runs, n);

@@ -1,5 +1,5 @@
 // hk_launch.h — kernel argument blocks and launchers shared by hk_kernels.hip and the
-// host runtime (hk_runtime.cpp).
+// host runtime (hk_runtime.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -32,6 +32,9 @@ struct FrameArgs {
     Counters cnt;
     LaunchOpts opt;       // host-side launcher choices (not read by the kernels)
 };
+// (host) the columns / rows a launch covers: its window (Frame::win_cols / win_rows) if set, else the plane extent given
+inline uint32_t launch_cols(const Frame& F, uint32_t width) { return F.win_cols > 0 ? (uint32_t)F.win_cols : width; }
+inline int32_t launch_rows(const Frame& F, int32_t rows) { return F.win_rows > 0 ? F.win_rows : rows; }
 
 // One channel's bindings: group 5 (variance/render) + group 6 (reservoir pair) of light.rs:455-555.
 struct ChannelArgs {
@@ -162,7 +165,7 @@ void launch_indirect(const FrameArgs& A, const ChannelArgs& C, bool multi, hipSt
 // material, material-sorted shade; W.ctl must be zeroed on `st` before
 void launch_indirect_wavefront(const FrameArgs& A, const ChannelArgs& C, const WfArgs& W, hipStream_t st);
 void launch_spatial(const FrameArgs& A, const ChannelArgs& C, bool emissive_lit, hipStream_t st);
-// the direct-light passes stage the scene in LDS (HK_LDS_SCENE=2 with a small enough scene)
+// the direct-light passes stage the scene in LDS (option lds_scene = 2 with a small enough scene)
 bool light_lds_direct(const FrameArgs& A);
 // direct_lit + emissive (fused per pixel) and the one-bounce indirect pass in one launch (k_light_merged)
 void launch_light_merged(const FrameArgs& A, const ChannelArgs& C0, const ChannelArgs& C1, const ChannelArgs& C2,

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -77,6 +78,203 @@ constexpr OptDef OPTS[OPT_COUNT] = {
     {"direct_w4_min_px", 4e5, 0.0, 1e12},  {"fused_w4", 1, 0, 1},          {"persistent_indirect", 0, 0, 1},
     {"compact_emitter", 0, 0, 1},          {"compact_shadow", 0, 0, 1},
 };
+
+// One slot of the planes k_gbuffer double-buffers (hk_ctx::g / g_prev: swapped on each hk_render_gbuffer) so a
+// frame's G-buffer can be traced ahead.  A host upload (hk_set_gbuffer_plane) swaps the position or the velocity
+// plane alone, so the members of one slot need not come from the same allocation round.
+struct GSlot {
+    float4* position = nullptr;
+    uint32_t* normal = nullptr;
+    float2* depth_gradient = nullptr;
+    float2* instance_material = nullptr;
+    float4* velocity_uv = nullptr;
+    uint2* albedo = nullptr;  // the light targets' albedo plane (k_gbuffer writes it with the others)
+};
+
+// The flags and counters of FrameSchedule: what its reset() returns to the values below.
+struct ScheduleState {
+    // G-buffer pipelining: k_gbuffer of frame f runs on gb_stream, next to frame f-1's light passes
+    bool gb_pending = false;   // a k_gbuffer launch was made on gb_stream
+    bool gb_serial = true;     // the next k_gbuffer runs in caller-stream order
+    bool post_pending = false;
+    bool gb_call_rec = false;  // the last call recorded ev_gb_call (it was pipelined)
+    uint32_t gb_calls = 0;
+    // fork shortcut bookkeeping (hk_render_frame): at each hk_render_gbuffer entry (by call parity) the counts
+    // of FrameSchedule::other_picks / frame_st_epoch; the latest k_gbuffer ran on gb_stream (gb_on_gs) after the
+    // caller stream at the previous call's entry (gb_wait_*: the counts there) and after frame tail gb_tail_seq;
+    // the previous hk_render_frame ran its indirect chain on the side stream only (rf_side_only)
+    uint64_t entry_other[2] = {0, 0}, entry_epoch[2] = {0, 0};
+    bool gb_on_gs = false, gb_wait_valid = false, rf_side_only = false;
+    uint64_t gb_wait_other = 0, gb_wait_epoch = 0, gb_tail_seq = 0;
+    // hk_render_frame calls (rf_seq) and the latest one that recorded ev_rf (rf_rec_seq, with the counts
+    // there); the ev_rf the open tail waited for (tail_rf), per G-buffer slot the one its last tail
+    // waited for; per call parity, at hk_render_gbuffer's entry: the latest hk_render_frame and whether
+    // only the frame sequence ran since it recorded ev_rf (entry_clean)
+    uint64_t rf_seq = 0, rf_rec_seq = 0, rf_other = 0, rf_epoch = 0, tail_rf = 0;
+    uint64_t gslot_rf[2] = {0, 0}, entry_rf[2] = {0, 0};
+    bool entry_clean[2] = {false, false};
+    // Frame-tail pipelining: the demodulation, a-trous levels and tone-sum of frame f run on dn_stream next to
+    // frame f+1's light passes.  Slot events: the latest tail work that read render slot r / G-buffer slot g.
+    bool rslot_rec[2] = {false, false}, gslot_rec[2] = {false, false};
+    // tail_end calls so far, and the one that last recorded each slot event (0: none)
+    uint64_t tail_seq = 0, rslot_seq[2] = {0, 0}, gslot_seq[2] = {0, 0};
+    uint32_t rslot = 0, gslot = 0;  // current render / G-buffer slot
+    bool dn_pending = false;        // work was queued on dn_stream
+    bool rf_swapped = false;        // the latest hk_render_frame wrote the other render slot
+    bool tail_open = false;         // dn_stream already waits for that frame (ev_rf)
+};
+
+// Everything that orders a context's work across streams: the streams and events, and which waits are due.
+// A new stream dependency is added here (and nowhere else in hk_ctx).
+struct FrameSchedule : ScheduleState {
+    std::string* error = nullptr;  // hk_ctx::error
+    // channel fork-join: the indirect chain on side[1] next to direct_lit -> emissive (side[0]: see create)
+    hipStream_t side[2] = {nullptr, nullptr};
+    hipStream_t gb_stream = nullptr, dn_stream = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};
+    hipEvent_t ev_gb_done = nullptr;                // after the latest k_gbuffer launch on gb_stream
+    hipEvent_t ev_gb_call[2] = {nullptr, nullptr};  // caller stream at the entry of the last two pipelined calls
+    hipEvent_t ev_post = nullptr;                   // after a post-process read of the previous slot
+    hipEvent_t ev_rf = nullptr;                     // caller stream, end of the latest hk_render_frame
+    hipEvent_t ev_rslot[2] = {nullptr, nullptr}, ev_gslot[2] = {nullptr, nullptr};
+    hipEvent_t ev_dn_last = nullptr;                // dn_stream, after its latest work
+    hipEvent_t ev_frame_mark = nullptr;  // the frame stream's position, waited for by a foreign-stream copy
+    // reads of output planes on streams other than the frame sequence's (hk_copy_output_rows): the plane
+    // and an event after the copy; the next write of that plane waits for it (ext_wait)
+    std::vector<std::pair<const void*, hipEvent_t>> ext_reads;
+    std::vector<hipEvent_t> ext_pool;
+    // API calls outside the frame sequence, the frame sequence's stream and its changes (pick / pick_frame)
+    uint64_t other_picks = 0, frame_st_epoch = 0;
+    hipStream_t frame_st = nullptr;
+
+    std::array<hipEvent_t*, 14> events()
+    {
+        return {&ev_fork,     &ev_join[0],  &ev_join[1],  &ev_gb_done,  &ev_gb_call[0], &ev_gb_call[1], &ev_post,
+                &ev_rf,       &ev_rslot[0], &ev_rslot[1], &ev_gslot[0], &ev_gslot[1],   &ev_dn_last,    &ev_frame_mark};
+    }
+    int fail(const char* msg) const
+    {
+        *error = msg;
+        return HK_ERR_HIP;
+    }
+    int create(std::string* err)
+    {
+        error = err;
+        // side[1] runs the indirect chain.  side[0] carries no work but is kept: streams are mapped
+        // round-robin onto the process's hardware queues (GPU_MAX_HW_QUEUES = 4), and without it the
+        // G-buffer / tail streams land on queues that serialise them behind the light passes
+        // (cornell 1080p 0.601 -> 0.674 ms/frame measured without it).  Keep this creation order.
+        for (hipStream_t* s : {&side[0], &side[1], &gb_stream, &dn_stream})
+            if (hipStreamCreateWithFlags(s, hipStreamNonBlocking) != hipSuccess) return HK_ERR_HIP;
+        for (hipEvent_t* e : events())
+            if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) return HK_ERR_HIP;
+        return HK_OK;
+    }
+    void destroy()
+    {
+        for (auto& r : ext_reads) ext_pool.push_back(r.second);
+        for (hipEvent_t e : ext_pool) (void)hipEventDestroy(e);
+        for (hipStream_t s : side)
+            if (s) (void)hipStreamSynchronize(s);
+        for (hipEvent_t* e : events())
+            if (*e) (void)hipEventDestroy(*e);
+        for (hipStream_t s : {side[0], side[1], gb_stream, dn_stream})
+            if (s) (void)hipStreamDestroy(s);
+    }
+    // A resize: resize_impl has synchronised the context's streams and freed every plane, and synchronises the
+    // device before it returns, so every event recorded so far has completed by the next API call and a cleared
+    // flag only skips a wait on a completed event.  Every flag and counter returns to a new context's value.
+    // What persists: the streams and events themselves, ext_reads / ext_pool (they own events; a stale entry costs
+    // one wait on a completed event), and other_picks / frame_st / frame_st_epoch (they describe the caller's
+    // streams, not the targets: a foreign-stream copy after a resize still has to know the frame stream).
+    void reset() { static_cast<ScheduleState&>(*this) = ScheduleState{}; }
+
+    // Work that reads G-buffer planes, counters or targets, or that changes the scene, first waits
+    // for any k_gbuffer launched ahead on gb_stream and any denoise / tone-sum queued on dn_stream
+    // (hipStreamWaitEvent: device-side, no host wait).
+    int gb_join(hipStream_t st, bool with_denoise = true) const
+    {
+        if (gb_pending && hipStreamWaitEvent(st, ev_gb_done, 0) != hipSuccess)
+            return fail("hipStreamWaitEvent(G-buffer) failed");
+        if (with_denoise && dn_pending && hipStreamWaitEvent(st, ev_dn_last, 0) != hipSuccess)
+            return fail("hipStreamWaitEvent(denoise) failed");
+        return HK_OK;
+    }
+    // The next write of `plane` (nullptr: of any plane) waits on `st` for the foreign-stream copies that read it.
+    int ext_wait(hipStream_t st, const void* plane)
+    {
+        for (size_t k = 0; k < ext_reads.size();) {
+            if (plane && ext_reads[k].first != plane) {
+                ++k;
+                continue;
+            }
+            if (hipStreamWaitEvent(st, ext_reads[k].second, 0) != hipSuccess)
+                return fail("hipStreamWaitEvent(output read) failed");
+            ext_pool.push_back(ext_reads[k].second);
+            ext_reads[k] = ext_reads.back();
+            ext_reads.pop_back();
+        }
+        return HK_OK;
+    }
+    // frame-tail work on dn_stream: it starts after the frame's hk_render_frame (ev_rf) and marks
+    // the render / G-buffer slots it read
+    int tail_begin()
+    {
+        if (!tail_open) {
+            if (hipStreamWaitEvent(dn_stream, ev_rf, 0) != hipSuccess) return fail("hipStreamWaitEvent(frame) failed");
+            tail_rf = rf_rec_seq;
+        }
+        tail_open = true;
+        return HK_OK;
+    }
+    int tail_end()
+    {
+        if (hipEventRecord(ev_rslot[rslot], dn_stream) != hipSuccess ||
+            hipEventRecord(ev_gslot[gslot], dn_stream) != hipSuccess ||
+            hipEventRecord(ev_dn_last, dn_stream) != hipSuccess)
+            return fail("hipEventRecord(frame tail) failed");
+        rslot_rec[rslot] = gslot_rec[gslot] = true;
+        tail_seq++;
+        rslot_seq[rslot] = gslot_seq[gslot] = tail_seq;
+        gslot_rf[gslot] = tail_rf;
+        dn_pending = true;
+        return HK_OK;
+    }
+    // the scene, sizes or G-buffer planes change on the caller's stream: the next k_gbuffer must run
+    // in caller-stream order (and a synchronous change waits for the one in flight)
+    int gb_serialize(bool host_sync)
+    {
+        gb_serial = true;
+        if (host_sync && gb_stream && hipStreamSynchronize(gb_stream) != hipSuccess)
+            return fail("hipStreamSynchronize(G-buffer stream) failed");
+        if (host_sync && dn_stream && hipStreamSynchronize(dn_stream) != hipSuccess)
+            return fail("hipStreamSynchronize(denoise stream) failed");
+        return HK_OK;
+    }
+
+    // The three conditions under which a wait packet is dropped (each one ahead of a kernel delays it).
+    // hk_render_gbuffer, pipelined, slot g = gslot ^ 1, w = the call parity whose entry marker it would wait for:
+    // frame f-2's tail (dn_stream) read this slot; it waited for ev_rf of a hk_render_frame (gslot_rf).
+    // When that is the one whose ev_rf marked the caller stream where the previous call's entry
+    // marker stands (nothing but the frame sequence ran in between: entry_clean) or a later one, the
+    // tail's event implies the entry marker, and k_gbuffer waits for the tail alone: one packet fewer
+    // ahead of it in the queue it shares with the indirect chain.
+    bool tail_covers(uint32_t w, uint32_t g) const
+    {
+        return gb_call_rec && gslot_rec[g] && entry_clean[w] && entry_rf[w] > 0 && gslot_rf[g] >= entry_rf[w];
+    }
+    // hk_render_frame: this frame's G-buffer ran pipelined on gb_stream after the caller stream at the previous
+    // hk_render_gbuffer's entry (W), and since W only the frame sequence ran, on this stream (no other
+    // API call, no stream change): frame f-1's hk_render_frame, denoise, tone-sum and this frame's
+    // hk_render_gbuffer.  See the fork there.
+    bool gb_fresh() const
+    {
+        return gb_on_gs && gb_wait_valid && other_picks == gb_wait_other && frame_st_epoch == gb_wait_epoch && gb_pending;
+    }
+    // hk_render_frame: the render slot's last reader (frame f-2's tail) is also covered by ev_gb_done when
+    // k_gbuffer waited for that tail or a later one (dn_stream is in order)
+    bool slot_covered() const { return gb_fresh() && rslot_seq[rslot] <= gb_tail_seq; }
+};
 }  // namespace
 
 struct hk_ctx {
@@ -123,72 +321,13 @@ struct hk_ctx {
     bool albedo_fresh = false;  // the albedo target matches the G-buffer (k_gbuffer wrote both)
     bool sized = false;
 
-    // G-buffer (band-local, S-wide)
-    float4* g_position = nullptr;
-    uint32_t* g_normal = nullptr;
-    float2* g_depth_gradient = nullptr;
-    float2* g_instance_material = nullptr;
-    float4* g_velocity_uv = nullptr;
-    float4* g_prev_position = nullptr;    // the previous frame's planes (prepass.rs:309-317 swap)
-    float4* g_prev_velocity_uv = nullptr;
-    // the other slot of the planes k_gbuffer double-buffers (swapped with the current ones on each
-    // hk_render_gbuffer, like position / velocity above) so a frame's G-buffer can be traced ahead
-    uint32_t* g_prev_normal = nullptr;
-    float2* g_prev_depth_gradient = nullptr;
-    float2* g_prev_instance_material = nullptr;
-    uint2* albedo_prev = nullptr;
-    // G-buffer pipelining: k_gbuffer of frame f runs on gb_stream, next to frame f-1's light passes
-    hipStream_t gb_stream = nullptr;
-    hipEvent_t ev_gb_done = nullptr;            // after the latest k_gbuffer launch on gb_stream
-    hipEvent_t ev_gb_call[2] = {nullptr, nullptr};  // caller stream at the entry of the last two pipelined calls
-    hipEvent_t ev_post = nullptr;               // after a post-process read of the previous slot
-    bool gb_pending = false;                    // a k_gbuffer launch was made on gb_stream
-    bool gb_serial = true;                      // the next k_gbuffer runs in caller-stream order
-    bool post_pending = false;
-    bool gb_call_rec = false;                   // the last call recorded ev_gb_call (it was pipelined)
-    uint32_t gb_calls = 0;
-    // fork shortcut bookkeeping (pick / pick_frame, hk_render_frame): API calls outside the frame
-    // sequence, the frame sequence's stream and its changes; at each hk_render_gbuffer entry (by call
-    // parity) those counts; the latest k_gbuffer ran on gb_stream (gb_on_gs) after the caller stream at
-    // the previous call's entry (gb_wait_*: the counts there) and after frame tail gb_tail_seq; the
-    // previous hk_render_frame ran its indirect chain on the side stream only (rf_side_only)
-    uint64_t other_picks = 0, frame_st_epoch = 0;
-    hipStream_t frame_st = nullptr;
-    uint64_t entry_other[2] = {0, 0}, entry_epoch[2] = {0, 0};
-    bool gb_on_gs = false, gb_wait_valid = false, rf_side_only = false;
-    uint64_t gb_wait_other = 0, gb_wait_epoch = 0, gb_tail_seq = 0;
-    // hk_render_frame calls (rf_seq) and the latest one that recorded ev_rf (rf_rec_seq, with the counts
-    // there); the ev_rf the open tail waited for (tail_rf), per G-buffer slot the one its last tail
-    // waited for; per call parity, at hk_render_gbuffer's entry: the latest hk_render_frame and whether
-    // only the frame sequence ran since it recorded ev_rf (entry_clean)
-    uint64_t rf_seq = 0, rf_rec_seq = 0, rf_other = 0, rf_epoch = 0, tail_rf = 0;
-    uint64_t gslot_rf[2] = {0, 0}, entry_rf[2] = {0, 0};
-    bool entry_clean[2] = {false, false};
-    // Frame-tail pipelining: the demodulation, a-trous levels and tone-sum of frame f run on
-    // dn_stream next to frame f+1's light passes; render / variance are double-buffered for it.
-    // Slot events: the latest tail work that read render slot r / G-buffer slot g.
-    uint2* render_alt[3] = {};
-    float* variance_alt[3] = {};
-    hipStream_t dn_stream = nullptr;
-    hipEvent_t ev_rf = nullptr;                 // caller stream, end of the latest hk_render_frame
-    hipEvent_t ev_rslot[2] = {nullptr, nullptr};
-    hipEvent_t ev_gslot[2] = {nullptr, nullptr};
-    hipEvent_t ev_dn_last = nullptr;            // dn_stream, after its latest work
-    bool rslot_rec[2] = {false, false}, gslot_rec[2] = {false, false};
-    // tail_end calls so far, and the one that last recorded each slot event (0: none)
-    uint64_t tail_seq = 0, rslot_seq[2] = {0, 0}, gslot_seq[2] = {0, 0};
-    uint32_t rslot = 0, gslot = 0;              // current render / G-buffer slot
-    bool dn_pending = false;                    // work was queued on dn_stream
-    bool rf_swapped = false;                    // the latest hk_render_frame wrote the other render slot
-    bool tail_open = false;                     // dn_stream already waits for that frame (ev_rf)
-    uint32_t head = 0;                    // frame_number % 2 (PostProcessTextures.head)
-    // channel fork-join: emissive and indirect passes on side streams next to direct_lit
-    hipStream_t side[2] = {nullptr, nullptr};
-    hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};
-    // light targets
-    uint2* albedo = nullptr;
-    float* variance[3] = {};
-    uint2* render[3] = {};
+    // G-buffer (band-local, S-wide): this frame's planes and the previous frame's (prepass.rs:309-317 swap)
+    GSlot g, g_prev;
+    FrameSchedule sch;  // everything that orders work across streams
+    uint32_t head = 0;  // frame_number % 2 (PostProcessTextures.head)
+    // light targets (albedo: GSlot); render / variance are double-buffered for frame-tail pipelining (sch.rslot)
+    float* variance[3] = {}, *variance_alt[3] = {};
+    uint2* render[3] = {}, *render_alt[3] = {};
     uint4* reservoirs[HK_RESERVOIR_BUFFERS] = {};
     uint32_t res_n = 0;
     // background store elision masks (ChannelArgs::bg): [0] the fused direct/emissive pair, [1] the
@@ -233,11 +372,6 @@ struct hk_ctx {
     uint32_t* wf_ctl = nullptr;
     uint32_t wf_seg_cap = 0;
 
-    // reads of output planes on streams other than the frame sequence's (hk_copy_output_rows): the plane
-    // and an event after the copy; the next write of that plane waits for it (ext_wait)
-    std::vector<std::pair<const void*, hipEvent_t>> ext_reads;
-    std::vector<hipEvent_t> ext_pool;
-    hipEvent_t ev_frame_mark = nullptr;  // the frame stream's position, waited for by a foreign-stream copy
     // G-buffer reuse (option gbuffer_reuse): what produced the planes now in each G-buffer slot — the
     // view, jitter and band window of the k_gbuffer that wrote them and the input generation at that
     // time (bumped by every scene / texture / instance / size / host-plane / option change)
@@ -285,19 +419,18 @@ int fail(hk_ctx* c, int code, const std::string& msg)
 // shortcut there).
 hipStream_t pick(hk_ctx* c, void* stream)
 {
-    c->other_picks++;
+    c->sch.other_picks++;
     return stream ? (hipStream_t)stream : c->stream;
 }
 hipStream_t pick_frame(hk_ctx* c, void* stream)
 {
     const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (s != c->frame_st) {
-        c->frame_st = s;
-        c->frame_st_epoch++;
+    if (s != c->sch.frame_st) {
+        c->sch.frame_st = s;
+        c->sch.frame_st_epoch++;
     }
     return s;
 }
-
 
 #define HK_TRY(expr)            \
     do {                        \
@@ -305,58 +438,8 @@ hipStream_t pick_frame(hk_ctx* c, void* stream)
         if (_r != HK_OK) return _r; \
     } while (0)
 
-// Work that reads G-buffer planes, counters or targets, or that changes the scene, first waits
-// for any k_gbuffer launched ahead on gb_stream and any denoise / tone-sum queued on dn_stream
-// (hipStreamWaitEvent: device-side, no host wait).
-int gb_join(hk_ctx* c, hipStream_t st, bool with_denoise = true)
-{
-    if (c->gb_pending && hipStreamWaitEvent(st, c->ev_gb_done, 0) != hipSuccess)
-        return fail(c, HK_ERR_HIP, "hipStreamWaitEvent(G-buffer) failed");
-    if (with_denoise && c->dn_pending && hipStreamWaitEvent(st, c->ev_dn_last, 0) != hipSuccess)
-        return fail(c, HK_ERR_HIP, "hipStreamWaitEvent(denoise) failed");
-    return HK_OK;
-}
-// The next write of `plane` (nullptr: of any plane) waits on `st` for the foreign-stream copies that read it.
-int ext_wait(hk_ctx* c, hipStream_t st, const void* plane)
-{
-    for (size_t k = 0; k < c->ext_reads.size();) {
-        if (plane && c->ext_reads[k].first != plane) {
-            ++k;
-            continue;
-        }
-        if (hipStreamWaitEvent(st, c->ext_reads[k].second, 0) != hipSuccess)
-            return fail(c, HK_ERR_HIP, "hipStreamWaitEvent(output read) failed");
-        c->ext_pool.push_back(c->ext_reads[k].second);
-        c->ext_reads[k] = c->ext_reads.back();
-        c->ext_reads.pop_back();
-    }
-    return HK_OK;
-}
-// frame-tail work on dn_stream: it starts after the frame's hk_render_frame (ev_rf) and marks
-// the render / G-buffer slots it read
-int tail_begin(hk_ctx* c)
-{
-    if (!c->tail_open) {
-        if (hipStreamWaitEvent(c->dn_stream, c->ev_rf, 0) != hipSuccess)
-            return fail(c, HK_ERR_HIP, "hipStreamWaitEvent(frame) failed");
-        c->tail_rf = c->rf_rec_seq;
-    }
-    c->tail_open = true;
-    return HK_OK;
-}
-int tail_end(hk_ctx* c)
-{
-    if (hipEventRecord(c->ev_rslot[c->rslot], c->dn_stream) != hipSuccess ||
-        hipEventRecord(c->ev_gslot[c->gslot], c->dn_stream) != hipSuccess ||
-        hipEventRecord(c->ev_dn_last, c->dn_stream) != hipSuccess)
-        return fail(c, HK_ERR_HIP, "hipEventRecord(frame tail) failed");
-    c->rslot_rec[c->rslot] = c->gslot_rec[c->gslot] = true;
-    c->tail_seq++;
-    c->rslot_seq[c->rslot] = c->gslot_seq[c->gslot] = c->tail_seq;
-    c->gslot_rf[c->gslot] = c->tail_rf;
-    c->dn_pending = true;
-    return HK_OK;
-}
+// a 2-D tile (hk_resize_tile): the context owns some of the columns only
+bool tile_columns(const hk_ctx* c) { return c->core_cols > 0 && c->core_cols < (int32_t)c->S[0]; }
 // Frame pipelining pays on large frames: on a small stripe of traversal + NEE alone (a 2- to 8-way split
 // of 1080p: <= 1 Mpx, 0.1-0.25 ms frames) the cross-stream waits cost more than the overlap hides
 // (cornell 8-way stripe 0.145 -> 0.172 ms), on a 1080p frame or a 4K band it gains.  A frame with spatial
@@ -368,7 +451,7 @@ int tail_end(hk_ctx* c)
 double ctx_px(const hk_ctx* c)
 {
     double cols = (double)c->s[0];
-    if (c->core_cols > 0 && c->core_cols < (int32_t)c->S[0])
+    if (tile_columns(c))
         cols = (double)(std::min((int32_t)c->s[0], c->core_col0 + c->core_cols + c->halo) - std::max(0, c->core_col0 - c->halo));
     return cols * (double)c->s_rows;
 }
@@ -378,17 +461,6 @@ bool pipeline_size(const hk_ctx* c)
     return px >= c->opt[OPT_PIPELINE_MIN_PX] || (c->heavy && px >= c->opt[OPT_PIPELINE_HEAVY_MIN_PX]);
 }
 bool dn_pipeline_enabled(const hk_ctx* c) { return c->on(OPT_TAIL_PIPELINE) && pipeline_size(c); }
-// the scene, sizes or G-buffer planes change on the caller's stream: the next k_gbuffer must run
-// in caller-stream order (and a synchronous change waits for the one in flight)
-int gb_serialize(hk_ctx* c, bool host_sync)
-{
-    c->gb_serial = true;
-    if (host_sync && c->gb_stream && hipStreamSynchronize(c->gb_stream) != hipSuccess)
-        return fail(c, HK_ERR_HIP, "hipStreamSynchronize(G-buffer stream) failed");
-    if (host_sync && c->dn_stream && hipStreamSynchronize(c->dn_stream) != hipSuccess)
-        return fail(c, HK_ERR_HIP, "hipStreamSynchronize(denoise stream) failed");
-    return HK_OK;
-}
 
 template <typename T>
 void release(T*& p)
@@ -397,69 +469,72 @@ void release(T*& p)
     p = nullptr;
 }
 
+// Every device target whose size follows hk_resize, named once: resize_impl allocates from this table and
+// free_targets releases from it, so a new plane is its typed member in hk_ctx plus one line here.  Only those two
+// walk the table; the frame path reads the typed members.
+struct Target {
+    void** ptr;
+    size_t bpp;     // bytes per pixel
+    char plane;     // sized by 'S': S[0] x S_rows pixels, 's': s[0] x s_rows; 0: allocated on first use where it
+                    // is needed (hk_post_process, hk_accumulate, ensure_wavefront) and only released from here
+    uint32_t mult;  // planes per buffer
+    bool zero;      // zero-filled by hk_resize
+};
+std::vector<Target> targets(hk_ctx* c)
+{
+    std::vector<Target> t;
+    auto add = [&t](auto*& p, char plane, uint32_t mult = 1, bool zero = true) {
+        t.push_back(Target{(void**)&p, sizeof(*p), plane, mult, zero});
+    };
+    for (GSlot* g : {&c->g, &c->g_prev}) {
+        add(g->position, 'S');
+        add(g->normal, 'S');
+        add(g->depth_gradient, 'S');
+        add(g->instance_material, 'S');
+        add(g->velocity_uv, 'S');
+        add(g->albedo, 'S');
+    }
+    for (int i = 0; i < 3; ++i) {
+        add(c->variance[i], 's');
+        add(c->render[i], 's');
+        add(c->variance_alt[i], 's');
+        add(c->render_alt[i], 's');
+        add(c->denoised[i], 's');
+        add(c->internal_variance[i], 's');
+    }
+    for (auto& r : c->reservoirs) add(r, 's', 4);  // light.rs:355-358 zero-fill
+    // (the elision masks are not zero-filled: their valid flags are cleared instead)
+    for (auto& m : c->bgmask) add(m, 's', 1, false);
+    add(c->gbmask, 'S', 1, false);
+    add(c->sp_view, 's', VIEW_PLANES);
+    for (int i = 0; i < 4; ++i) {
+        add(c->dn_rgb[i], 's');
+        add(c->dn_bi[i], 's');
+    }
+    add(c->dn_nd, 's');
+    add(c->dn_center, 's');
+    add(c->dn_den2, 's');
+    for (auto& b : c->tone_buf) add(b, 's');
+    add(c->upscale, 0);
+    for (auto& b : c->taa_buf) add(b, 0);
+    add(c->accum, 0);
+    add(c->accum_out, 0);
+    add(c->wf_queue1, 0);
+    add(c->wf_keys, 0);
+    add(c->wf_queue2, 0);
+    add(c->wf_hit, 0);
+    add(c->wf_hit_t, 0);
+    add(c->wf_ctl, 0);
+    return t;
+}
+
 void free_targets(hk_ctx* c)
 {
-    release(c->g_position);
-    release(c->g_normal);
-    release(c->g_depth_gradient);
-    release(c->g_instance_material);
-    release(c->g_velocity_uv);
-    release(c->albedo);
-    for (int i = 0; i < 3; ++i) {
-        release(c->variance[i]);
-        release(c->render[i]);
-        release(c->variance_alt[i]);
-        release(c->render_alt[i]);
-        release(c->denoised[i]);
-    }
-    for (int i = 0; i < HK_RESERVOIR_BUFFERS; ++i) release(c->reservoirs[i]);
-    for (int k = 0; k < 2; ++k) {
-        release(c->bgmask[k]);
-        c->bg_valid[k] = false;
-    }
-    release(c->gbmask);
-    c->gb_valid = false;
-    release(c->sp_view);
-    for (int ch = 0; ch < 3; ++ch) {
-        release(c->internal_variance[ch]);
-    }
-    for (int i = 0; i < 4; ++i) {
-        release(c->dn_rgb[i]);
-        release(c->dn_bi[i]);
-    }
-    release(c->dn_nd);
-    release(c->dn_center);
-    release(c->dn_den2);
-    for (int k = 0; k < 2; ++k) {
-        release(c->tone_buf[k]);
-        release(c->taa_buf[k]);
-    }
-    release(c->upscale);
-    release(c->g_prev_position);
-    release(c->g_prev_velocity_uv);
-    release(c->g_prev_normal);
-    release(c->g_prev_depth_gradient);
-    release(c->g_prev_instance_material);
-    release(c->albedo_prev);
-    c->gb_serial = true;
-    c->gb_calls = 0;
-    c->gb_on_gs = c->gb_wait_valid = c->rf_side_only = false;
-    c->gb_call_rec = false;
-    c->rf_swapped = c->tail_open = false;
-    c->rslot_rec[0] = c->rslot_rec[1] = c->gslot_rec[0] = c->gslot_rec[1] = false;
-    c->rslot_seq[0] = c->rslot_seq[1] = c->gslot_seq[0] = c->gslot_seq[1] = 0;
-    c->gslot_rf[0] = c->gslot_rf[1] = 0;
-    c->entry_clean[0] = c->entry_clean[1] = false;
+    for (const Target& t : targets(c)) release(*t.ptr);
+    c->bg_valid[0] = c->bg_valid[1] = c->gb_valid = false;
     c->upscale_wh[0] = c->upscale_wh[1] = c->taa_wh[0] = c->taa_wh[1] = 0;
-    release(c->accum);
-    release(c->accum_out);
     c->accum_n = 0;
-    release(c->wf_queue1);
-    release(c->wf_keys);
-    release(c->wf_queue2);
-    release(c->wf_hit);
-    release(c->wf_hit_t);
-    release(c->wf_ctl);
+    c->sch.reset();
     c->sized = false;
 }
 
@@ -648,7 +723,7 @@ FrameArgs frame_args(hk_ctx* c, const hk_settings* st, const hk_frame_inputs* in
     F.count_Sy1 = c->S_rows == (int32_t)c->S[1] && c->core_rows == (int32_t)c->s[1] ? (int32_t)c->S[1]
                                                                                       : F.count_Sy0 + c->core_rows;
     // columns: a tile's own (ratio 1, so the same for the G-buffer), every column otherwise
-    const bool tile = c->core_cols > 0 && c->core_cols < (int32_t)c->S[0];
+    const bool tile = tile_columns(c);
     F.count_x0 = tile ? c->core_col0 : 0;
     F.count_x1 = tile ? c->core_col0 + c->core_cols : INT32_MAX;
     F.win_col0 = F.win_cols = 0;
@@ -659,11 +734,11 @@ FrameArgs frame_args(hk_ctx* c, const hk_settings* st, const hk_frame_inputs* in
         F.count_y1 = (int32_t)c->s[1];
         F.count_Sy1 = (int32_t)c->S[1];
     }
-    A.G.position = c->g_position;
-    A.G.normal = c->g_normal;
-    A.G.depth_gradient = c->g_depth_gradient;
-    A.G.instance_material = c->g_instance_material;
-    A.G.velocity_uv = c->g_velocity_uv;
+    A.G.position = c->g.position;
+    A.G.normal = c->g.normal;
+    A.G.depth_gradient = c->g.depth_gradient;
+    A.G.instance_material = c->g.instance_material;
+    A.G.velocity_uv = c->g.velocity_uv;
     A.noise = c->noise;
     A.cnt.top = c->counters;
     A.cnt.emitter = c->counters + COUNTER_SPAN;
@@ -703,7 +778,6 @@ constexpr int32_t GBUFFER_REACH = DENOISE_OUT_REACH + SPATIAL_RANGE;
 // Only for a static frame: under camera or instance motion temporal reprojection reads the previous
 // frame's reservoirs at other rows, so every pass runs on the whole band (velocity_zero is set by
 // hk_render_gbuffer before its own window is taken, and cleared by a host G-buffer plane upload).
-bool tile_columns(const hk_ctx* c) { return c->core_cols > 0 && c->core_cols < (int32_t)c->S[0]; }
 bool band_windowed(const hk_ctx* c)
 {
     return !(c->stripe_n >= 2 || (c->core_rows >= c->s_rows && !tile_columns(c)) || c->S_rows != c->s_rows ||
@@ -821,11 +895,11 @@ int band_windows(hk_ctx* c, const hk_settings* st, hipStream_t s)
 uint64_t gbuffer_primary_rays(const FrameArgs& A)
 {
     const Frame& F = A.F;
-    const int32_t w0 = F.win_rows > 0 ? F.win_row0 : 0, w1 = F.win_rows > 0 ? F.win_row0 + F.win_rows : F.S_rows;
+    const int32_t w0 = F.win_rows > 0 ? F.win_row0 : 0, w1 = w0 + launch_rows(F, F.S_rows);
     if (F.stripe_n >= 2) return (uint64_t)F.S[0] * (uint64_t)(w1 - w0);
     const int32_t lo = std::max(F.S_row0 + w0, F.count_Sy0), hi = std::min(F.S_row0 + w1, F.count_Sy1);
-    const int32_t x0 = std::max(F.win_cols > 0 ? F.win_col0 : 0, F.count_x0);
-    const int32_t x1 = std::min(F.win_cols > 0 ? F.win_col0 + F.win_cols : (int32_t)F.S[0], F.count_x1);
+    const int32_t c0 = F.win_cols > 0 ? F.win_col0 : 0, c1 = c0 + (int32_t)launch_cols(F, F.S[0]);
+    const int32_t x0 = std::max(c0, F.count_x0), x1 = std::min(c1, F.count_x1);
     return hi > lo && x1 > x0 ? (uint64_t)(x1 - x0) * (uint64_t)(hi - lo) : 0u;
 }
 
@@ -887,30 +961,7 @@ int hk_create(int device, hk_ctx** out)
         delete c;
         return HK_ERR_HIP;
     }
-    // side[1] runs the indirect chain.  side[0] carries no work but is kept: streams are mapped
-    // round-robin onto the process's hardware queues (GPU_MAX_HW_QUEUES = 4), and without it the
-    // G-buffer / tail streams land on queues that serialise them behind the light passes
-    // (cornell 1080p 0.601 -> 0.674 ms/frame measured without it)
-    for (int k = 0; k < 2; ++k)
-        if (hipStreamCreateWithFlags(&c->side[k], hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_join[k], hipEventDisableTiming) != hipSuccess) {
-            hk_destroy(c);
-            return HK_ERR_HIP;
-        }
-    if (hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->gb_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_gb_done, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_gb_call[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_gb_call[1], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_post, hipEventDisableTiming) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->dn_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_rf, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_rslot[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_rslot[1], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_gslot[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_gslot[1], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_dn_last, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_frame_mark, hipEventDisableTiming) != hipSuccess) {
+    if (c->sch.create(&c->error) != HK_OK) {
         hk_destroy(c);
         return HK_ERR_HIP;
     }
@@ -922,8 +973,8 @@ void hk_destroy(hk_ctx* c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    if (c->gb_stream) (void)hipStreamSynchronize(c->gb_stream);
-    if (c->dn_stream) (void)hipStreamSynchronize(c->dn_stream);
+    if (c->sch.gb_stream) (void)hipStreamSynchronize(c->sch.gb_stream);
+    if (c->sch.dn_stream) (void)hipStreamSynchronize(c->sch.dn_stream);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     free_targets(c);
     for (int i = 0; i < 9; ++i) release(c->buf[i]);
@@ -945,20 +996,7 @@ void hk_destroy(hk_ctx* c)
         c->event_pool.push_back(t.stop);
     }
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
-    for (auto& r : c->ext_reads) c->ext_pool.push_back(r.second);
-    for (hipEvent_t e : c->ext_pool) (void)hipEventDestroy(e);
-    if (c->ev_frame_mark) (void)hipEventDestroy(c->ev_frame_mark);
-    for (int k = 0; k < 2; ++k) {
-        if (c->side[k]) (void)hipStreamSynchronize(c->side[k]);
-        if (c->side[k]) (void)hipStreamDestroy(c->side[k]);
-        if (c->ev_join[k]) (void)hipEventDestroy(c->ev_join[k]);
-    }
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    for (hipEvent_t e : {c->ev_gb_done, c->ev_gb_call[0], c->ev_gb_call[1], c->ev_post, c->ev_rf, c->ev_rslot[0],
-                         c->ev_rslot[1], c->ev_gslot[0], c->ev_gslot[1], c->ev_dn_last})
-        if (e) (void)hipEventDestroy(e);
-    if (c->gb_stream && c->gb_stream != c->side[0]) (void)hipStreamDestroy(c->gb_stream);
-    if (c->dn_stream && c->dn_stream != c->side[0]) (void)hipStreamDestroy(c->dn_stream);
+    c->sch.destroy();
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1000,7 +1038,7 @@ int hk_scene_upload(hk_ctx* c, const hk_scene_desc* d)
 {
     if (!c || !d) return HK_ERR_INVALID;
     (void)hipSetDevice(c->device);
-    HK_TRY(gb_serialize(c, true));
+    HK_TRY(c->sch.gb_serialize(true));
     const hk_array* arr[9] = {&d->vertices, &d->primitives, &d->asset_nodes, &d->alias_table, &d->instances,
                               &d->instance_nodes, &d->materials, &d->emissive_nodes, &d->emissives};
     const size_t elem[9] = {sizeof(hk_vertex), sizeof(hk_primitive), sizeof(hk_node), sizeof(hk_alias_entry),
@@ -1116,8 +1154,8 @@ int hk_update_instances(hk_ctx* c, const float* models, const float* local_aabbs
         return fail(c, HK_ERR_STATE, "scene BVHs are not bvh-0.7.1 flattened (3n - 2 nodes); cannot rebuild");
     (void)hipSetDevice(c->device);
     hipStream_t st = pick(c, stream);
-    HK_TRY(gb_join(c, st));
-    HK_TRY(gb_serialize(c, false));
+    HK_TRY(c->sch.gb_join(st));
+    HK_TRY(c->sch.gb_serialize(false));
     c->gen++;
     const uint32_t n = count, m = c->count[8], n_alias = c->count[3];
     const uint32_t nm = n > m ? n : m;
@@ -1201,7 +1239,7 @@ int hk_texture_upload(hk_ctx* c, const hk_texture* t, uint32_t count)
 {
     if (!c || (count && !t)) return HK_ERR_INVALID;
     (void)hipSetDevice(c->device);
-    HK_TRY(gb_serialize(c, true));
+    HK_TRY(c->sch.gb_serialize(true));
     std::vector<hk_texture_desc> desc(count);
     uint64_t total = 0;
     c->gen++;
@@ -1241,7 +1279,7 @@ int hk_set_noise(hk_ctx* c, const uint8_t* rgba, uint32_t count, uint32_t size)
     if (!c || !rgba) return HK_ERR_INVALID;
     if (count != 16 || size != 64) return fail(c, HK_ERR_INVALID, "blue noise must be 16 textures of 64x64 RGBA8");
     (void)hipSetDevice(c->device);
-    HK_TRY(gb_serialize(c, true));
+    HK_TRY(c->sch.gb_serialize(true));
     if (!c->noise) HK_HIP(c, hipMalloc(&c->noise, 16 * 64 * 64 * 4));
     HK_HIP(c, hipMemcpy(c->noise, rgba, 16 * 64 * 64 * 4, hipMemcpyHostToDevice));
     c->has_noise = true;
@@ -1306,8 +1344,8 @@ static int resize_impl(hk_ctx* c, uint32_t width, uint32_t height, float ratio, 
         whole = false;
     }
     HK_HIP(c, hipStreamSynchronize(c->stream));
-    HK_HIP(c, hipStreamSynchronize(c->gb_stream));
-    HK_HIP(c, hipStreamSynchronize(c->dn_stream));
+    HK_HIP(c, hipStreamSynchronize(c->sch.gb_stream));
+    HK_HIP(c, hipStreamSynchronize(c->sch.dn_stream));
     free_targets(c);
     c->gen++;
     c->albedo_fresh = false;
@@ -1343,76 +1381,14 @@ static int resize_impl(hk_ctx* c, uint32_t width, uint32_t height, float ratio, 
         c->core_row0 = (int32_t)band_y0 - r0;
         c->core_rows = (int32_t)band_rows;
     }
-    size_t SP = (size_t)width * c->S_rows, sp = (size_t)c->s[0] * c->s_rows;
-    HK_HIP(c, hipMalloc(&c->g_position, SP * sizeof(float4)));
-    HK_HIP(c, hipMalloc(&c->g_normal, SP * sizeof(uint32_t)));
-    HK_HIP(c, hipMalloc(&c->g_depth_gradient, SP * sizeof(float2)));
-    HK_HIP(c, hipMalloc(&c->g_instance_material, SP * sizeof(float2)));
-    HK_HIP(c, hipMalloc(&c->g_velocity_uv, SP * sizeof(float4)));
-    HK_HIP(c, hipMalloc(&c->g_prev_position, SP * sizeof(float4)));
-    HK_HIP(c, hipMalloc(&c->g_prev_velocity_uv, SP * sizeof(float4)));
-    HK_HIP(c, hipMemset(c->g_prev_position, 0, SP * sizeof(float4)));
-    HK_HIP(c, hipMemset(c->g_prev_velocity_uv, 0, SP * sizeof(float4)));
-    HK_HIP(c, hipMalloc(&c->g_prev_normal, SP * sizeof(uint32_t)));
-    HK_HIP(c, hipMalloc(&c->g_prev_depth_gradient, SP * sizeof(float2)));
-    HK_HIP(c, hipMalloc(&c->g_prev_instance_material, SP * sizeof(float2)));
-    HK_HIP(c, hipMalloc(&c->albedo_prev, SP * sizeof(uint2)));
-    HK_HIP(c, hipMemset(c->g_prev_normal, 0, SP * sizeof(uint32_t)));
-    HK_HIP(c, hipMemset(c->g_prev_depth_gradient, 0, SP * sizeof(float2)));
-    HK_HIP(c, hipMemset(c->g_prev_instance_material, 0, SP * sizeof(float2)));
-    HK_HIP(c, hipMemset(c->albedo_prev, 0, SP * sizeof(uint2)));
-    HK_HIP(c, hipMalloc(&c->albedo, SP * sizeof(uint2)));
-    HK_HIP(c, hipMemset(c->g_position, 0, SP * sizeof(float4)));
-    HK_HIP(c, hipMemset(c->g_normal, 0, SP * sizeof(uint32_t)));
-    HK_HIP(c, hipMemset(c->g_depth_gradient, 0, SP * sizeof(float2)));
-    HK_HIP(c, hipMemset(c->g_instance_material, 0, SP * sizeof(float2)));
-    HK_HIP(c, hipMemset(c->g_velocity_uv, 0, SP * sizeof(float4)));
-    HK_HIP(c, hipMemset(c->albedo, 0, SP * sizeof(uint2)));
-    for (int i = 0; i < 3; ++i) {
-        HK_HIP(c, hipMalloc(&c->variance[i], sp * sizeof(float)));
-        HK_HIP(c, hipMalloc(&c->render[i], sp * sizeof(uint2)));
-        HK_HIP(c, hipMalloc(&c->denoised[i], sp * sizeof(uint2)));
-        HK_HIP(c, hipMemset(c->variance[i], 0, sp * sizeof(float)));
-        HK_HIP(c, hipMemset(c->render[i], 0, sp * sizeof(uint2)));
-        HK_HIP(c, hipMalloc(&c->variance_alt[i], sp * sizeof(float)));
-        HK_HIP(c, hipMalloc(&c->render_alt[i], sp * sizeof(uint2)));
-        HK_HIP(c, hipMemset(c->variance_alt[i], 0, sp * sizeof(float)));
-        HK_HIP(c, hipMemset(c->render_alt[i], 0, sp * sizeof(uint2)));
-        HK_HIP(c, hipMemset(c->denoised[i], 0, sp * sizeof(uint2)));
-    }
+    const size_t SP = (size_t)width * c->S_rows, sp = (size_t)c->s[0] * c->s_rows;
     c->res_n = (uint32_t)sp;
     c->win_out = c->win_emi = c->win_ind = -1;
-    for (int i = 0; i < HK_RESERVOIR_BUFFERS; ++i) {
-        HK_HIP(c, hipMalloc(&c->reservoirs[i], 4 * sp * sizeof(uint4)));
-        HK_HIP(c, hipMemset(c->reservoirs[i], 0, 4 * sp * sizeof(uint4)));  // light.rs:355-358 zero-fill
-    }
-    for (int k = 0; k < 2; ++k) {
-        HK_HIP(c, hipMalloc(&c->bgmask[k], sp));
-        c->bg_valid[k] = false;
-    }
-    HK_HIP(c, hipMalloc(&c->gbmask, SP));
-    c->gb_valid = false;
-    HK_HIP(c, hipMalloc(&c->sp_view, VIEW_PLANES * sp * sizeof(uint4)));
-    HK_HIP(c, hipMemset(c->sp_view, 0, VIEW_PLANES * sp * sizeof(uint4)));
-    for (int ch = 0; ch < 3; ++ch) {
-        HK_HIP(c, hipMalloc(&c->internal_variance[ch], sp * sizeof(float)));
-        HK_HIP(c, hipMemset(c->internal_variance[ch], 0, sp * sizeof(float)));
-    }
-    for (int i = 0; i < 4; ++i) {
-        HK_HIP(c, hipMalloc(&c->dn_rgb[i], sp * sizeof(uint4)));
-        HK_HIP(c, hipMemset(c->dn_rgb[i], 0, sp * sizeof(uint4)));
-        HK_HIP(c, hipMalloc(&c->dn_bi[i], sp * sizeof(uint2)));
-        HK_HIP(c, hipMemset(c->dn_bi[i], 0, sp * sizeof(uint2)));
-    }
-    HK_HIP(c, hipMalloc(&c->dn_nd, sp * sizeof(float4)));
-    HK_HIP(c, hipMemset(c->dn_nd, 0, sp * sizeof(float4)));
-    HK_HIP(c, hipMalloc(&c->dn_center, sp * sizeof(float4)));
-    HK_HIP(c, hipMemset(c->dn_center, 0, sp * sizeof(float4)));
-    HK_HIP(c, hipMalloc(&c->dn_den2, sp * sizeof(float)));
-    HK_HIP(c, hipMemset(c->dn_den2, 0, sp * sizeof(float)));
-    for (int k = 0; k < 2; ++k) {
-        HK_HIP(c, hipMalloc(&c->tone_buf[k], sp * sizeof(uint2)));
-        HK_HIP(c, hipMemset(c->tone_buf[k], 0, sp * sizeof(uint2)));
+    for (const Target& t : targets(c)) {
+        if (!t.plane) continue;
+        const size_t bytes = (t.plane == 'S' ? SP : sp) * t.bpp * t.mult;
+        HK_HIP(c, hipMalloc(t.ptr, bytes));
+        if (t.zero) HK_HIP(c, hipMemset(*t.ptr, 0, bytes));
     }
     HK_HIP(c, hipDeviceSynchronize());
     c->sized = true;
@@ -1457,7 +1433,8 @@ int hk_render_gbuffer(hk_ctx* c, const hk_frame_inputs* in, void* stream)
     // Event markers are recorded only on the pipelined path: each one between two kernels of a stream
     // costs it ~6 us (cornell 8-way stripe, where the serial frame is 3 kernels), and the serial path
     // has no other stream waiting on them.
-    const uint32_t e = c->gb_calls & 1u;
+    FrameSchedule& q = c->sch;
+    const uint32_t e = q.gb_calls & 1u;
     hipStream_t gs = st;
     // G-buffer reuse: the slot this frame's planes go to (the other one) already holds exactly them when the
     // k_gbuffer that wrote it saw the same view, jitter and band window, nothing it reads changed since
@@ -1481,80 +1458,62 @@ int hk_render_gbuffer(hk_ctx* c, const hk_frame_inputs* in, void* stream)
     const bool jitter_static = in->jitter == HK_JITTER_NONE;
     const bool still = !c->models_dirty &&
                        std::memcmp(sig.view + 3, sig.view + 3 + 32, 16 * sizeof(float)) == 0;  // previous view = view
-    const bool pipe = pipeline && pipeline_size(c) && !c->gb_serial && c->gb_calls > 0;
-    c->entry_other[e] = c->other_picks;
-    c->entry_epoch[e] = c->frame_st_epoch;
-    c->entry_rf[e] = c->rf_seq;
-    c->entry_clean[e] = c->rf_seq > 0 && c->rf_rec_seq == c->rf_seq && c->other_picks == c->rf_other &&
-                        c->frame_st_epoch == c->rf_epoch;
-    c->gb_tail_seq = 0;
-    c->gb_wait_valid = false;
+    const bool pipe = pipeline && pipeline_size(c) && !q.gb_serial && q.gb_calls > 0;
+    q.entry_other[e] = q.other_picks;
+    q.entry_epoch[e] = q.frame_st_epoch;
+    q.entry_rf[e] = q.rf_seq;
+    q.entry_clean[e] = q.rf_seq > 0 && q.rf_rec_seq == q.rf_seq && q.other_picks == q.rf_other && q.frame_st_epoch == q.rf_epoch;
+    q.gb_tail_seq = 0;
+    q.gb_wait_valid = false;
+    // a new frame: this frame's planes replace the previous ones (prepass.rs:309-317); the one whole-slot swap
+    auto next_slot = [&] {
+        std::swap(c->g, c->g_prev);
+        q.gslot ^= 1u;
+        c->head = in->frame_number & 1u;
+        c->timing_frame = in->frame_number % c->timing_every == 0u;
+    };
     {
-        const uint32_t next = c->gslot ^ 1u;  // the slot this frame's planes go to
+        const uint32_t next = q.gslot ^ 1u;  // the slot this frame's planes go to
         FrameArgs W = pass_window(c, frame_args(c, nullptr, in), GBUFFER_REACH);
         sig.win[0] = W.F.win_row0;
         sig.win[1] = W.F.win_rows;
         const hk_ctx::GbSig& have = c->gsig[next];
         if (c->on(OPT_GBUFFER_REUSE) && still && jitter_static && have.valid && c->velocity_zero &&
             c->albedo_fresh && have.gen == sig.gen && have.win[0] == sig.win[0] &&
-            have.win[1] == sig.win[1] && std::memcmp(have.view, sig.view, sizeof(sig.view)) == 0 && !c->gb_serial && c->gb_calls > 0) {
+            have.win[1] == sig.win[1] && std::memcmp(have.view, sig.view, sizeof(sig.view)) == 0 && !q.gb_serial && q.gb_calls > 0) {
             // (the previous frame's G-buffer came from k_gbuffer too — albedo_fresh, velocity_zero — so both
             // slots hold traced planes of a still camera)
-            std::swap(c->g_position, c->g_prev_position);
-            std::swap(c->g_velocity_uv, c->g_prev_velocity_uv);
-            std::swap(c->g_normal, c->g_prev_normal);
-            std::swap(c->g_depth_gradient, c->g_prev_depth_gradient);
-            std::swap(c->g_instance_material, c->g_prev_instance_material);
-            std::swap(c->albedo, c->albedo_prev);
-            c->gslot = next;
-            c->head = in->frame_number & 1u;
-            c->timing_frame = in->frame_number % c->timing_every == 0u;
+            next_slot();
             // (post_pending stays: a post-process read both slots, and the next launch overwrites one)
             // no launch to reason about: the next hk_render_frame records its fork marker
-            c->gb_call_rec = false;
-            c->gb_on_gs = false;
-            c->gb_calls++;
+            q.gb_call_rec = false;
+            q.gb_on_gs = false;
+            q.gb_calls++;
             c->primary_reused += gbuffer_primary_rays(W);
             return HK_OK;
         }
     }
     if (pipe) {
-        HK_HIP(c, hipEventRecord(c->ev_gb_call[e], st));
-        gs = c->gb_stream;
+        HK_HIP(c, hipEventRecord(q.ev_gb_call[e], st));
+        gs = q.gb_stream;
         // the caller stream at the previous call's entry; when that call was serial (its k_gbuffer ran
         // on st, no record), the caller stream now.  The previous pipelined k_gbuffer is earlier on gs.
-        const uint32_t w = c->gb_call_rec ? e ^ 1u : e;
-        // Frame f-2's tail (dn_stream) read this slot; it waited for ev_rf of a hk_render_frame (gslot_rf).
-        // When that is the one whose ev_rf marked the caller stream where the previous call's entry
-        // marker stands (nothing but the frame sequence ran in between: entry_clean) or a later one, the
-        // tail's event implies the entry marker, and k_gbuffer waits for the tail alone: one packet fewer
-        // ahead of it in the queue it shares with the indirect chain.
-        const uint32_t g = c->gslot ^ 1u;
-        const bool tail_covers = c->gb_call_rec && c->gslot_rec[g] && c->entry_clean[w] && c->entry_rf[w] > 0 &&
-                                 c->gslot_rf[g] >= c->entry_rf[w];
-        if (!tail_covers) HK_HIP(c, hipStreamWaitEvent(gs, c->ev_gb_call[w], 0));
-        c->gb_wait_valid = true;
-        c->gb_wait_other = c->entry_other[w];
-        c->gb_wait_epoch = c->entry_epoch[w];
-        if (c->post_pending) HK_HIP(c, hipStreamWaitEvent(gs, c->ev_post, 0));
-        if (c->gslot_rec[g]) {
-            HK_HIP(c, hipStreamWaitEvent(gs, c->ev_gslot[g], 0));
-            c->gb_tail_seq = c->gslot_seq[g];
+        const uint32_t w = q.gb_call_rec ? e ^ 1u : e;
+        const uint32_t g = q.gslot ^ 1u;
+        if (!q.tail_covers(w, g)) HK_HIP(c, hipStreamWaitEvent(gs, q.ev_gb_call[w], 0));
+        q.gb_wait_valid = true;
+        q.gb_wait_other = q.entry_other[w];
+        q.gb_wait_epoch = q.entry_epoch[w];
+        if (q.post_pending) HK_HIP(c, hipStreamWaitEvent(gs, q.ev_post, 0));
+        if (q.gslot_rec[g]) {
+            HK_HIP(c, hipStreamWaitEvent(gs, q.ev_gslot[g], 0));
+            q.gb_tail_seq = q.gslot_seq[g];
         }
     } else {
-        HK_TRY(gb_join(c, st));
+        HK_TRY(q.gb_join(st));
     }
-    c->post_pending = false;
-    // a new frame: this frame's planes replace the previous ones (prepass.rs:309-317)
-    std::swap(c->g_position, c->g_prev_position);
-    std::swap(c->g_velocity_uv, c->g_prev_velocity_uv);
-    std::swap(c->g_normal, c->g_prev_normal);
-    std::swap(c->g_depth_gradient, c->g_prev_depth_gradient);
-    std::swap(c->g_instance_material, c->g_prev_instance_material);
-    std::swap(c->albedo, c->albedo_prev);
-    c->gslot ^= 1u;
-    c->head = in->frame_number & 1u;
-    c->timing_frame = in->frame_number % c->timing_every == 0u;
+    q.post_pending = false;
+    next_slot();
     FrameArgs A = frame_args(c, nullptr, in);
     ViewArgs V;
     for (int i = 0; i < 3; ++i) V.world_position[i] = in->view.world_position[i];
@@ -1596,29 +1555,29 @@ int hk_render_gbuffer(hk_ctx* c, const hk_frame_inputs* in, void* stream)
             c->gb_key[1] = A.F.win_rows;
         }
         V.bg = c->gbmask;
-        V.bg_need = 1u << c->gslot;  // the planes' physical slot (swapped with gslot above)
+        V.bg_need = 1u << q.gslot;  // the planes' physical slot (swapped with gslot above)
     }
-    for (const void* plane : {(const void*)c->g_position, (const void*)c->g_velocity_uv, (const void*)c->g_normal,
-                              (const void*)c->g_depth_gradient, (const void*)c->g_instance_material, (const void*)c->albedo})
-        HK_TRY(ext_wait(c, gs, plane));
-    timed(c, "gbuffer", gs, [&] { launch_gbuffer(A, V, c->albedo, c->gb_stack_need, gs); });
+    for (const void* plane : std::initializer_list<const void*>{c->g.position, c->g.velocity_uv, c->g.normal, c->g.depth_gradient,
+                                                                c->g.instance_material, c->g.albedo})
+        HK_TRY(q.ext_wait(gs, plane));
+    timed(c, "gbuffer", gs, [&] { launch_gbuffer(A, V, c->g.albedo, c->gb_stack_need, gs); });
     sig.win[0] = A.F.win_row0;
     sig.win[1] = A.F.win_rows;
     sig.valid = V.motion == 0;
-    c->gsig[c->gslot] = sig;
+    c->gsig[q.gslot] = sig;
     if (c->models_dirty) {  // this frame's models become the next frame's previous ones
         HK_HIP(c, hipMemcpy2DAsync(c->prev_models, 64, (const char*)c->buf[4] + offsetof(hk_instance, model),
                                    sizeof(hk_instance), 64, c->count[4], hipMemcpyDeviceToDevice, gs));
         c->models_dirty = false;
     }
     if (gs != st) {
-        HK_HIP(c, hipEventRecord(c->ev_gb_done, gs));
-        c->gb_pending = true;
+        HK_HIP(c, hipEventRecord(q.ev_gb_done, gs));
+        q.gb_pending = true;
     }
-    c->gb_call_rec = pipe;
-    c->gb_on_gs = gs != st;
-    c->gb_serial = false;
-    c->gb_calls++;
+    q.gb_call_rec = pipe;
+    q.gb_on_gs = gs != st;
+    q.gb_serial = false;
+    q.gb_calls++;
     c->albedo_fresh = true;
     HK_HIP(c, hipGetLastError());
     return HK_OK;
@@ -1633,11 +1592,11 @@ int hk_set_gbuffer_plane(hk_ctx* c, int plane, const void* data, size_t bytes, i
     void* dst = nullptr;
     size_t need = 0;
     switch (plane) {
-    case 0: dst = c->g_position; need = SP * 16; break;
-    case 1: dst = c->g_normal; need = SP * 4; break;
-    case 2: dst = c->g_depth_gradient; need = SP * 8; break;
-    case 3: dst = c->g_instance_material; need = SP * 8; break;
-    case 4: dst = c->g_velocity_uv; need = SP * 16; break;
+    case 0: dst = c->g.position; need = SP * 16; break;
+    case 1: dst = c->g.normal; need = SP * 4; break;
+    case 2: dst = c->g.depth_gradient; need = SP * 8; break;
+    case 3: dst = c->g.instance_material; need = SP * 8; break;
+    case 4: dst = c->g.velocity_uv; need = SP * 16; break;
     default: return fail(c, HK_ERR_INVALID, "unknown G-buffer plane");
     }
     if (bytes != need) return fail(c, HK_ERR_INVALID, "G-buffer plane size mismatch");
@@ -1648,17 +1607,17 @@ int hk_set_gbuffer_plane(hk_ctx* c, int plane, const void* data, size_t bytes, i
     c->velocity_zero = false;
     // a new frame's position / velocity plane: the current one becomes the previous (prepass.rs:309-317)
     if (plane == 0) {
-        std::swap(c->g_position, c->g_prev_position);
-        dst = c->g_position;
+        std::swap(c->g.position, c->g_prev.position);
+        dst = c->g.position;
     } else if (plane == 4) {
-        std::swap(c->g_velocity_uv, c->g_prev_velocity_uv);
-        dst = c->g_velocity_uv;
+        std::swap(c->g.velocity_uv, c->g_prev.velocity_uv);
+        dst = c->g.velocity_uv;
     }
     (void)hipSetDevice(c->device);
     hipStream_t st = pick(c, stream);
-    HK_TRY(gb_join(c, st));
-    HK_TRY(ext_wait(c, st, dst));
-    c->gb_serial = true;
+    HK_TRY(c->sch.gb_join(st));
+    HK_TRY(c->sch.ext_wait(st, dst));
+    HK_TRY(c->sch.gb_serialize(false));
     HK_HIP(c, hipMemcpyAsync(dst, data, bytes, device_ptr ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
     if (!device_ptr) HK_HIP(c, hipStreamSynchronize(st));
     return HK_OK;
@@ -1703,7 +1662,7 @@ static int bg_mask(hk_ctx* c, int k, const FrameArgs& A, bool use, bool pair, hi
     C.bg = c->bgmask[k];
     // targets of this frame: reservoir parity (the temporal buffer), render / variance slot, and
     // (pair: no spatial reuse pass rewrites it) the spatial pair, both of whose buffers are stored
-    C.bg_need = (1u << (A.F.number & 1u)) | (4u << c->rslot) | (pair ? 16u : 0u);
+    C.bg_need = (1u << (A.F.number & 1u)) | (4u << c->sch.rslot) | (pair ? 16u : 0u);
     return HK_OK;
 }
 
@@ -1726,39 +1685,34 @@ int hk_render_frame(hk_ctx* c, const hk_settings* settings, const hk_frame_input
     // targets are the other slot, last read by frame f-2's denoise / tone-sum, so frame f-1's tail
     // (on dn_stream) can still be running while this frame's light passes start.
     const bool swap = dn_pipeline_enabled(c) && settings->indirect_bounces >= 1u;
-    // This frame's G-buffer ran pipelined on gb_stream after the caller stream at the previous
-    // hk_render_gbuffer's entry (W), and since W only the frame sequence ran, on this stream (no other
-    // API call, no stream change): frame f-1's hk_render_frame, denoise, tone-sum and this frame's
-    // hk_render_gbuffer.  See the fork below.
-    const bool gb_fresh = c->gb_on_gs && c->gb_wait_valid && c->other_picks == c->gb_wait_other &&
-                          c->frame_st_epoch == c->gb_wait_epoch && c->gb_pending;
+    FrameSchedule& q = c->sch;
+    const bool gb_fresh = q.gb_fresh();  // see the fork below
     if (swap) {
         for (int ch = 0; ch < 3; ++ch) {
             std::swap(c->render[ch], c->render_alt[ch]);
             std::swap(c->variance[ch], c->variance_alt[ch]);
         }
-        c->rslot ^= 1u;
+        q.rslot ^= 1u;
     }
-    // the render slot's last reader (frame f-2's tail) — also covered by ev_gb_done when k_gbuffer waited
-    // for that tail or a later one (dn_stream is in order); each wait packet costs the stream latency
-    const bool slot_wait = swap && c->rslot_rec[c->rslot];
-    const bool slot_covered = gb_fresh && c->gb_pending && c->rslot_seq[c->rslot] <= c->gb_tail_seq;
-    if (slot_wait && !slot_covered) HK_HIP(c, hipStreamWaitEvent(st, c->ev_rslot[c->rslot], 0));
+    // the render slot's last reader (frame f-2's tail); each wait packet costs the stream latency
+    const bool slot_wait = swap && q.rslot_rec[q.rslot];
+    const bool slot_covered = q.slot_covered();
+    if (slot_wait && !slot_covered) HK_HIP(c, hipStreamWaitEvent(st, q.ev_rslot[q.rslot], 0));
     // (k_albedo rewrites the albedo plane a previous tail may still read: full join then)
-    HK_TRY(gb_join(c, st, !swap || !c->albedo_fresh));
+    HK_TRY(q.gb_join(st, !swap || !c->albedo_fresh));
     // foreign-stream copies of the planes this call writes wait on st; when the indirect chain's own planes
     // are among them, its side stream must fork from st after those waits (no fork shortcut below)
     bool had_ext = false;
-    for (const auto& r : c->ext_reads) had_ext |= r.first == c->render[2] || r.first == c->variance[2];
-    if (!c->ext_reads.empty()) {
-        HK_TRY(ext_wait(c, st, c->albedo));
+    for (const auto& r : q.ext_reads) had_ext |= r.first == c->render[2] || r.first == c->variance[2];
+    if (!q.ext_reads.empty()) {
+        HK_TRY(q.ext_wait(st, c->g.albedo));
         for (int ch = 0; ch < 3; ++ch) {
-            HK_TRY(ext_wait(c, st, c->render[ch]));
-            HK_TRY(ext_wait(c, st, c->variance[ch]));
+            HK_TRY(q.ext_wait(st, c->render[ch]));
+            HK_TRY(q.ext_wait(st, c->variance[ch]));
         }
     }
-    c->rf_swapped = swap;
-    c->tail_open = false;
+    q.rf_swapped = swap;
+    q.tail_open = false;
     c->head = in->frame_number & 1u;
     c->timing_frame = in->frame_number % c->timing_every == 0u;
     FrameArgs A = frame_args(c, settings, in);
@@ -1772,11 +1726,11 @@ int hk_render_frame(hk_ctx* c, const hk_settings* settings, const hk_frame_input
     const bool fork = c->on(OPT_CHANNEL_STREAMS);
     // fork_events: the indirect chain really runs on the side stream (not when k_light_merged takes it)
     bool fork_events = false;
-    hipStream_t s1 = st, s2 = fork ? c->side[1] : st;
+    hipStream_t s1 = st, s2 = fork ? q.side[1] : st;
     const FrameArgs A_all = A;
     if (!c->albedo_fresh) {
         const FrameArgs AG = pass_window(c, A_all, GBUFFER_REACH);
-        timed(c, "full_screen_albedo", st, [&] { launch_albedo(AG, c->albedo, st); });
+        timed(c, "full_screen_albedo", st, [&] { launch_albedo(AG, c->g.albedo, st); });
     }
     // per-pass row windows of a band (pass_window): each channel's temporal pass on the rows its spatial
     // pass reads (core +-(OUT + that channel's range): direct_lit has no spatial pass, light.rs:656-676),
@@ -1835,7 +1789,7 @@ int hk_render_frame(hk_ctx* c, const hk_settings* settings, const hk_frame_input
     // (one grid for all three channels: the wider window)
     if (merge) A = AE = pass_window(c, A_all, std::max(c->win_ind, c->win_emi));
     if (fork && !merge) {
-        if (gb_fresh && c->rf_side_only && swap && c->albedo_fresh && !had_ext) {
+        if (gb_fresh && q.rf_side_only && swap && c->albedo_fresh && !had_ext) {
             // The fork marker would make the side stream wait for the caller stream here.  What the
             // indirect chain reads of that stream's work: the work before W (k_gbuffer waited for it),
             // frame f-1's hk_render_frame (its indirect chain ran on the side stream itself; the rest of
@@ -1845,11 +1799,11 @@ int hk_render_frame(hk_ctx* c, const hk_settings* settings, const hk_frame_input
             // waited for that tail or a later one) and the G-buffer.  So the side stream waits for
             // ev_gb_done alone: every packet queued ahead of a kernel delays it, and the side stream
             // shares its hardware queue with gb_stream (cornell 1080p 0.472 -> 0.45 ms/frame).
-            if (slot_wait && !slot_covered) HK_HIP(c, hipStreamWaitEvent(s2, c->ev_rslot[c->rslot], 0));
-            HK_HIP(c, hipStreamWaitEvent(s2, c->ev_gb_done, 0));
+            if (slot_wait && !slot_covered) HK_HIP(c, hipStreamWaitEvent(s2, q.ev_rslot[q.rslot], 0));
+            HK_HIP(c, hipStreamWaitEvent(s2, q.ev_gb_done, 0));
         } else {
-            HK_HIP(c, hipEventRecord(c->ev_fork, st));
-            HK_HIP(c, hipStreamWaitEvent(s2, c->ev_fork, 0));
+            HK_HIP(c, hipEventRecord(q.ev_fork, st));
+            HK_HIP(c, hipStreamWaitEvent(s2, q.ev_fork, 0));
         }
         fork_events = true;
     }
@@ -1886,16 +1840,16 @@ int hk_render_frame(hk_ctx* c, const hk_settings* settings, const hk_frame_input
         if (settings->indirect_spatial_reuse) timed(c, "indirect_spatial_reuse", s2, [&] { launch_spatial(AS, C2, false, s2); });
     }
     if (fork_events) {
-        HK_HIP(c, hipEventRecord(c->ev_join[1], s2));
-        HK_HIP(c, hipStreamWaitEvent(st, c->ev_join[1], 0));
+        HK_HIP(c, hipEventRecord(q.ev_join[1], s2));
+        HK_HIP(c, hipStreamWaitEvent(st, q.ev_join[1], 0));
     }
-    c->rf_side_only = fork_events && c->albedo_fresh;  // (no k_albedo on the caller stream)
-    c->rf_seq++;
+    q.rf_side_only = fork_events && c->albedo_fresh;  // (no k_albedo on the caller stream)
+    q.rf_seq++;
     if (swap) {
-        HK_HIP(c, hipEventRecord(c->ev_rf, st));
-        c->rf_rec_seq = c->rf_seq;
-        c->rf_other = c->other_picks;
-        c->rf_epoch = c->frame_st_epoch;
+        HK_HIP(c, hipEventRecord(q.ev_rf, st));
+        q.rf_rec_seq = q.rf_seq;
+        q.rf_other = q.other_picks;
+        q.rf_epoch = q.frame_st_epoch;
     }
     HK_HIP(c, hipGetLastError());
     return HK_OK;
@@ -1912,20 +1866,20 @@ int hk_denoise(hk_ctx* c, const hk_settings* settings, const hk_frame_inputs* in
     (void)hipSetDevice(c->device);
     hipStream_t caller = pick_frame(c, stream);
     // after a slot-swapping hk_render_frame: on dn_stream, next to the following frame's passes
-    const bool async = c->rf_swapped;
-    hipStream_t st = async ? c->dn_stream : caller;
-    if (async) HK_TRY(tail_begin(c));
-    else HK_TRY(gb_join(c, st));
+    const bool async = c->sch.rf_swapped;
+    hipStream_t st = async ? c->sch.dn_stream : caller;
+    if (async) HK_TRY(c->sch.tail_begin());
+    else HK_TRY(c->sch.gb_join(st));
     for (int ch = 0; ch < 3; ++ch) {
-        HK_TRY(ext_wait(c, st, c->denoised[ch]));
-        HK_TRY(ext_wait(c, st, c->internal_variance[ch]));  // HK_OUT_DENOISE_INTERNAL_VARIANCE copies
+        HK_TRY(c->sch.ext_wait(st, c->denoised[ch]));
+        HK_TRY(c->sch.ext_wait(st, c->internal_variance[ch]));  // HK_OUT_DENOISE_INTERNAL_VARIANCE copies
     }
     FrameArgs A = frame_args(c, settings, in);
     int channels = settings->indirect_bounces == 0u ? 2 : 3;  // post_process.rs:949-954
     DenoiseArgs D;
     std::memset(&D, 0, sizeof(D));
     D.channels = channels;
-    D.albedo = c->albedo;
+    D.albedo = c->g.albedo;
     for (int ch = 0; ch < 3; ++ch) {
         D.render[ch] = c->render[ch];
         D.variance[ch] = c->variance[ch];
@@ -1948,7 +1902,7 @@ int hk_denoise(hk_ctx* c, const hk_settings* settings, const hk_frame_inputs* in
         const FrameArgs AL = pass_window(c, A, LEVEL_REACH[level]);
         timed(c, "denoise", st, [&] { launch_denoise(AL, D, level, st); });
     }
-    if (async) HK_TRY(tail_end(c));
+    if (async) HK_TRY(c->sch.tail_end());
     HK_HIP(c, hipGetLastError());
     return HK_OK;
 }
@@ -1960,10 +1914,10 @@ int hk_tone_sum(hk_ctx* c, const hk_settings* settings, void* stream)
     if (!settings) return fail(c, HK_ERR_INVALID, "null settings");
     (void)hipSetDevice(c->device);
     // after a slot-swapping hk_render_frame: on dn_stream (after that frame's denoise, if any)
-    const bool async = c->rf_swapped;
-    hipStream_t st = async ? c->dn_stream : pick_frame(c, stream);
-    if (async) HK_TRY(tail_begin(c));
-    else HK_TRY(gb_join(c, st));
+    const bool async = c->sch.rf_swapped;
+    hipStream_t st = async ? c->sch.dn_stream : pick_frame(c, stream);
+    if (async) HK_TRY(c->sch.tail_begin());
+    else HK_TRY(c->sch.gb_join(st));
     hk_frame_inputs dummy;
     std::memset(&dummy, 0, sizeof(dummy));
     const FrameArgs A = pass_window(c, frame_args(c, settings, &dummy), 0);
@@ -1972,9 +1926,9 @@ int hk_tone_sum(hk_ctx* c, const hk_settings* settings, void* stream)
     T.emissive = settings->denoise ? c->denoised[1] : c->render[1];
     T.indirect = settings->indirect_bounces == 0u ? nullptr : (settings->denoise ? c->denoised[2] : c->render[2]);
     T.output = c->tone_buf[c->head];
-    HK_TRY(ext_wait(c, st, T.output));
+    HK_TRY(c->sch.ext_wait(st, T.output));
     timed(c, "tone_mapping", st, [&] { launch_tone(A, T, st); });
-    if (async) HK_TRY(tail_end(c));
+    if (async) HK_TRY(c->sch.tail_end());
     HK_HIP(c, hipGetLastError());
     return HK_OK;
 }
@@ -1987,11 +1941,11 @@ int hk_post_process(hk_ctx* c, const hk_settings* st, const hk_frame_inputs* in,
     if (c->S_rows != (int32_t)c->S[1]) return fail(c, HK_ERR_STATE, "hk_post_process needs a whole-frame context");
     (void)hipSetDevice(c->device);
     hipStream_t s = pick(c, stream);
-    HK_TRY(gb_join(c, s));
+    HK_TRY(c->sch.gb_join(s));
     c->head = in->frame_number & 1u;
     const uint32_t head = c->head;
-    HK_TRY(ext_wait(c, s, c->upscale));
-    HK_TRY(ext_wait(c, s, c->taa_buf[head]));
+    HK_TRY(c->sch.ext_wait(s, c->upscale));
+    HK_TRY(c->sch.ext_wait(s, c->taa_buf[head]));
     // post_process.rs:663-731 sizes: ceil(S * scale), scale = 1 / ratio, x 2 after SMAA TU4x
     float scale = 1.0f / c->ratio;
     const bool smaa = st->upscale == 0u, taa = st->taa == 0u;
@@ -2005,11 +1959,11 @@ int hk_post_process(hk_ctx* c, const hk_settings* st, const hk_frame_inputs* in,
         return t;
     };
     const uint32_t S0 = c->S[0], S1 = c->S[1];
-    P.in.position = tex(c->g_position, S0, S1, 0, 4);
-    P.in.previous_position = tex(c->g_prev_position, S0, S1, 0, 4);
-    P.in.velocity_uv = tex(c->g_velocity_uv, S0, S1, 0, 4);
-    P.in.previous_velocity_uv = tex(c->g_prev_velocity_uv, S0, S1, 0, 4);
-    P.in.instance_material = tex(c->g_instance_material, S0, S1, 0, 2);
+    P.in.position = tex(c->g.position, S0, S1, 0, 4);
+    P.in.previous_position = tex(c->g_prev.position, S0, S1, 0, 4);
+    P.in.velocity_uv = tex(c->g.velocity_uv, S0, S1, 0, 4);
+    P.in.previous_velocity_uv = tex(c->g_prev.velocity_uv, S0, S1, 0, 4);
+    P.in.instance_material = tex(c->g.instance_material, S0, S1, 0, 2);
     hk_pp_tex taa_input = tex(c->tone_buf[head], c->s[0], c->s[1], 1, 4);
     if (smaa) {
         scale *= 2.0f;
@@ -2043,8 +1997,8 @@ int hk_post_process(hk_ctx* c, const hk_settings* st, const hk_frame_inputs* in,
         timed(c, "taa_jasmine", s, [&] { launch_taa(P, s); });
     }
     // the next k_gbuffer overwrites the previous-frame planes read here
-    HK_HIP(c, hipEventRecord(c->ev_post, s));
-    c->post_pending = true;
+    HK_HIP(c, hipEventRecord(c->sch.ev_post, s));
+    c->sch.post_pending = true;
     HK_HIP(c, hipGetLastError());
     return HK_OK;
 }
@@ -2057,10 +2011,10 @@ int hk_accumulate(hk_ctx* c, int reset, void* stream)
     int rc = check_ready(c, false);
     if (rc) return rc;
     (void)hipSetDevice(c->device);
-    const bool async = c->rf_swapped && c->tail_open;  // this frame's tone-sum ran in the tail
-    hipStream_t st = async ? c->dn_stream : pick_frame(c, stream);
-    if (async) HK_TRY(tail_begin(c));
-    else HK_TRY(gb_join(c, st));
+    const bool async = c->sch.rf_swapped && c->sch.tail_open;  // this frame's tone-sum ran in the tail
+    hipStream_t st = async ? c->sch.dn_stream : pick_frame(c, stream);
+    if (async) HK_TRY(c->sch.tail_begin());
+    else HK_TRY(c->sch.gb_join(st));
     const size_t n = (size_t)c->s[0] * (size_t)c->s_rows;
     if (!c->accum) {
         HK_HIP(c, hipMalloc(&c->accum, n * sizeof(float4)));
@@ -2070,7 +2024,7 @@ int hk_accumulate(hk_ctx* c, int reset, void* stream)
     }
     if (reset) c->accum_n = 0;
     timed(c, "accumulate", st, [&] { launch_accumulate(c->tone_buf[c->head], c->accum, (uint32_t)n, reset, st); });
-    if (async) HK_TRY(tail_end(c));
+    if (async) HK_TRY(c->sch.tail_end());
     HK_HIP(c, hipGetLastError());
     c->accum_n += 1;
     return HK_OK;
@@ -2082,14 +2036,14 @@ int hk_resolve_accumulation(hk_ctx* c, void* stream)
     if (rc) return rc;
     if (!c->accum || c->accum_n == 0) return fail(c, HK_ERR_STATE, "nothing accumulated (hk_accumulate)");
     (void)hipSetDevice(c->device);
-    const bool async = c->rf_swapped && c->tail_open;
-    hipStream_t st = async ? c->dn_stream : pick_frame(c, stream);
-    if (async) HK_TRY(tail_begin(c));
-    else HK_TRY(gb_join(c, st));
-    HK_TRY(ext_wait(c, st, c->accum_out));
+    const bool async = c->sch.rf_swapped && c->sch.tail_open;
+    hipStream_t st = async ? c->sch.dn_stream : pick_frame(c, stream);
+    if (async) HK_TRY(c->sch.tail_begin());
+    else HK_TRY(c->sch.gb_join(st));
+    HK_TRY(c->sch.ext_wait(st, c->accum_out));
     const size_t n = (size_t)c->s[0] * (size_t)c->s_rows;
     timed(c, "resolve", st, [&] { launch_resolve(c->accum, (uint32_t)n, (float)c->accum_n, c->accum_out, st); });
-    if (async) HK_TRY(tail_end(c));
+    if (async) HK_TRY(c->sch.tail_end());
     HK_HIP(c, hipGetLastError());
     return HK_OK;
 }
@@ -2098,8 +2052,9 @@ static void* output_ptr(hk_ctx* c, int id, uint32_t* w, uint32_t* h, uint32_t* b
 {
     uint32_t W = c->s[0], H = (uint32_t)c->s_rows, B = 8;
     void* p = nullptr;
+    auto S_plane = [&](void* plane, uint32_t bpp) { p = plane, W = c->S[0], H = (uint32_t)c->S_rows, B = bpp; };
     switch (id) {
-    case HK_OUT_ALBEDO: p = c->albedo; W = c->S[0]; H = (uint32_t)c->S_rows; break;
+    case HK_OUT_ALBEDO: S_plane(c->g.albedo, 8); break;
     case HK_OUT_VARIANCE_DIRECT: case HK_OUT_VARIANCE_EMISSIVE: case HK_OUT_VARIANCE_INDIRECT:
         p = c->variance[id - HK_OUT_VARIANCE_DIRECT]; B = 4; break;
     case HK_OUT_RENDER_DIRECT: case HK_OUT_RENDER_EMISSIVE: case HK_OUT_RENDER_INDIRECT:
@@ -2111,11 +2066,11 @@ static void* output_ptr(hk_ctx* c, int id, uint32_t* w, uint32_t* h, uint32_t* b
     case HK_OUT_UPSCALED: p = c->upscale; W = c->upscale_wh[0]; H = c->upscale_wh[1]; break;
     case HK_OUT_TAA: p = c->taa_buf[c->head]; W = c->taa_wh[0]; H = c->taa_wh[1]; break;
     case HK_OUT_ACCUMULATED: p = c->accum_out; break;
-    case HK_OUT_GBUF_POSITION: p = c->g_position; W = c->S[0]; H = (uint32_t)c->S_rows; B = 16; break;
-    case HK_OUT_GBUF_NORMAL: p = c->g_normal; W = c->S[0]; H = (uint32_t)c->S_rows; B = 4; break;
-    case HK_OUT_GBUF_DEPTH_GRADIENT: p = c->g_depth_gradient; W = c->S[0]; H = (uint32_t)c->S_rows; B = 8; break;
-    case HK_OUT_GBUF_INSTANCE_MATERIAL: p = c->g_instance_material; W = c->S[0]; H = (uint32_t)c->S_rows; B = 8; break;
-    case HK_OUT_GBUF_VELOCITY_UV: p = c->g_velocity_uv; W = c->S[0]; H = (uint32_t)c->S_rows; B = 16; break;
+    case HK_OUT_GBUF_POSITION: S_plane(c->g.position, 16); break;
+    case HK_OUT_GBUF_NORMAL: S_plane(c->g.normal, 4); break;
+    case HK_OUT_GBUF_DEPTH_GRADIENT: S_plane(c->g.depth_gradient, 8); break;
+    case HK_OUT_GBUF_INSTANCE_MATERIAL: S_plane(c->g.instance_material, 8); break;
+    case HK_OUT_GBUF_VELOCITY_UV: S_plane(c->g.velocity_uv, 16); break;
     case HK_OUT_DENOISE_INTERNAL_VARIANCE: p = c->internal_variance[c->last_denoised_channels - 1]; B = 4; break;
     default: return nullptr;
     }
@@ -2161,7 +2116,7 @@ int hk_sync(hk_ctx* c, void* stream)
 {
     if (!c) return HK_ERR_INVALID;
     (void)hipSetDevice(c->device);
-    return gb_join(c, pick(c, stream));
+    return c->sch.gb_join(pick(c, stream));
 }
 
 int hk_get_output(hk_ctx* c, int id, void* dst, size_t bytes, int to_host, void* stream)
@@ -2175,7 +2130,7 @@ int hk_get_output(hk_ctx* c, int id, void* dst, size_t bytes, int to_host, void*
     if (bytes != need) return fail(c, HK_ERR_INVALID, "output size mismatch");
     (void)hipSetDevice(c->device);
     hipStream_t st = pick(c, stream);
-    HK_TRY(gb_join(c, st));
+    HK_TRY(c->sch.gb_join(st));
     HK_HIP(c, hipMemcpyAsync(dst, p, bytes, to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
     if (to_host) HK_HIP(c, hipStreamSynchronize(st));
     return HK_OK;
@@ -2219,16 +2174,16 @@ static int copy_output_rect(hk_ctx* c, int id, uint32_t row0, uint32_t rows, uin
     // never waits for the copy, and the plane's next writer waits for it (ext_reads).  The tone-mapped,
     // accumulated and denoised planes of a pipelined frame come from its tail (dn_stream, ev_dn_last).
     const hipStream_t given = stream ? (hipStream_t)stream : c->stream;
-    const bool foreign = c->frame_st && given != c->frame_st && !to_host;
+    const bool foreign = c->sch.frame_st && given != c->sch.frame_st && !to_host;
     hipStream_t st = foreign ? given : pick(c, stream);
-    HK_TRY(gb_join(c, st));
+    HK_TRY(c->sch.gb_join(st));
     if (foreign) {
-        const bool from_tail = c->rf_swapped && c->tail_open &&
+        const bool from_tail = c->sch.rf_swapped && c->sch.tail_open &&
                                (id == HK_OUT_TONE_MAPPED || id == HK_OUT_TONE_MAPPED_PREVIOUS || id == HK_OUT_ACCUMULATED ||
                                 (id >= HK_OUT_DENOISED_DIRECT && id <= HK_OUT_DENOISED_INDIRECT));
         if (!from_tail) {
-            HK_HIP(c, hipEventRecord(c->ev_frame_mark, c->frame_st));
-            HK_HIP(c, hipStreamWaitEvent(st, c->ev_frame_mark, 0));
+            HK_HIP(c, hipEventRecord(c->sch.ev_frame_mark, c->sch.frame_st));
+            HK_HIP(c, hipStreamWaitEvent(st, c->sch.ev_frame_mark, 0));
         }
     }
     size_t pitch = (size_t)w * b;
@@ -2242,24 +2197,24 @@ static int copy_output_rect(hk_ctx* c, int id, uint32_t row0, uint32_t rows, uin
     if (foreign) {
         // entries whose copies have completed go back to the pool (a plane nobody rewrites would otherwise keep its
         // entries, and ext_reads would grow with every copy of it)
-        for (size_t k = 0; k < c->ext_reads.size();) {
-            if (hipEventQuery(c->ext_reads[k].second) == hipSuccess) {
-                c->ext_pool.push_back(c->ext_reads[k].second);
-                c->ext_reads[k] = c->ext_reads.back();
-                c->ext_reads.pop_back();
+        for (size_t k = 0; k < c->sch.ext_reads.size();) {
+            if (hipEventQuery(c->sch.ext_reads[k].second) == hipSuccess) {
+                c->sch.ext_pool.push_back(c->sch.ext_reads[k].second);
+                c->sch.ext_reads[k] = c->sch.ext_reads.back();
+                c->sch.ext_reads.pop_back();
             } else {
                 ++k;
             }
         }
         hipEvent_t e = nullptr;
-        if (!c->ext_pool.empty()) {
-            e = c->ext_pool.back();
-            c->ext_pool.pop_back();
+        if (!c->sch.ext_pool.empty()) {
+            e = c->sch.ext_pool.back();
+            c->sch.ext_pool.pop_back();
         } else {
             HK_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
         }
         HK_HIP(c, hipEventRecord(e, st));
-        c->ext_reads.emplace_back(p, e);
+        c->sch.ext_reads.emplace_back(p, e);
     }
     return HK_OK;
 }
@@ -2271,7 +2226,7 @@ int hk_dump_reservoirs(hk_ctx* c, int id, hk_packed_reservoir* dst, size_t count
     if (count != c->res_n) return fail(c, HK_ERR_INVALID, "reservoir count mismatch");
     (void)hipSetDevice(c->device);
     hipStream_t st = pick(c, stream);
-    HK_TRY(gb_join(c, st));
+    HK_TRY(c->sch.gb_join(st));
     std::vector<uint4> planes((size_t)4 * c->res_n);
     HK_HIP(c, hipMemcpyAsync(planes.data(), c->reservoirs[id], planes.size() * sizeof(uint4), hipMemcpyDeviceToHost, st));
     HK_HIP(c, hipStreamSynchronize(st));
@@ -2290,7 +2245,7 @@ int hk_load_reservoirs(hk_ctx* c, int id, const hk_packed_reservoir* src, size_t
     if (count != c->res_n) return fail(c, HK_ERR_INVALID, "reservoir count mismatch");
     (void)hipSetDevice(c->device);
     hipStream_t st = pick(c, stream);
-    HK_TRY(gb_join(c, st));
+    HK_TRY(c->sch.gb_join(st));
     std::vector<uint4> planes((size_t)4 * c->res_n);
     const ResBuf layout{nullptr, c->res_n};
     for (size_t i = 0; i < count; ++i) {
@@ -2333,11 +2288,11 @@ int hk_reservoir_rows(hk_ctx* c, int id, int32_t frame_row0, int32_t rows, void*
     if (rows == 0) return HK_OK;
     (void)hipSetDevice(c->device);
     hipStream_t st = pick(c, stream);
-    HK_TRY(gb_join(c, st));
+    HK_TRY(c->sch.gb_join(st));
     // after every pass the frame sequence enqueued (its side streams joined its stream before returning)
-    if (c->frame_st && c->frame_st != st) {
-        HK_HIP(c, hipEventRecord(c->ev_frame_mark, c->frame_st));
-        HK_HIP(c, hipStreamWaitEvent(st, c->ev_frame_mark, 0));
+    if (c->sch.frame_st && c->sch.frame_st != st) {
+        HK_HIP(c, hipEventRecord(c->sch.ev_frame_mark, c->sch.frame_st));
+        HK_HIP(c, hipStreamWaitEvent(st, c->sch.ev_frame_mark, 0));
     }
     const size_t w = c->s[0], n = (size_t)rows * w;
     for (size_t k = 0; k < 4; ++k) {
@@ -2354,7 +2309,7 @@ int hk_reset_counters(hk_ctx* c, void* stream)
 {
     if (!c) return HK_ERR_INVALID;
     (void)hipSetDevice(c->device);
-    HK_TRY(gb_join(c, pick(c, stream)));
+    HK_TRY(c->sch.gb_join(pick(c, stream)));
     HK_HIP(c, hipMemsetAsync(c->counters, 0, COUNTER_BYTES, pick(c, stream)));
     c->primary_reused = 0;
     return HK_OK;
@@ -2365,7 +2320,7 @@ int hk_read_counters(hk_ctx* c, hk_counters* out, void* stream)
     if (!c || !out) return HK_ERR_INVALID;
     (void)hipSetDevice(c->device);
     hipStream_t st = pick(c, stream);
-    HK_TRY(gb_join(c, st));
+    HK_TRY(c->sch.gb_join(st));
     std::vector<unsigned long long> v(3 * COUNTER_SPAN);
     HK_HIP(c, hipMemcpyAsync(v.data(), c->counters, COUNTER_BYTES, hipMemcpyDeviceToHost, st));
     HK_HIP(c, hipStreamSynchronize(st));
@@ -2417,7 +2372,7 @@ int hk_trace(hk_ctx* c, const float* rays, const float* max_d, const float* earl
     if (n == 0) return HK_OK;
     (void)hipSetDevice(c->device);
     hipStream_t st = pick(c, stream);
-    HK_TRY(gb_join(c, st));
+    HK_TRY(c->sch.gb_join(st));
     FrameArgs A = frame_args(c, nullptr, nullptr);
     if (device_ptrs) {
         launch_trace(A.sc, rays, max_d, early_d, excl, n, (uint32_t*)hits, c->counters, st);

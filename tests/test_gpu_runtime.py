@@ -212,6 +212,42 @@ def test_foreign_copies_of_the_internal_variance():
     hip.hipStreamDestroy(stream)
 
 
+def test_resize_between_pipelined_frames_bit_exact():
+    """hk_resize in the middle of a pipelined sequence (pipeline_min_px = 0; denoise and indirect spatial reuse, so
+    the G-buffer stream and the tail stream both carry work): frames 0-3 at 64x64 are queued without any readback,
+    which leaves the frame schedule in mid-flight; then the context is resized to the odd 63x47 for frames 4-7
+    and back to 64x64 for frames 8-11.  A resize zero-fills all history and resets the schedule
+    (FrameSchedule::reset), so every frame after it equals a fresh oracle of that size fed the same frame
+    numbers: 17 outputs and 10 reservoir buffers bit for bit, and the segment's ray counters."""
+    from hikari_amd import HikariSettings, Upscale, frame_inputs, load_noise
+    from oracle import Oracle
+    st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=True, denoise=True)
+    scene, cam, lights, r, o = _pair("cornell", 64, 64, st, options={"pipeline_min_px": 0})
+    desc = scene.build()
+    s = st.to_c()
+
+    def frame(x, f, w, h):
+        fi = frame_inputs(f, cam, lights, w, h)
+        x.render_gbuffer(fi)
+        x.render_frame(s, fi)
+        x.denoise(s, fi)
+        x.tone_sum(s)
+
+    for f in range(4):
+        frame(r, f, 64, 64)
+    errors = []
+    for first, (w, h) in ((4, (63, 47)), (8, (64, 64))):
+        r.resize(w, h, st.upscale.ratio())
+        r.reset_counters()
+        o = Oracle(desc, load_noise(), w, h, st.upscale.ratio(), textures=scene.textures)
+        for f in range(first, first + 4):
+            frame(r, f, w, h)
+            frame(o, f, w, h)
+            _compare(r, o, f, errors)
+        assert not errors, "\n".join(errors[:20])
+        assert r.counters() == o.counters(), f"frames {first}-{first + 3} at {w}x{h}"
+
+
 def test_option_values():
     """hk_set_option: on/off switches and modes take integers only (0.5 used to count as on), the
     pixel-count thresholds any value in range; unknown keys and out-of-range values are refused."""
