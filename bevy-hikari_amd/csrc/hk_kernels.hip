@@ -1,15 +1,26 @@
 // hk_kernels.hip — gfx950 kernels of the integrator and denoiser.
 //
-// Entry point map (reference -> kernel):
-//   light.wgsl:1019 full_screen_albedo          -> k_albedo
-//   light.wgsl:1044 direct_lit (+RENDER_EMISSIVE / +EMISSIVE_LIT) -> k_direct<EMISSIVE_LIT, RENDER_EMISSIVE>
-//   light.wgsl:1263 indirect_lit_ambient (+MULTIPLE_BOUNCES)      -> k_indirect<MULTI>
-//   light.wgsl:1503 spatial_reuse (+EMISSIVE_LIT)                 -> k_spatial<EMISSIVE_LIT>
-//   denoise.wgsl:135 demodulation (x3 channels)                   -> k_demod3<C>
-//   denoise.wgsl:215 denoise (DENOISE_LEVEL_0..3, FIREFLY) x3 ch  -> k_denoise3<C, LEVEL>
-//   tone_mapping.wgsl:21 tone_mapping                             -> k_tone
-//   prepass.wgsl:84-100 (raster G-buffer)                         -> k_gbuffer (primary rays)
-//   light.wgsl:442 traverse_top                                   -> k_trace
+// Entry point map.  A light-pass kernel is a one-line __global__ wrapper (it carries the launch attributes) around a
+// shared HKD body; the launcher's condition picks the wrapper.
+//   kernel                      body (reference)                            launcher: condition
+//   k_gbuffer, k_albedo         own (prepass.wgsl:84-100, light.wgsl:1019)   launch_gbuffer: staging / stack depth; launch_albedo
+//   k_direct<EL,RE,LDS,VAL>     direct_kernel (light.wgsl:1044 direct_lit)   launch_direct: the emissive pass; direct_lit below
+//                                                                            direct_w4_min_px pixels
+//   k_direct_lit_w4<LDS,VAL>    direct_kernel<false,true>, 4 waves per SIMD  launch_direct: direct_lit from direct_w4_min_px up
+//   k_direct_fused<LDS,VD,VE>   direct_fused_kernel (both direct passes)     launch_direct_fused: fused_w4 off, or a staged
+//                                                                            emissive-validation frame
+//   k_direct_fused_w4<LDS,VD,VE> direct_fused_kernel, 4 waves per SIMD       launch_direct_fused: fused_w4 (default) otherwise
+//   k_direct_fused_cw<VD,CS>    own: direct_begin / _candidate / _finish     launch_direct_fused: compact_emitter or compact_shadow,
+//                               around compact_walks                         unstaged, not an emissive-validation frame
+//   k_indirect<MULTI,LDS,CS>    indirect_body (light.wgsl:1263); CS:         launch_indirect: default; CS: compact_shadow
+//                               indirect_begin / compact_walks / indirect_end
+//   k_indirect_persist<MULTI,LDS> persist_tiles over indirect_body           launch_indirect: persistent_indirect
+//   k_light_merged<VD,VE,LDS_I> fused_direct_pixel | indirect_body by role   launch_light_merged: the runtime's merged frames
+//   k_wf_gen / _trace / _shade  indirect_body<false, IND_GEN / _TRACE /      launch_indirect_wavefront: wavefront frames
+//   (k_wf_scan, k_wf_scatter)   _SHADE> (own: the bin sort between them)
+//   k_spatial, k_spatial_nowin  spatial_kernel (light.wgsl:1503)             launch_spatial: with / without a pass window
+//   k_demod3<C>, k_denoise3<C,LEVEL>, k_tone, k_tone_run   own (denoise.wgsl:135, :215, tone_mapping.wgsl:21)
+//   k_trace                     own (light.wgsl:442 traverse_top)            launch_trace (tests)
 //
 // Launch shape: 256-thread workgroups covering a 16x16 pixel tile, each wave an 8x8
 // sub-tile (the reference's workgroup footprint), so rays of one wave stay coherent.
@@ -491,6 +502,21 @@ HKD bool direct_begin(const FrameArgs& A, const Scene& sc, const ChannelArgs& C,
                                n_emitter, D.L);
     return true;
 }
+// whether a pass's light candidate gets a shadow ray from a surface with normal n (light.wgsl:1101,1132), and the
+// radiance that ray brings in (light.wgsl:1104,1135): the candidate and the validation block ask both
+template <bool EMISSIVE_LIT>
+HKD bool direct_traces(const LightCandidate& cand, f3 n)
+{
+    bool trace = dot(cand.direction, n) > 0.0f && cand.p > 0.0f;
+    if (EMISSIVE_LIT) trace = trace && cand.emissive_instance != DONT_SAMPLE_EMISSIVE;
+    return trace;
+}
+template <bool EMISSIVE_LIT>
+HKD f4 direct_input_radiance(const Scene& sc, const Frame& F, const Ray& ray, const HitInfo& info, const LightCandidate& cand)
+{
+    return EMISSIVE_LIT ? input_radiance(sc, F, ray, info, false, cand.emissive_instance, false)
+                        : input_radiance(sc, F, ray, info, true, DONT_SAMPLE_EMISSIVE, false);
+}
 // the candidate block after its emitter walk (hit, traced: light_pick_walk's result), up to its shadow walk:
 // returns whether the shadow ray (D.ray, cand's distances) is traced
 template <bool EMISSIVE_LIT>
@@ -505,8 +531,7 @@ HKD bool direct_candidate_a(const Scene& sc, const DirectPixel& P, DirectState& 
     ray.origin = xyz(D.position) + normal * RAY_BIAS;
     ray.direction = cand.direction;
     ray.inv_direction = inv(ray.direction);
-    bool trace = dot(cand.direction, normal) > 0.0f && cand.p > 0.0f;
-    if (EMISSIVE_LIT) trace = trace && cand.emissive_instance != DONT_SAMPLE_EMISSIVE;
+    const bool trace = direct_traces<EMISSIVE_LIT>(cand, normal);
     if (trace) n_top++;
     return trace;
 }
@@ -520,8 +545,7 @@ HKD void direct_candidate_b(const FrameArgs& A, const Scene& sc, DirectState& D,
     const Ray& ray = D.ray;
     if (trace) {
         occlude_hit_info(ray, hit, D.info);
-        s.radiance = EMISSIVE_LIT ? input_radiance(sc, F, ray, D.info, false, cand.emissive_instance, false)
-                                  : input_radiance(sc, F, ray, D.info, true, DONT_SAMPLE_EMISSIVE, false);
+        s.radiance = direct_input_radiance<EMISSIVE_LIT>(sc, F, ray, D.info, cand);
     }
     s.sample_position = D.info.position;
     s.sample_normal = D.info.normal;
@@ -576,21 +600,16 @@ HKD void direct_finish(const FrameArgs& A, const Scene& sc, const ChannelArgs& C
         }
         // (r.s.visible_normal for the trace test below comes back with the reservoir)
         f4 validate_radiance = mk4(0, 0, 0, 0);
-        bool trace;
-        if constexpr (PARK) {
-            const f3 vn = mk3(lds[12 * 256 + threadIdx.x], lds[13 * 256 + threadIdx.x], lds[14 * 256 + threadIdx.x]);
-            trace = dot(cand.direction, vn) > 0.0f && cand.p > 0.0f;
-        } else {
-            trace = dot(cand.direction, r.s.visible_normal) > 0.0f && cand.p > 0.0f;
-        }
-        if (EMISSIVE_LIT) trace = trace && cand.emissive_instance != DONT_SAMPLE_EMISSIVE;
+        f3 vn;
+        if constexpr (PARK) vn = mk3(lds[12 * 256 + threadIdx.x], lds[13 * 256 + threadIdx.x], lds[14 * 256 + threadIdx.x]);
+        else vn = r.s.visible_normal;
+        const bool trace = direct_traces<EMISSIVE_LIT>(cand, vn);
         if constexpr (PARK) __asm__ volatile("" ::: "memory");
         if (trace) {
             n_top++;
             Hit hit = traverse_top(sc, ray, cand.max_distance, cand.min_distance, cand.emissive_instance);
             occlude_hit_info(ray, hit, info);
-            validate_radiance = EMISSIVE_LIT ? input_radiance(sc, F, ray, info, false, cand.emissive_instance, false)
-                                             : input_radiance(sc, F, ray, info, true, DONT_SAMPLE_EMISSIVE, false);
+            validate_radiance = direct_input_radiance<EMISSIVE_LIT>(sc, F, ray, info, cand);
         }
         if constexpr (PARK) {
             __asm__ volatile("" ::: "memory");
@@ -682,6 +701,20 @@ HKD Reservoir background_reservoir()
     set_reservoir(r, zero_sample(), 0.0f);
     return r;
 }
+// BG_SKIP_OWN: of a background pixel's stores only the emissive pass's into the spatial pair (direct_begin) are due
+HKD void store_background_pair(const ChannelArgs& C, int32_t idx)
+{
+    const Reservoir z = background_reservoir();
+    store_res(C.spatial, idx, z);
+    store_res(C.prev_spatial, idx, z);
+}
+// the light kernels' epilogue: the thread's walk counts, none for a pixel outside the counted region
+HKD void finish_counts(const FrameArgs& A, int32_t x, int32_t y, uint32_t n_top, uint32_t n_emitter)
+{
+    if (!counted(A.F, x, y)) n_top = n_emitter = 0;
+    wave_count(A.cnt.top, n_top);
+    wave_count(A.cnt.emitter, n_emitter);
+}
 
 // The separate direct_lit / emissive launches share the pair's mask (ChannelArgs::bg of both):
 // direct_lit, first on the stream, only reads it (its targets are among the bits); the emissive
@@ -699,17 +732,17 @@ HKD void direct_pass(const FrameArgs& A, const Scene& sc, const ChannelArgs& C, 
         const uint32_t bg = bg_elide(C, P.idx, background);
         if (bg == BG_SKIP_ALL) return;
         if (bg == BG_SKIP_OWN) {
-            const Reservoir z = background_reservoir();
-            store_res(C.spatial, P.idx, z);
-            store_res(C.prev_spatial, P.idx, z);
+            store_background_pair(C, P.idx);
             return;
         }
     }
     direct_body<EMISSIVE_LIT, RENDER_EMISSIVE, VALIDATE>(A, sc, C, P, n_top, n_emitter);
 }
 
+// One direct-light pass per launch: the body of k_direct and k_direct_lit_w4.  (The argument blocks by value, as a
+// kernel has them: by reference the unstaged variants compile to other code.)
 template <bool EMISSIVE_LIT, bool RENDER_EMISSIVE, bool LDS, bool VALIDATE>
-__global__ __launch_bounds__(256) void k_direct(FrameArgs A, ChannelArgs C)
+HKD void direct_kernel(FrameArgs A, ChannelArgs C)
 {
     int32_t x, y;
     const bool active = tile_pixel<TRACE_ORDER>(A.F, A.F.s[0], A.F.s_row0, A.F.s_rows, x, y);
@@ -720,11 +753,13 @@ __global__ __launch_bounds__(256) void k_direct(FrameArgs A, ChannelArgs C)
     else sc = A.sc;
     uint32_t n_top = 0, n_emitter = 0;
     if (active) direct_pass<EMISSIVE_LIT, RENDER_EMISSIVE, VALIDATE>(A, sc, C, x, y, n_top, n_emitter, &tex);
-    if (!counted(A.F, x, y)) n_top = n_emitter = 0;
-    wave_count(A.cnt.top, n_top);
-    wave_count(A.cnt.emitter, n_emitter);
+    finish_counts(A, x, y, n_top, n_emitter);
 }
-
+template <bool EMISSIVE_LIT, bool RENDER_EMISSIVE, bool LDS, bool VALIDATE>
+__global__ __launch_bounds__(256) void k_direct(FrameArgs A, ChannelArgs C)
+{
+    direct_kernel<EMISSIVE_LIT, RENDER_EMISSIVE, LDS, VALIDATE>(A, C);
+}
 // direct_lit alone (no emissive sampling) fits 128 VGPRs with at most a few scratch words: the
 // same body with 4 waves per SIMD for the separate-launch path (bands / stripes) when the grid
 // has enough waves to use them (>= 400 K pixels): cornell 2-way stripe 0.348 -> 0.328 ms/frame,
@@ -733,27 +768,32 @@ __global__ __launch_bounds__(256) void k_direct(FrameArgs A, ChannelArgs C)
 template <bool LDS, bool VALIDATE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_direct_lit_w4(FrameArgs A, ChannelArgs C)
 {
-    int32_t x, y;
-    const bool active = tile_pixel<TRACE_ORDER>(A.F, A.F.s[0], A.F.s_row0, A.F.s_rows, x, y);
-    PixelTexels tex;
-    if (active) tex = load_pixel_texels(A, x, y);
-    Scene sc;
-    if constexpr (LDS) sc = stage_scene<PLAN_LIGHT>(A.sc, hk_lds_scene);
-    else sc = A.sc;
-    uint32_t n_top = 0, n_emitter = 0;
-    if (active) direct_pass<false, true, VALIDATE>(A, sc, C, x, y, n_top, n_emitter, &tex);
-    if (!counted(A.F, x, y)) n_top = n_emitter = 0;
-    wave_count(A.cnt.top, n_top);
-    wave_count(A.cnt.emitter, n_emitter);
+    direct_kernel<false, true, LDS, VALIDATE>(A, C);
 }
 
+// direct_lit then the emissive pass of one pixel (the fused kernels, k_light_merged's direct role): the pair's
+// background elision, then both passes with the pixel's surface (same material and uv in both) fetched once
+template <bool VD, bool VE, int PARK>
+HKD void fused_direct_pixel(const FrameArgs& A, const Scene& sc, const ChannelArgs& C0, const ChannelArgs& C1,
+                            const DirectPixel& P, uint32_t& n_top, uint32_t& n_emitter)
+{
+    const uint32_t bg = bg_elide(C0, P.idx, P.pd.w < HK_F32_EPSILON);
+    if (bg == BG_SKIP_OWN) {
+        store_background_pair(C1, P.idx);
+    } else if (bg == BG_STORE) {
+        Surface surface;
+        direct_body<false, true, VD, PARK>(A, sc, C0, P, n_top, n_emitter, &surface);
+        direct_body<true, false, VE, PARK>(A, sc, C1, P, n_top, n_emitter, nullptr, &surface);
+    }
+}
 // direct_lit then the emissive pass in one launch, each thread running both passes for its pixel
 // in the reference's pass order.  Both passes store into the spatial reservoir pair they share
 // only at their own pixel when the reprojection is the identity (zero velocity at upscale ratio
 // 1: the G-buffer of k_gbuffer), so per-thread program order is the reference's pass order for
 // every stored word; the runtime uses it only then.  One launch and one tail instead of two.
+// The body of k_direct_fused and k_direct_fused_w4 (argument blocks by value: direct_kernel).
 template <bool LDS, bool VD, bool VE>
-__global__ __launch_bounds__(256) void k_direct_fused(FrameArgs A, ChannelArgs C0, ChannelArgs C1)
+HKD void direct_fused_kernel(FrameArgs A, ChannelArgs C0, ChannelArgs C1)
 {
     int32_t x, y;
     const bool active = tile_pixel<TRACE_ORDER>(A.F, A.F.s[0], A.F.s_row0, A.F.s_rows, x, y);
@@ -763,25 +803,14 @@ __global__ __launch_bounds__(256) void k_direct_fused(FrameArgs A, ChannelArgs C
     if constexpr (LDS) sc = stage_scene<PLAN_LIGHT>(A.sc, hk_lds_scene);
     else sc = A.sc;
     uint32_t n_top = 0, n_emitter = 0;
-    if (active) {
-        const DirectPixel P = direct_pixel_of(A, x, y, tex);
-        const uint32_t bg = bg_elide(C0, P.idx, P.pd.w < HK_F32_EPSILON);
-        if (bg == BG_SKIP_OWN) {  // the emissive pass's stores into the spatial pair (direct_body)
-            const Reservoir z = background_reservoir();
-            store_res(C1.spatial, P.idx, z);
-            store_res(C1.prev_spatial, P.idx, z);
-        } else if (bg == BG_STORE) {
-            // the pixel's surface (same material and uv in both passes) is fetched once
-            Surface surface;
-            direct_body<false, true, VD, !LDS>(A, sc, C0, P, n_top, n_emitter, &surface);
-            direct_body<true, false, VE, !LDS>(A, sc, C1, P, n_top, n_emitter, nullptr, &surface);
-        }
-    }
-    if (!counted(A.F, x, y)) n_top = n_emitter = 0;
-    wave_count(A.cnt.top, n_top);
-    wave_count(A.cnt.emitter, n_emitter);
+    if (active) fused_direct_pixel<VD, VE, !LDS>(A, sc, C0, C1, direct_pixel_of(A, x, y, tex), n_top, n_emitter);
+    finish_counts(A, x, y, n_top, n_emitter);
 }
-
+template <bool LDS, bool VD, bool VE>
+__global__ __launch_bounds__(256) void k_direct_fused(FrameArgs A, ChannelArgs C0, ChannelArgs C1)
+{
+    direct_fused_kernel<LDS, VD, VE>(A, C0, C1);
+}
 // The fused launch on frames that are not emissive-validation frames, held to 4 waves per SIMD
 // (128 VGPRs): without the emissive validation block the body needs 117-137 VGPRs (the direct
 // validation block on every third frame), a few of which then spill.
@@ -791,31 +820,7 @@ template <bool LDS, bool VD, bool VE = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_direct_fused_w4(FrameArgs A, ChannelArgs C0,
                                                                                                    ChannelArgs C1)
 {
-    int32_t x, y;
-    const bool active = tile_pixel<TRACE_ORDER>(A.F, A.F.s[0], A.F.s_row0, A.F.s_rows, x, y);
-    PixelTexels tex;
-    if (active) tex = load_pixel_texels(A, x, y);  // in flight during the staging
-    Scene sc;
-    if constexpr (LDS) sc = stage_scene<PLAN_LIGHT>(A.sc, hk_lds_scene);
-    else sc = A.sc;
-    uint32_t n_top = 0, n_emitter = 0;
-    if (active) {
-        const DirectPixel P = direct_pixel_of(A, x, y, tex);
-        const uint32_t bg = bg_elide(C0, P.idx, P.pd.w < HK_F32_EPSILON);
-        if (bg == BG_SKIP_OWN) {  // the emissive pass's stores into the spatial pair (direct_body)
-            const Reservoir z = background_reservoir();
-            store_res(C1.spatial, P.idx, z);
-            store_res(C1.prev_spatial, P.idx, z);
-        } else if (bg == BG_STORE) {
-            // the pixel's surface (same material and uv in both passes) is fetched once
-            Surface surface;
-            direct_body<false, true, VD, !LDS>(A, sc, C0, P, n_top, n_emitter, &surface);
-            direct_body<true, false, VE, !LDS>(A, sc, C1, P, n_top, n_emitter, nullptr, &surface);
-        }
-    }
-    if (!counted(A.F, x, y)) n_top = n_emitter = 0;
-    wave_count(A.cnt.top, n_top);
-    wave_count(A.cnt.emitter, n_emitter);
+    direct_fused_kernel<LDS, VD, VE>(A, C0, C1);
 }
 
 // Emitter walks of a workgroup as one compacted batch (the CW variant of the fused launch).  In city the
@@ -839,80 +844,112 @@ HKD float* cw_area()
     __shared__ float cw[CW_WORDS * 256];
     return cw;
 }
-// every thread of the workgroup calls this at the same point (barriers); need = the thread's pixel walks
-HKD bool compact_emitter_walks(const Scene& sc, float* lds, const LightPick& L, bool need, Hit& hit)
-{
-    uint32_t* const queue = reinterpret_cast<uint32_t*>(lds + 9 * 256);
-    __shared__ uint32_t wave_counts[8];
-    const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
-    uint32_t node_offset = 0u, node_count = 0u;
-    if (need) {
-        const hk_instance& ein = get_instance(sc, L.cand.emissive_instance);
-        node_offset = ein.mesh.node[0];
-        node_count = ein.mesh.node[1];
-        lds[0 * 256 + t] = L.local.origin.x;
-        lds[1 * 256 + t] = L.local.origin.y;
-        lds[2 * 256 + t] = L.local.origin.z;
-        lds[3 * 256 + t] = L.local.direction.x;
-        lds[4 * 256 + t] = L.local.direction.y;
-        lds[5 * 256 + t] = L.local.direction.z;
-        lds[6 * 256 + t] = __uint_as_float(node_offset);
-        lds[7 * 256 + t] = __uint_as_float(node_count);
-        lds[8 * 256 + t] = __uint_as_float(ein.mesh.primitive);
+// one thread's column of the batch's rows
+struct WalkRows {
+    float* lds;
+    uint32_t col;
+    HKD float& operator[](int k) const { return lds[k * 256 + col]; }
+    HKD uint32_t bits(int k) const { return __float_as_uint(lds[k * 256 + col]); }
+    HKD void put_ray(const Ray& r) const  // rows 0-5: origin, direction
+    {
+        const float v[6] = {r.origin.x, r.origin.y, r.origin.z, r.direction.x, r.direction.y, r.direction.z};
+#pragma unroll
+        for (int k = 0; k < 6; ++k) (*this)[k] = v[k];
     }
-    const bool lng = need && node_count > CW_LONG_NODES;
-    const uint64_t m_long = __ballot(lng), m_short = __ballot(need && !lng);
-    if (lane == 0u) {
-        wave_counts[2u * w] = (uint32_t)__popcll(m_long);
-        wave_counts[2u * w + 1u] = (uint32_t)__popcll(m_short);
+    HKD Ray ray() const
+    {
+        Ray r;
+        r.origin = mk3((*this)[0], (*this)[1], (*this)[2]);
+        r.direction = mk3((*this)[3], (*this)[4], (*this)[5]);
+        r.inv_direction = inv(r.direction);
+        return r;
+    }
+};
+HKD Hit missed_hit()
+{
+    Hit h;
+    h.uv = mk2(0, 0);
+    h.distance = HK_F32_MAX;
+    h.instance_index = HK_U32_MAX;
+    h.primitive_index = HK_U32_MAX;
+    return h;
+}
+// A compacted batch of walks W.  Every thread of the workgroup calls this at the same point and reaches its three
+// barriers: nothing here returns early.  A thread that needs a walk writes its request into its column
+// (walk.request, which returns the request's class); the requests are queued class 0 first, in pixel order inside a
+// class, from per-wave ballots and counts; thread t runs queue entry t (W::run: the request's column in, the result
+// over it, read only by the requesting thread); then each thread reads its own result (W::result).
+template <class W>
+HKD bool compact_walks(const Scene& sc, float* lds, bool need, const W& walk, Hit& hit)
+{
+    constexpr uint32_t NC = W::CLASSES;
+    uint32_t* const queue = reinterpret_cast<uint32_t*>(lds + 9 * 256);
+    __shared__ uint32_t wave_counts[4 * NC];
+    const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
+    uint32_t cls = 0u;
+    if (need) cls = walk.request(sc, WalkRows{lds, t});
+    uint64_t mine = 0ull;  // this wave's requests of the thread's class
+#pragma unroll
+    for (uint32_t c = 0; c < NC; ++c) {
+        const uint64_t m = __ballot(need && cls == c);
+        if (lane == 0u) wave_counts[NC * w + c] = (uint32_t)__popcll(m);
+        if (cls == c) mine = m;
     }
     __syncthreads();
-    uint32_t n_long = 0u, n_short = 0u, below_long = 0u, below_short = 0u;
+    // the batch's size, and the requests queued before this thread's: the earlier classes, then its own class in
+    // the waves below its own, then in the lanes below its own
+    uint32_t n = 0u, pos = (uint32_t)__popcll(mine & ((1ull << lane) - 1ull));
 #pragma unroll
     for (uint32_t k = 0; k < 4u; ++k) {
-        const uint32_t a = wave_counts[2u * k], b = wave_counts[2u * k + 1u];
-        below_long += k < w ? a : 0u;
-        below_short += k < w ? b : 0u;
-        n_long += a;
-        n_short += b;
+#pragma unroll
+        for (uint32_t c = 0; c < NC; ++c) {
+            const uint32_t a = wave_counts[NC * k + c];
+            pos += (c < cls || (c == cls && k < w)) ? a : 0u;
+            n += a;
+        }
     }
-    if (need) {
-        const uint64_t below = (1ull << lane) - 1ull;
-        const uint32_t pos = lng ? below_long + (uint32_t)__popcll(m_long & below)
-                                 : n_long + below_short + (uint32_t)__popcll(m_short & below);
-        queue[pos] = t;
-    }
+    if (need) queue[pos] = t;
     __syncthreads();
-    if (t < n_long + n_short) {
-        const uint32_t o = queue[t];
-        Ray r;
-        r.origin = mk3(lds[0 * 256 + o], lds[1 * 256 + o], lds[2 * 256 + o]);
-        r.direction = mk3(lds[3 * 256 + o], lds[4 * 256 + o], lds[5 * 256 + o]);
-        r.inv_direction = inv(r.direction);
-        Hit h;
-        h.uv = mk2(0, 0);
-        h.distance = HK_F32_MAX;
-        h.instance_index = HK_U32_MAX;
-        h.primitive_index = HK_U32_MAX;
-        const bool traced = traverse_bottom(sc, h, r, __float_as_uint(lds[6 * 256 + o]), __float_as_uint(lds[7 * 256 + o]),
-                                            __float_as_uint(lds[8 * 256 + o]), 0.0f);
-        // the result over the request's own slots (read only by this thread)
-        lds[0 * 256 + o] = h.uv.x;
-        lds[1 * 256 + o] = h.uv.y;
-        lds[2 * 256 + o] = h.distance;
-        lds[3 * 256 + o] = __uint_as_float(h.primitive_index);
-        lds[4 * 256 + o] = traced ? 1.0f : 0.0f;
-    }
+    if (t < n) W::run(sc, WalkRows{lds, queue[t]});
     __syncthreads();
-    hit.uv = mk2(0, 0);
-    hit.distance = HK_F32_MAX;
-    hit.instance_index = HK_U32_MAX;
-    hit.primitive_index = HK_U32_MAX;
-    if (!need) return false;
-    hit.uv = mk2(lds[0 * 256 + t], lds[1 * 256 + t]);
-    hit.distance = lds[2 * 256 + t];
-    hit.primitive_index = __float_as_uint(lds[3 * 256 + t]);
-    return lds[4 * 256 + t] != 0.0f;
+    return need && W::result(WalkRows{lds, t}, hit);
+}
+// the emissive pass's emitter BLAS walks (light_pick_walk): two classes, long walks first
+struct EmitterWalks {
+    static constexpr uint32_t CLASSES = 2u;
+    const LightPick& L;
+    HKD uint32_t request(const Scene& sc, const WalkRows q) const
+    {
+        const hk_instance& ein = get_instance(sc, L.cand.emissive_instance);
+        q.put_ray(L.local);
+        q[6] = __uint_as_float(ein.mesh.node[0]);
+        q[7] = __uint_as_float(ein.mesh.node[1]);
+        q[8] = __uint_as_float(ein.mesh.primitive);
+        return ein.mesh.node[1] > CW_LONG_NODES ? 0u : 1u;
+    }
+    HKD static void run(const Scene& sc, const WalkRows q)
+    {
+        Hit h = missed_hit();
+        const bool traced = traverse_bottom(sc, h, q.ray(), q.bits(6), q.bits(7), q.bits(8), 0.0f);
+        q[0] = h.uv.x;
+        q[1] = h.uv.y;
+        q[2] = h.distance;
+        q[3] = __uint_as_float(h.primitive_index);
+        q[4] = traced ? 1.0f : 0.0f;
+    }
+    HKD static bool result(const WalkRows q, Hit& hit)
+    {
+        hit.uv = mk2(q[0], q[1]);
+        hit.distance = q[2];
+        hit.primitive_index = q.bits(3);
+        return q[4] != 0.0f;
+    }
+};
+// need = the thread's pixel walks; returns light_pick_walk's result (a miss, not traced, without a walk)
+HKD bool compact_emitter_walks(const Scene& sc, float* lds, const LightPick& L, bool need, Hit& hit)
+{
+    hit = missed_hit();
+    return compact_walks(sc, lds, need, EmitterWalks{L}, hit);
 }
 
 // Shadow walks (traverse_top any-hit) of a workgroup as one compacted batch: the lanes that trace a shadow
@@ -923,55 +960,41 @@ HKD bool compact_emitter_walks(const Scene& sc, float* lds, const LightPick& L, 
 // busy, indirect emissive shadows 0.25 -> 0.41; tools/walk_lanes.py).  The walk's result depends only on
 // the request, so it is the per-pixel walk's.
 // (LDS: the rows of compact_emitter_walks, cw_area / park columns)
+struct TopWalks {
+    static constexpr uint32_t CLASSES = 1u;
+    const Ray& shadow;
+    float max_distance, early_distance;
+    uint32_t exclude;
+    HKD uint32_t request(const Scene&, const WalkRows q) const
+    {
+        q.put_ray(shadow);
+        q[6] = max_distance;
+        q[7] = early_distance;
+        q[8] = __uint_as_float(exclude);
+        return 0u;
+    }
+    HKD static void run(const Scene& sc, const WalkRows q)
+    {
+        const Hit h = traverse_top(sc, q.ray(), q[6], q[7], q.bits(8));
+        q[0] = h.uv.x;
+        q[1] = h.uv.y;
+        q[2] = h.distance;
+        q[3] = __uint_as_float(h.instance_index);
+        q[4] = __uint_as_float(h.primitive_index);
+    }
+    HKD static bool result(const WalkRows q, Hit& hit)
+    {
+        hit.uv = mk2(q[0], q[1]);
+        hit.distance = q[2];
+        hit.instance_index = q.bits(3);
+        hit.primitive_index = q.bits(4);
+        return true;
+    }
+};
 HKD bool compact_top_walks(const Scene& sc, float* lds, bool need, const Ray& ray, float max_distance, float early_distance,
                            uint32_t exclude, Hit& hit)
 {
-    uint32_t* const ct_queue = reinterpret_cast<uint32_t*>(lds + 9 * 256);
-    __shared__ uint32_t ct_counts[4];
-    const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
-    if (need) {
-        lds[0 * 256 + t] = ray.origin.x;
-        lds[1 * 256 + t] = ray.origin.y;
-        lds[2 * 256 + t] = ray.origin.z;
-        lds[3 * 256 + t] = ray.direction.x;
-        lds[4 * 256 + t] = ray.direction.y;
-        lds[5 * 256 + t] = ray.direction.z;
-        lds[6 * 256 + t] = max_distance;
-        lds[7 * 256 + t] = early_distance;
-        lds[8 * 256 + t] = __uint_as_float(exclude);
-    }
-    const uint64_t m = __ballot(need);
-    if (lane == 0u) ct_counts[w] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t n = 0u, below = 0u;
-#pragma unroll
-    for (uint32_t k = 0; k < 4u; ++k) {
-        const uint32_t a = ct_counts[k];
-        below += k < w ? a : 0u;
-        n += a;
-    }
-    if (need) ct_queue[below + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = t;
-    __syncthreads();
-    if (t < n) {
-        const uint32_t o = ct_queue[t];
-        Ray r;
-        r.origin = mk3(lds[0 * 256 + o], lds[1 * 256 + o], lds[2 * 256 + o]);
-        r.direction = mk3(lds[3 * 256 + o], lds[4 * 256 + o], lds[5 * 256 + o]);
-        r.inv_direction = inv(r.direction);
-        const Hit h = traverse_top(sc, r, lds[6 * 256 + o], lds[7 * 256 + o], __float_as_uint(lds[8 * 256 + o]));
-        lds[0 * 256 + o] = h.uv.x;
-        lds[1 * 256 + o] = h.uv.y;
-        lds[2 * 256 + o] = h.distance;
-        lds[3 * 256 + o] = __uint_as_float(h.instance_index);
-        lds[4 * 256 + o] = __uint_as_float(h.primitive_index);
-    }
-    __syncthreads();
-    if (!need) return false;
-    hit.uv = mk2(lds[0 * 256 + t], lds[1 * 256 + t]);
-    hit.distance = lds[2 * 256 + t];
-    hit.instance_index = __float_as_uint(lds[3 * 256 + t]);
-    hit.primitive_index = __float_as_uint(lds[4 * 256 + t]);
-    return true;
+    return compact_walks(sc, lds, need, TopWalks{ray, max_distance, early_distance, exclude}, hit);
 }
 
 // k_direct_fused_w4 on the frames that validate neither pass's emitter picks (VE false) with the emissive
@@ -993,11 +1016,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     if (on) {
         P = direct_pixel_of(A, x, y, load_pixel_texels(A, x, y));
         bg = bg_elide(C0, P.idx, P.pd.w < HK_F32_EPSILON);
-        if (bg == BG_SKIP_OWN) {  // the emissive pass's stores into the spatial pair (direct_body)
-            const Reservoir z = background_reservoir();
-            store_res(C1.spatial, P.idx, z);
-            store_res(C1.prev_spatial, P.idx, z);
-        }
+        if (bg == BG_SKIP_OWN) store_background_pair(C1, P.idx);
     }
     const bool work = on && bg == BG_STORE;
     Surface surface;
@@ -1038,9 +1057,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
         direct_candidate<true>(A, sc, P, D, hit, traced, n_top);
         direct_finish<true, false, false, 0>(A, sc, C1, P, D, n_top, n_emitter, nullptr, &surface);
     }
-    if (!counted(A.F, x, y)) n_top = n_emitter = 0;
-    wave_count(A.cnt.top, n_top);
-    wave_count(A.cnt.emitter, n_emitter);
+    finish_counts(A, x, y, n_top, n_emitter);
 }
 
 // ------------------------------------------------------------------ indirect_lit_ambient (light.wgsl:1263-1498)
@@ -1129,9 +1146,6 @@ HKD void bounce_hit_b(const Scene& sc, const Frame& F, BounceState& B, bool shad
     }
 }
 
-// The pass up to the one-bounce path's shadow walk (I.shadow: whether it is traced; the multiple-bounce
-// path runs its whole loop here).  Returns false when the pixel's pass ends here: a background pixel (its
-// stores done), the IND_GEN / IND_TRACE stages (*ret: their result).
 // The pixel's G-buffer and blue-noise fields, kept in LDS through the walks by the tile kernels (k_indirect,
 // k_light_merged): indirect_end reads them back from there instead of from global memory (one thread's slot,
 // struct-of-arrays so that a wave's 16-byte accesses are conflict-free)
@@ -1151,6 +1165,109 @@ struct IndirectState {
     float pdf;
     bool shadow;
 };
+// The pixel's inputs of the pass, from the kernel's preloaded texels (tex) or by its own loads, in two steps as the
+// pass reads them (direct_pixel_of / load_direct_pixel for the direct passes): the position texel first, which
+// decides whether the pixel is background, and the rest only for a pixel that goes on.
+struct IndirectPixel {
+    int32_t dx, dy;  // the jittered G-buffer coordinates
+    f4 pd;           // position, depth
+    f3 normal;       // normalised
+    uint32_t im_x, im_y;  // instance, material
+    f4 velocity_uv, random;
+};
+HKD IndirectPixel indirect_pixel_head(const FrameArgs& A, f2 uv, const PixelTexels* tex)
+{
+    IndirectPixel P;
+    jittered_coords(A.F, uv, P.dx, P.dy);
+    P.pd = tex ? mk4(tex->pd.x, tex->pd.y, tex->pd.z, tex->pd.w) : load_position(A.F, A.G, P.dx, P.dy);
+    return P;
+}
+HKD void indirect_pixel_rest(const FrameArgs& A, int32_t x, int32_t y, const PixelTexels* tex, IndirectPixel& P)
+{
+    const Frame& F = A.F;
+    if (tex) {
+        P.normal = normalize(texel_normal(tex->normal));
+        P.im_x = f2u32(tex->imf.x);
+        P.im_y = f2u32(tex->imf.y);
+        P.velocity_uv = mk4(tex->vel.x, tex->vel.y, tex->vel.z, tex->vel.w);
+        P.random = noise_of(tex->noise, F.number);
+    } else {
+        P.normal = normalize(load_normal(F, A.G, P.dx, P.dy));
+        const f2 imf = load_instance_material(F, A.G, P.dx, P.dy);
+        P.im_x = f2u32(imf.x);
+        P.im_y = f2u32(imf.y);
+        P.velocity_uv = load_velocity_uv(F, A.G, P.dx, P.dy);
+        P.random = noise_random(A.noise, F.number, x, y);
+    }
+}
+// The multiple-bounce path (light.wgsl:1300-1394 with MULTIPLE_BOUNCES) from the pixel's sample s: the whole loop,
+// both walks of every bounce included.  B.s is the path's current vertex; the first bounce's hit becomes s's sample
+// point and its pdf is returned.  The shading tail is the loop's own: from the second bounce on it divides by the
+// bounce's pdf, and it clamps the luminance and weighs by the path's throughput, none of which bounce_hit_b does.
+HKD float indirect_multi_bounces(const Scene& sc, const Frame& F, Sample& s, uint32_t& n_top, uint32_t& n_emitter)
+{
+    BounceState B;
+    Sample& bs = B.s;
+    bs = s;
+    float pdf = 0.0f;
+    f3 ct = mk3(1.0f, 1.0f, 1.0f);
+    for (uint32_t n = 0u; n < F.indirect_bounces && (ct.x > 0.01f || ct.y > 0.01f || ct.z > 0.01f); n += 1u) {
+        const f4 rs = bounce_ray(B);
+        Ray& ray = B.ray;
+        HitInfo& info = B.info;
+        n_top++;
+        Hit hit = traverse_top(sc, ray, HK_F32_MAX, 0.0f, DONT_EXCLUDE);
+        info = hit_info(sc, ray, hit);
+        if (n == 0u) {
+            s.sample_position = info.position;
+            s.sample_normal = info.normal;
+            pdf = rs.w;
+        }
+        bs.sample_position = info.position;
+        bs.sample_normal = info.normal;
+        if (hit.instance_index != HK_U32_MAX) {
+            f3 out = mk3(0, 0, 0);
+            Surface surface = retreive_surface(sc, info.material_index, info.uv);
+            surface.roughness = 1.0f;
+            LightCandidate cand = select_light_candidate<true>(sc, F, bs.random, xyz(bs.sample_position),
+                                                               bs.sample_normal, info.instance_index, info, n_emitter);
+            bool sample_directional = cand.emissive_instance == DONT_SAMPLE_EMISSIVE;
+            f3 bvd = normalize(xyz(bs.visible_position) - xyz(bs.sample_position));
+            if (dot(cand.direction, bs.sample_normal) > 0.0f && cand.p > 0.0f) {
+                ray.origin = xyz(bs.sample_position) + bs.sample_normal * RAY_BIAS;
+                ray.direction = cand.direction;
+                ray.inv_direction = inv(ray.direction);
+                n_top++;
+                Hit sh = traverse_top(sc, ray, cand.max_distance, cand.min_distance, cand.emissive_instance);
+                occlude_hit_info(ray, sh, info);
+                f4 in_rad = input_radiance(sc, F, ray, info, sample_directional, cand.emissive_instance, false);
+                out = shading(F, bvd, bs.sample_normal, ray.direction, surface, in_rad);
+                out = out / cand.p;
+                if (n > 0u) out = rs.w < 0.01f ? mk3(0, 0, 0) : out / rs.w;
+                float ol = lum(out);
+                if (ol > F.max_indirect_luminance) out = (out * F.max_indirect_luminance) / ol;
+                f3 add = ct * out;
+                s.radiance = mk4(s.radiance.x + add.x, s.radiance.y + add.y, s.radiance.z + add.z, s.radiance.w + 1.0f);
+            }
+            ct = ct * env_brdf(bvd, bs.sample_normal, surface);
+            float fn = (float)F.number * HK_GOLDEN_RATIO;
+            bs.random = mk4(hk_fract(bs.random.x + fn), hk_fract(bs.random.y + fn), hk_fract(bs.random.z + fn),
+                            hk_fract(bs.random.w + fn));
+            bs.visible_position = bs.sample_position;
+            bs.visible_normal = bs.sample_normal;
+        } else {
+            f3 out = xyz(input_radiance(sc, F, ray, info, false, DONT_SAMPLE_EMISSIVE, true));
+            f3 add = ct * out;
+            s.radiance = mk4(s.radiance.x + add.x, s.radiance.y + add.y, s.radiance.z + add.z, s.radiance.w + 0.0f);
+            break;
+        }
+    }
+    return pdf;
+}
+// The pass up to the one-bounce path's shadow walk (I.shadow: whether it is traced; the multiple-bounce
+// path runs its whole loop here).  Returns false when the pixel's pass ends here: a background pixel (its
+// stores done), the IND_GEN / IND_TRACE stages (*ret: their result).  In order: the background stores and the
+// stage exits, the pixel, the stash, the bounces, the state for indirect_end.
 template <bool MULTI, int STAGE = IND_ALL>
 HKD bool indirect_begin(const FrameArgs& A, const Scene& sc, const ChannelArgs& C, int32_t x, int32_t y, uint32_t& n_top,
                         uint32_t& n_emitter, const WfArgs* W, uint32_t* key, IndirectState& I, bool& ret,
@@ -1162,9 +1279,8 @@ HKD bool indirect_begin(const FrameArgs& A, const Scene& sc, const ChannelArgs& 
     const Frame& F = A.F;
     const int32_t idx = s_index(F, x, y);
     const f2 uv = coords_to_uv(x, y, F.s);
-    int32_t dx, dy;
-    jittered_coords(F, uv, dx, dy);
-    f4 pd = tex ? mk4(tex->pd.x, tex->pd.y, tex->pd.z, tex->pd.w) : load_position(F, A.G, dx, dy);
+    IndirectPixel P = indirect_pixel_head(A, uv, tex);
+    const f4 pd = P.pd;
     f4 position = mk4(pd.x, pd.y, pd.z, 1.0f);
     float depth = pd.w;
     Sample s = zero_sample();
@@ -1190,12 +1306,12 @@ HKD bool indirect_begin(const FrameArgs& A, const Scene& sc, const ChannelArgs& 
         ret = true;
         return false;
     }
-    f3 normal = normalize(tex ? texel_normal(tex->normal) : load_normal(F, A.G, dx, dy));
-    f2 imf = tex ? mk2(tex->imf.x, tex->imf.y) : load_instance_material(F, A.G, dx, dy);
-    uint32_t im_x = f2u32(imf.x), im_y = f2u32(imf.y);
-    f4 velocity_uv = tex ? mk4(tex->vel.x, tex->vel.y, tex->vel.z, tex->vel.w) : load_velocity_uv(F, A.G, dx, dy);
+    indirect_pixel_rest(A, x, y, tex, P);
+    const f3 normal = P.normal;
+    const uint32_t im_x = P.im_x, im_y = P.im_y;
+    const f4 velocity_uv = P.velocity_uv;
 
-    s.random = tex ? noise_of(tex->noise, F.number) : noise_random(A.noise, F.number, x, y);
+    s.random = P.random;
     s.visible_position = mk4(position.x, position.y, position.z, depth);
     s.visible_normal = normal;
     s.visible_instance = im_x;
@@ -1208,72 +1324,13 @@ HKD bool indirect_begin(const FrameArgs& A, const Scene& sc, const ChannelArgs& 
         stash->im_y[t] = im_y;
     }
 
-    Ray ray;
-    HitInfo info;
     float pdf = 0.0f;
-    Surface surface;
-
-    if (MULTI) {
-        Sample bs = s;
-        f3 ct = mk3(1.0f, 1.0f, 1.0f);
-        for (uint32_t n = 0u; n < F.indirect_bounces && (ct.x > 0.01f || ct.y > 0.01f || ct.z > 0.01f); n += 1u) {
-            f4 rs = sample_cosine_hemisphere(mk2(bs.random.x, bs.random.y));
-            ray.origin = xyz(bs.visible_position) + bs.visible_normal * RAY_BIAS;
-            f3 bt, bb;
-            normal_basis(bs.visible_normal, bt, bb);
-            ray.direction = basis_mul(bt, bb, bs.visible_normal, xyz(rs));
-            ray.inv_direction = inv(ray.direction);
-            n_top++;
-            Hit hit = traverse_top(sc, ray, HK_F32_MAX, 0.0f, DONT_EXCLUDE);
-            info = hit_info(sc, ray, hit);
-            if (n == 0u) {
-                s.sample_position = info.position;
-                s.sample_normal = info.normal;
-                pdf = rs.w;
-            }
-            bs.sample_position = info.position;
-            bs.sample_normal = info.normal;
-            if (hit.instance_index != HK_U32_MAX) {
-                f3 out = mk3(0, 0, 0);
-                surface = retreive_surface(sc, info.material_index, info.uv);
-                surface.roughness = 1.0f;
-                LightCandidate cand = select_light_candidate<true>(sc, F, bs.random, xyz(bs.sample_position),
-                                                                   bs.sample_normal, info.instance_index, info, n_emitter);
-                bool sample_directional = cand.emissive_instance == DONT_SAMPLE_EMISSIVE;
-                f3 bvd = normalize(xyz(bs.visible_position) - xyz(bs.sample_position));
-                if (dot(cand.direction, bs.sample_normal) > 0.0f && cand.p > 0.0f) {
-                    ray.origin = xyz(bs.sample_position) + bs.sample_normal * RAY_BIAS;
-                    ray.direction = cand.direction;
-                    ray.inv_direction = inv(ray.direction);
-                    n_top++;
-                    Hit sh = traverse_top(sc, ray, cand.max_distance, cand.min_distance, cand.emissive_instance);
-                    occlude_hit_info(ray, sh, info);
-                    f4 in_rad = input_radiance(sc, F, ray, info, sample_directional, cand.emissive_instance, false);
-                    out = shading(F, bvd, bs.sample_normal, ray.direction, surface, in_rad);
-                    out = out / cand.p;
-                    if (n > 0u) out = rs.w < 0.01f ? mk3(0, 0, 0) : out / rs.w;
-                    float ol = lum(out);
-                    if (ol > F.max_indirect_luminance) out = (out * F.max_indirect_luminance) / ol;
-                    f3 add = ct * out;
-                    s.radiance = mk4(s.radiance.x + add.x, s.radiance.y + add.y, s.radiance.z + add.z, s.radiance.w + 1.0f);
-                }
-                ct = ct * env_brdf(bvd, bs.sample_normal, surface);
-                float fn = (float)F.number * HK_GOLDEN_RATIO;
-                bs.random = mk4(hk_fract(bs.random.x + fn), hk_fract(bs.random.y + fn), hk_fract(bs.random.z + fn),
-                                hk_fract(bs.random.w + fn));
-                bs.visible_position = bs.sample_position;
-                bs.visible_normal = bs.sample_normal;
-            } else {
-                f3 out = xyz(input_radiance(sc, F, ray, info, false, DONT_SAMPLE_EMISSIVE, true));
-                f3 add = ct * out;
-                s.radiance = mk4(s.radiance.x + add.x, s.radiance.y + add.y, s.radiance.z + add.z, s.radiance.w + 0.0f);
-                break;
-            }
-        }
+    if constexpr (MULTI) {
+        pdf = indirect_multi_bounces(sc, F, s, n_top, n_emitter);
+        I.B.s = s;
     } else {
         BounceState B;
         B.s = s;
-        B.ray = ray;
         Hit hit;
         const f4 rs = bounce_ray(B);
         if constexpr (STAGE == IND_SHADE) {
@@ -1292,7 +1349,6 @@ HKD bool indirect_begin(const FrameArgs& A, const Scene& sc, const ChannelArgs& 
         I.shadow = bounce_hit_a(sc, F, B, hit, n_top, n_emitter);
         I.B = B;
     }
-    if (MULTI) I.B.s = s;
     I.x = x;
     I.y = y;
     I.idx = idx;
@@ -1445,9 +1501,7 @@ __global__ __launch_bounds__(256) void k_indirect(FrameArgs A, ChannelArgs C)
         __shared__ IndStash stash;
         indirect_body<MULTI>(A, sc, C, x, y, n_top, n_emitter, nullptr, nullptr, &stash, PRE ? &tex : nullptr);
     }
-    if (!counted(A.F, x, y)) n_top = n_emitter = 0;
-    wave_count(A.cnt.top, n_top);
-    wave_count(A.cnt.emitter, n_emitter);
+    finish_counts(A, x, y, n_top, n_emitter);
 }
 
 // ------------------------------------------------------------------ persistent waves (the north star's layout)
@@ -1540,21 +1594,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     } else if (active) {
         const Scene& sc = A.sc;
         // (its own loads: the texel preload here measured 0-1 % slower on the cornell 2- to 8-way stripes, r06/c16-c17)
-        const DirectPixel P = load_direct_pixel(A, x, y);
-        const uint32_t bg = bg_elide(C0, P.idx, P.pd.w < HK_F32_EPSILON);
-        if (bg == BG_SKIP_OWN) {  // the emissive pass's stores into the spatial pair (direct_body)
-            const Reservoir z = background_reservoir();
-            store_res(C1.spatial, P.idx, z);
-            store_res(C1.prev_spatial, P.idx, z);
-        } else if (bg == BG_STORE) {
-            Surface surface;
-            direct_body<false, true, VD, 2>(A, sc, C0, P, n_top, n_emitter, &surface);
-            direct_body<true, false, VE, 2>(A, sc, C1, P, n_top, n_emitter, nullptr, &surface);
-        }
+        fused_direct_pixel<VD, VE, 2>(A, sc, C0, C1, load_direct_pixel(A, x, y), n_top, n_emitter);
     }
-    if (!counted(A.F, x, y)) n_top = n_emitter = 0;
-    wave_count(A.cnt.top, n_top);
-    wave_count(A.cnt.emitter, n_emitter);
+    finish_counts(A, x, y, n_top, n_emitter);
 }
 
 // ------------------------------------------------------------------ wavefront indirect pass (config 5)
@@ -2569,19 +2611,20 @@ static void launch_fused_v(const FrameArgs& A, const ChannelArgs& C0, const Chan
                            uint32_t lds, hipStream_t st)
 {
     const bool w4 = A.opt.fused_w4 != 0;
+    // The family: the 4-wave kernel takes an emissive-validation frame only unstaged (its validation blocks parked in
+    // LDS); the compacted one replaces it, unstaged, on the frames without one.  Each family has all four (VD, VE) or
+    // (VD, CS) members for either LDS, so dispatch adds no kernel.
     if (!LDS && w4 && !ve && (A.opt.compact_emitter || A.opt.compact_shadow)) {
         // (compact_shadow implies the emitter compaction: one kernel variant per shadow choice)
         dispatch([&](auto VD, auto CS) { hipLaunchKernelGGL((k_direct_fused_cw<VD, CS>), g, dim3(256), lds, st, A, C0, C1); },
                  vd, A.opt.compact_shadow != 0);
-    } else if (!LDS && w4 && ve) {
-        if (vd) hipLaunchKernelGGL((k_direct_fused_w4<LDS, true, true>), g, dim3(256), lds, st, A, C0, C1);
-        else hipLaunchKernelGGL((k_direct_fused_w4<LDS, false, true>), g, dim3(256), lds, st, A, C0, C1);
-    } else if (vd && ve) hipLaunchKernelGGL((k_direct_fused<LDS, true, true>), g, dim3(256), lds, st, A, C0, C1);
-    else if (ve) hipLaunchKernelGGL((k_direct_fused<LDS, false, true>), g, dim3(256), lds, st, A, C0, C1);
-    else if (w4 && vd) hipLaunchKernelGGL((k_direct_fused_w4<LDS, true>), g, dim3(256), lds, st, A, C0, C1);
-    else if (w4) hipLaunchKernelGGL((k_direct_fused_w4<LDS, false>), g, dim3(256), lds, st, A, C0, C1);
-    else if (vd) hipLaunchKernelGGL((k_direct_fused<LDS, true, false>), g, dim3(256), lds, st, A, C0, C1);
-    else hipLaunchKernelGGL((k_direct_fused<LDS, false, false>), g, dim3(256), lds, st, A, C0, C1);
+    } else if (w4 && (!LDS || !ve)) {
+        dispatch([&](auto VD, auto VE) { hipLaunchKernelGGL((k_direct_fused_w4<LDS, VD, VE>), g, dim3(256), lds, st, A, C0, C1); },
+                 vd, ve);
+    } else {
+        dispatch([&](auto VD, auto VE) { hipLaunchKernelGGL((k_direct_fused<LDS, VD, VE>), g, dim3(256), lds, st, A, C0, C1); },
+                 vd, ve);
+    }
 }
 void launch_direct_fused(const FrameArgs& A, const ChannelArgs& C0, const ChannelArgs& C1, hipStream_t st)
 {

@@ -290,7 +290,8 @@ def test_host_gbuffer_planes_bit_exact():
 @pytest.mark.parametrize("lds", ["0", "1"])
 def test_forced_kernel_variants_bit_exact(hk_options, lds):
     """Kernel variants the size thresholds normally pick only at large sizes, forced on a small
-    frame: k_direct_lit_w4 (4 waves per SIMD; direct_w4_min_px=0 with fuse=0), the fused
+    frame: k_direct_lit_w4 (4 waves per SIMD; direct_w4_min_px=0 with fuse=0; fuse=0 alone: the separate
+    k_direct launches of both passes, the same shared body), the fused
     direct+emissive launch next to the indirect side stream (fuse_min_px=0, merge=0: its emitter walks per
     pixel; with compact_emitter=1 compacted per workgroup, k_direct_fused_cw<VD, false>; with compact_shadow=1
     its shadow walks and the indirect pass's compacted too, k_direct_fused_cw<VD, true>) and the
@@ -302,7 +303,7 @@ def test_forced_kernel_variants_bit_exact(hk_options, lds):
     w, h = 64, 48
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0)
     s = st.to_c()
-    for env in ({"direct_w4_min_px": 0, "fuse": 0}, {"fuse_min_px": 0, "merge": 0},
+    for env in ({"direct_w4_min_px": 0, "fuse": 0}, {"fuse": 0}, {"fuse_min_px": 0, "merge": 0},
                 {"fuse_min_px": 0, "merge": 0, "compact_emitter": 1},
                 {"fuse_min_px": 0, "merge": 0, "compact_shadow": 1},
                 {"merge": 1}, {"persistent_indirect": 1, "merge": 0}):
