@@ -130,13 +130,27 @@ constexpr int TRACE_ORDER = RASTER;        // G-buffer and light-pass kernels
 constexpr int DENOISE_ORDER = XCD_STRIPS;  // the a-trous levels (taps up to 8 px away): city 4K 0.529 -> 0.436 ms per level
 
 // ------------------------------------------------------------------ G-buffer
-HKD f3 primary_direction(const ViewArgs& V, float px, float py, const uint32_t* size)
+// The primary ray through (px, py) (oracle/hk_oracle.c primary_ray, step for step).  ORTHO (view.projection[3].w
+// == 1): from the unprojected near-plane point along the negated orthographic view vector of calculate_view;
+// otherwise from the view's world position towards that point.
+template <bool ORTHO>
+HKD Ray primary_ray(const Frame& F, const ViewArgs& V, float px, float py)
 {
-    float ndc_x = (px / (float)size[0]) * 2.0f - 1.0f;
-    float ndc_y = 1.0f - (py / (float)size[1]) * 2.0f;
+    float ndc_x = (px / (float)F.S[0]) * 2.0f - 1.0f;
+    float ndc_y = 1.0f - (py / (float)F.S[1]) * 2.0f;
     f4 p = mat4_mul(V.inverse_view_proj, mk4(ndc_x, ndc_y, 1.0f, 1.0f));
     f3 nearp = mk3(p.x / p.w, p.y / p.w, p.z / p.w);
-    return normalize(nearp - ld3(V.world_position));
+    Ray ray;
+    if constexpr (ORTHO) {
+        const f3 v = normalize(ld3(F.view_proj_z));
+        ray.origin = nearp;
+        ray.direction = mk3(-v.x, -v.y, -v.z);
+    } else {
+        ray.origin = ld3(V.world_position);
+        ray.direction = normalize(nearp - ray.origin);
+    }
+    ray.inv_direction = inv(ray.direction);
+    return ray;
 }
 HKD float ndc_depth(const float* vp, f3 p)
 {
@@ -180,7 +194,8 @@ HKD f4 albedo_of(const Frame& F, const Scene& sc, f4 pd, uint32_t packed_normal,
 }
 
 // albedo != null: the frame's full_screen_albedo is written here too (hk_render_frame skips it)
-template <bool LDS, bool SHALLOW, int LVL = GB_STACK_LDS>
+// ORTHO: the orthographic primary rays (its own instantiation: the perspective kernel's code is as it was)
+template <bool LDS, bool SHALLOW, int LVL = GB_STACK_LDS, bool ORTHO = false>
 __global__ __launch_bounds__(256) void k_gbuffer(FrameArgs A, ViewArgs V, uint2* albedo)
 {
     // The traversal stack's LDS levels, in the launch's dynamic LDS (entry-major, [level][256]): every
@@ -199,10 +214,7 @@ __global__ __launch_bounds__(256) void k_gbuffer(FrameArgs A, ViewArgs V, uint2*
     if (active) {
         n_primary = 1;
         int32_t idx = band_index(A.F, x, y, A.F.S[0], A.F.S_row0, A.F.S_rows);
-        Ray ray;
-        ray.origin = ld3(V.world_position);
-        ray.direction = primary_direction(V, ((float)x + 0.5f) - V.jitter[0], ((float)y + 0.5f) - V.jitter[1], A.F.S);
-        ray.inv_direction = inv(ray.direction);
+        const Ray ray = primary_ray<ORTHO>(A.F, V, ((float)x + 0.5f) - V.jitter[0], ((float)y + 0.5f) - V.jitter[1]);
         Hit hit = closest_hit_ordered<SHALLOW, LVL>(sc, ray, gb_lds_stack);
         if (hit.instance_index == HK_U32_MAX) {
             // a miss stores constant zeros: skipped when this slot already holds them (V.bg)
@@ -241,13 +253,15 @@ __global__ __launch_bounds__(256) void k_gbuffer(FrameArgs A, ViewArgs V, uint2*
             float grad[2];
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
-                f3 d = primary_direction(V, ((float)x + 0.5f + (k == 0 ? 1.0f : 0.0f)) - V.jitter[0],
-                                         ((float)y + 0.5f + (k == 1 ? 1.0f : 0.0f)) - V.jitter[1], A.F.S);
-                float denom = dot(d, ng);
+                // (a perspective neighbour shares the pixel's origin; an orthographic one has its own)
+                const Ray nb = primary_ray<ORTHO>(A.F, V, ((float)x + 0.5f + (k == 0 ? 1.0f : 0.0f)) - V.jitter[0],
+                                                  ((float)y + 0.5f + (k == 1 ? 1.0f : 0.0f)) - V.jitter[1]);
+                const float plane_k = ORTHO ? dot(p - nb.origin, ng) : plane;
+                float denom = dot(nb.direction, ng);
                 grad[k] = 0.0f;
                 if (denom != 0.0f) {
-                    float t = plane / denom;
-                    grad[k] = ndc_depth(V.view_proj, ray.origin + d * t) - depth;
+                    float t = plane_k / denom;
+                    grad[k] = ndc_depth(V.view_proj, nb.origin + nb.direction * t) - depth;
                 }
             }
             A.G.depth_gradient[idx] = make_float2(grad[0], grad[1]);
@@ -2569,19 +2583,26 @@ void launch_gbuffer(const FrameArgs& A, const ViewArgs& V, uint2* albedo, uint32
     const bool small = (double)launch_cols(A.F, A.F.S[0]) * (double)launch_rows(A.F, A.F.S_rows) <= A.opt.gbuffer_lds_max_px;
     const uint32_t scene = lds_plan_bytes(A, PLAN_GBUFFER, small);
     // (scene + stack within the LDS budget of a staged kernel)
-    if (scene && shallow && scene + levels * level_bytes <= LDS_SCENE_MAX + 16384u)
-        hipLaunchKernelGGL((k_gbuffer<true, true>), g, dim3(256), scene + levels * level_bytes, st, A, V, albedo);
-    else if (scene) hipLaunchKernelGGL((k_gbuffer<true, false, 0>), g, dim3(256), scene, st, A, V, albedo);
-    else if (shallow) {
-        // pushes never exceed the bound (hk_runtime gb_stack_need: inner nodes on a TLAS + BLAS path)
-        hipLaunchKernelGGL((k_gbuffer<false, true>), g, dim3(256), levels * level_bytes, st, A, V, albedo);
-    } else {
-        // a deep scene: GB_DEEP_LDS levels in LDS, the rest in scratch (8 levels: 16 KiB per workgroup,
-        // 8 waves/SIMD instead of 5; city 4K G-buffer 0.388 -> 0.362 ms, 4 levels 0.374, scene 1080p
-        // unchanged)
-        hipLaunchKernelGGL((k_gbuffer<false, false, GB_DEEP_LDS>), g, dim3(256), (uint32_t)GB_DEEP_LDS * level_bytes, st, A,
-                           V, albedo);
-    }
+    auto launch = [&](auto ortho) {
+        constexpr bool O = decltype(ortho)::value;
+        if (scene && shallow && scene + levels * level_bytes <= LDS_SCENE_MAX + 16384u)
+            hipLaunchKernelGGL((k_gbuffer<true, true, GB_STACK_LDS, O>), g, dim3(256), scene + levels * level_bytes, st, A, V,
+                               albedo);
+        else if (scene) hipLaunchKernelGGL((k_gbuffer<true, false, 0, O>), g, dim3(256), scene, st, A, V, albedo);
+        else if (shallow) {
+            // pushes never exceed the bound (hk_runtime gb_stack_need: inner nodes on a TLAS + BLAS path)
+            hipLaunchKernelGGL((k_gbuffer<false, true, GB_STACK_LDS, O>), g, dim3(256), levels * level_bytes, st, A, V, albedo);
+        } else {
+            // a deep scene: GB_DEEP_LDS levels in LDS, the rest in scratch (8 levels: 16 KiB per workgroup,
+            // 8 waves/SIMD instead of 5; city 4K G-buffer 0.388 -> 0.362 ms, 4 levels 0.374, scene 1080p
+            // unchanged)
+            hipLaunchKernelGGL((k_gbuffer<false, false, GB_DEEP_LDS, O>), g, dim3(256), (uint32_t)GB_DEEP_LDS * level_bytes,
+                               st, A, V, albedo);
+        }
+    };
+    // view.projection[3].w == 1: the orthographic primary rays (primary_ray)
+    if (A.F.orthographic) launch(std::true_type{});
+    else launch(std::false_type{});
 }
 void launch_albedo(const FrameArgs& A, uint2* albedo, hipStream_t st)
 {

@@ -115,18 +115,49 @@ def perspective_infinite_reverse_rh(fov_y: float, aspect: float, near: float) ->
     return m
 
 
+def orthographic_reverse_rh(left: float, right: float, bottom: float, top: float, near: float, far: float) -> np.ndarray:
+    """Bevy 0.9 `OrthographicProjection::get_projection_matrix`: glam `Mat4::orthographic_rh(left, right,
+    bottom, top, far, near)`, near and far swapped for reverse z (the near plane at ndc z = 1); m[3, 3] == 1."""
+    n, f = far, near  # glam's (near, far) arguments as Bevy passes them
+    r = 1.0 / (n - f)
+    m = np.zeros((4, 4))
+    m[0, 0] = 2.0 / (right - left)
+    m[1, 1] = 2.0 / (top - bottom)
+    m[2, 2] = r
+    m[0, 3] = -(left + right) / (right - left)
+    m[1, 3] = -(top + bottom) / (top - bottom)
+    m[2, 3] = r * n
+    m[3, 3] = 1.0
+    return m
+
+
 @dataclass
 class Camera:
-    """Camera3dBundle with Bevy's default PerspectiveProjection (fov pi/4, near 0.1)."""
+    """Camera3dBundle with Bevy's default PerspectiveProjection (fov pi/4, near 0.1), or, with
+    `orthographic_height` set, an OrthographicProjection of that vertical extent centred on the view axis
+    (ScalingMode::FixedVertical, WindowOrigin::Center, scale 1; `Camera.orthographic`)."""
 
     transform: Transform
     fov_y: float = math.pi / 4.0
     near: float = 0.1
+    orthographic_height: Optional[float] = None
+    far: float = 1000.0  # orthographic only (the perspective projection is infinite)
+
+    @staticmethod
+    def orthographic(transform: Transform, height: float, near: float = 0.0, far: float = 1000.0) -> "Camera":
+        return Camera(transform, near=near, orthographic_height=height, far=far)
+
+    def projection(self, width: int, height: int) -> np.ndarray:
+        if self.orthographic_height is None:
+            return perspective_infinite_reverse_rh(self.fov_y, width / height, self.near)
+        half_h = 0.5 * self.orthographic_height
+        half_w = half_h * (width / height)
+        return orthographic_reverse_rh(-half_w, half_w, -half_h, half_h, self.near, self.far)
 
     def view(self, width: int, height: int) -> _abi.hk_view:
         # the view of an unchanged camera is computed once (the per-frame host work of a static camera is then
         # a struct copy: ~80 -> ~10 us per frame_inputs)
-        key = (width, height, self.fov_y, self.near, tuple(np.asarray(self.transform.translation, np.float64)),
+        key = (width, height, self.fov_y, self.near, self.orthographic_height, self.far, tuple(np.asarray(self.transform.translation, np.float64)),
                tuple(np.asarray(self.transform.rotation, np.float64)), tuple(np.asarray(self.transform.scale, np.float64)))
         cache = self.__dict__.setdefault("_view_cache", {})
         hit = cache.get(key)
@@ -137,7 +168,7 @@ class Camera:
         return _abi.hk_view.from_buffer_copy(hit)
 
     def _view(self, width: int, height: int) -> _abi.hk_view:
-        proj = perspective_infinite_reverse_rh(self.fov_y, width / height, self.near)
+        proj = self.projection(width, height)
         world = self.transform.matrix()
         view_proj = proj @ np.linalg.inv(world)
         v = _abi.hk_view()

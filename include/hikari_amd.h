@@ -114,7 +114,11 @@ typedef struct hk_view {
     float _pad0;
     float view_proj[16];         /* column-major */
     float inverse_view_proj[16]; /* column-major, used by hk_render_gbuffer for ray generation */
-    float projection[16];        /* column-major; projection[3].w == 1 => orthographic */
+    float projection[16];        /* column-major; projection[3].w == 1 => orthographic: the light passes take the
+                                    orthographic view vector normalize(view_proj[0].z, [1].z, [2].z), and
+                                    hk_render_gbuffer starts each primary ray at the unprojection of
+                                    (ndc_x, ndc_y, 1), the near plane, and runs it along the negated view vector
+                                    (otherwise: from world_position through that point) */
 } hk_view;
 
 /* The parts of Bevy's `Lights` uniform the integrator reads (light.wgsl:611,832,847,855). */

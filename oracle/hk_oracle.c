@@ -1712,13 +1712,28 @@ static int emitter_walk_ordered(const hko_ctx* c, Hit* hit, const Ray* ray, cons
     return hit->intersection.distance < d0 || hit->primitive_index != before;
 }
 
-static v3 primary_direction(const hk_view* view, float px, float py, const uint32_t* size)
+/* The primary ray through (px, py) of an S-sized frame (pixel units, y down).  Both kinds start from the
+ * unprojection of (ndc_x, ndc_y, 1), the point on the near plane (reverse z).
+ * Perspective: from view.world_position towards that point.
+ * Orthographic (view.projection[3].w == 1): from that point along the negated orthographic view vector of
+ * calculate_view, -normalize(view_proj[0].z, [1].z, [2].z): the same expression, so a hit's view direction is
+ * exactly opposite its ray.  (The rule is this project's) */
+static Ray primary_ray(const hk_view* view, float px, float py, const uint32_t* size)
 {
     float ndc_x = (px / (float)size[0]) * 2.0f - 1.0f;
     float ndc_y = 1.0f - (py / (float)size[1]) * 2.0f;
     v4 p = mat4_mul(view->inverse_view_proj, V4(ndc_x, ndc_y, 1.0f, 1.0f));
     v3 near = div3s(xyz(p), p.w);
-    return normalize3(sub3(near, ld3(view->world_position)));
+    Ray ray;
+    if (view->projection[15] == 1.0f) {
+        ray.origin = near;
+        ray.direction = neg3(normalize3(V3(view->view_proj[2], view->view_proj[6], view->view_proj[10])));
+    } else {
+        ray.origin = ld3(view->world_position);
+        ray.direction = normalize3(sub3(near, ray.origin));
+    }
+    ray.inv_direction = inv3(ray.direction);
+    return ray;
 }
 /* utils.wgsl:30-35 */
 static v2 clip_to_uv(v4 clip)
@@ -1758,10 +1773,7 @@ static void gbuffer_pixel(const hko_ctx* c, Counts* cnt, const hk_frame_inputs* 
 {
     size_t idx = (size_t)y * c->S[0] + (size_t)x;
     const hk_view* view = &in->view;
-    Ray ray;
-    ray.origin = ld3(view->world_position);
-    ray.direction = primary_direction(view, ((float)x + 0.5f) - G->jitter[0], ((float)y + 0.5f) - G->jitter[1], c->S);
-    ray.inv_direction = inv3(ray.direction);
+    Ray ray = primary_ray(view, ((float)x + 0.5f) - G->jitter[0], ((float)y + 0.5f) - G->jitter[1], c->S);
     cnt->primary++;
     Counts dummy = {0, 0, 0};
     (void)dummy;
@@ -1790,16 +1802,17 @@ static void gbuffer_pixel(const hko_ctx* c, Counts* cnt, const hk_frame_inputs* 
     v3 w1 = instance_position_local_to_world(instance, ld3(tv[1].position));
     v3 w2 = instance_position_local_to_world(instance, ld3(tv[2].position));
     v3 ng = cross3(sub3(w1, w0), sub3(w2, w0));
-    float plane = dot3(sub3(p, ray.origin), ng);
     float grad[2];
     for (int k = 0; k < 2; ++k) {
-        v3 d = primary_direction(view, ((float)x + 0.5f + (k == 0 ? 1.0f : 0.0f)) - G->jitter[0],
-                                 ((float)y + 0.5f + (k == 1 ? 1.0f : 0.0f)) - G->jitter[1], c->S);
-        float denom = dot3(d, ng);
+        /* (a perspective neighbour shares the pixel's origin; an orthographic one has its own) */
+        Ray nb = primary_ray(view, ((float)x + 0.5f + (k == 0 ? 1.0f : 0.0f)) - G->jitter[0],
+                             ((float)y + 0.5f + (k == 1 ? 1.0f : 0.0f)) - G->jitter[1], c->S);
+        float plane = dot3(sub3(p, nb.origin), ng);
+        float denom = dot3(nb.direction, ng);
         grad[k] = 0.0f;
         if (denom != 0.0f) {
             float t = plane / denom;
-            v3 q = add3(ray.origin, scale3(d, t));
+            v3 q = add3(nb.origin, scale3(nb.direction, t));
             grad[k] = ndc_depth(view->view_proj, q) - depth;
         }
     }
@@ -2469,11 +2482,7 @@ void hko_primary_hits(hko_ctx* c, const hk_frame_inputs* in, uint32_t* out)
 #pragma omp parallel for schedule(dynamic, 4) HKO_THREADS(c)
     for (long long y = 0; y < (long long)c->S[1]; ++y)
         for (uint32_t x = 0; x < c->S[0]; ++x) {
-            Ray ray;
-            ray.origin = ld3(in->view.world_position);
-            ray.direction = primary_direction(&in->view, ((float)x + 0.5f) - jitter[0],
-                                              ((float)y + 0.5f) - jitter[1], c->S);
-            ray.inv_direction = inv3(ray.direction);
+            Ray ray = primary_ray(&in->view, ((float)x + 0.5f) - jitter[0], ((float)y + 0.5f) - jitter[1], c->S);
             Counts k = {0, 0, 0};
             Hit a = closest_hit_ordered(c, &ray);
             Hit b = traverse_top(c, &k, &ray, HK_F32_MAX, 0.0f, DONT_EXCLUDE);

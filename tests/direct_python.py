@@ -522,14 +522,18 @@ def check_previous_reservoir(r, s):
 def direct_lit(sc, fr, gb, noise, bufs, x, y, emissive_lit, counts):
     """One pixel of one direct pass; writes into bufs {'prev', 'cur', 'prev_spatial', 'spatial':
     (N, 16) u32 arrays; 'variance': (H, W) f32; 'render': (H, W, 4) f32 (rounded to f16)}."""
-    W, H = fr["size"]
+    W, H = fr["size"]  # render_size: the reservoir index, the pixel's uv and the previous-uv coordinates
+    DW, DH = fr.get("deferred_size", fr["size"])  # textureDimensions(position_texture): light.wgsl:1007-1017
     idx = x + W * y
     n = fr["number"]
     uv = ((F(x) + F(0.5)) / F(W), (F(y) + F(0.5)) / F(H))
     j = F(-0.25) if n & 1 == 0 else F(0.25)
-    duv = tuple(uv[k] + (j * (F(1.0) / F(fr["size"][k]))) * (fr["ratio"] - F(1.0)) for k in range(2))
-    dx, dy = f2i(duv[0] * F(W)), f2i(duv[1] * F(H))
-    pd = gb["position"][dy, dx]
+    duv = tuple(uv[k] + (j * (F(1.0) / F((DW, DH)[k]))) * (fr["ratio"] - F(1.0)) for k in range(2))
+    dx, dy = f2i(duv[0] * F(DW)), f2i(duv[1] * F(DH))
+    if "deferred_lookups" in counts:
+        counts["deferred_lookups"].append((uv, (dx, dy)))
+    # textureLoad outside the texture returns zero: depth 0, the background branch
+    pd = gb["position"][dy, dx] if 0 <= dx < DW and 0 <= dy < DH else np.zeros(4, F)
     position = (pd[0], pd[1], pd[2], F(1.0))
     depth = pd[3]
     s = zero_reservoir()
@@ -637,7 +641,10 @@ def direct_lit(sc, fr, gb, noise, bufs, x, y, emissive_lit, counts):
         bufs["cur"][idx] = pack_reservoir(r)
     surface = retreive_surface(sc, im_y)
     wp = position[:3]
-    V = normalize(sub(fr["view_position"], wp))
+    if fr.get("orthographic_view") is not None:  # calculate_view(position, view.projection[3].w == 1.0)
+        V = normalize(fr["orthographic_view"])
+    else:
+        V = normalize(sub(fr["view_position"], wp))
     L = normalize(sub(r["sample_position"][:3], r["visible_position"][:3]))
     with np.errstate(all="ignore"):
         out = scale(shading(sc, fr, V, r["visible_normal"], L, surface, r["radiance"]), r["w"])

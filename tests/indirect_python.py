@@ -72,6 +72,7 @@ class Frame:
         self.size = fr["size"]              # render (integrator) size s
         self.dsize = fr.get("deferred_size", fr["size"])  # G-buffer size S
         self.ratio = fr["ratio"]
+        self.lookups = None  # a list: every deferred lookup's (uv, coords) is appended (test instrumentation)
 
     def jittered_uv(self, uv, amplitude=F(0.25)):
         j = -amplitude if (self.n & 1) == 0 else amplitude
@@ -80,7 +81,10 @@ class Frame:
 
     def deferred_coords(self, uv):
         d = self.jittered_uv(uv)
-        return dp.f2i(d[0] * F(self.dsize[0])), dp.f2i(d[1] * F(self.dsize[1]))
+        c = dp.f2i(d[0] * F(self.dsize[0])), dp.f2i(d[1] * F(self.dsize[1]))
+        if self.lookups is not None:
+            self.lookups.append((uv, c))
+        return c
 
     def load(self, plane, c):
         """textureLoad: out-of-bounds reads return zero."""
@@ -100,7 +104,11 @@ class Frame:
         return tuple(dp.fract(F(t) / F(255.0) + fn) for t in texel)
 
     def view_direction(self, position):
-        """calculate_view, perspective branch (the example cameras are perspective)."""
+        """calculate_view (light.wgsl:714-727): the orthographic view vector normalize(view_proj[0].z, [1].z,
+        [2].z) when view.projection[3].w == 1 (fr["orthographic_view"], those three components), else the
+        direction to the view's world position."""
+        if self.fr.get("orthographic_view") is not None:
+            return dp.normalize(self.fr["orthographic_view"])
         return dp.normalize(dp.sub(self.fr["view_position"], position[:3]))
 
 
