@@ -252,9 +252,11 @@ HKD Scene stage_scene(const Scene& g, uint32_t* lds)
     uint32_t* dst[SCENE_ARRAYS];
     uint4* const lds4 = reinterpret_cast<uint4*>(lds);  // (hk_lds_scene is 16-byte aligned)
     // The plan's arrays as one list of 16-byte chunks (array k at chunk off4[k], its last chunk rounded up: the
-    // bytes read past an array's end lie in the same 16-byte block of its own allocation, and no reader looks at
-    // them in LDS), copied four chunks per thread per iteration with the four loads issued before any store
-    // (cornell: 12 KiB, ~770 chunks, one iteration).
+    // bytes read past an array's end lie in the same 16-byte block of its own allocation — hk_scene_upload rounds
+    // the allocations of arrays 0..8 up to 16 bytes (staged_alloc_bytes), the wide layouts and walk-node copies are
+    // whole chunks per node, and an empty array has no chunk — and no reader looks at them in LDS), copied four
+    // chunks per thread per iteration with the four loads issued before any store (cornell: 12 KiB, ~770 chunks,
+    // one iteration; above 1024 chunks a second one).
     uint32_t off4[SCENE_ARRAYS];
     uint32_t total = 0;
 #pragma unroll

@@ -633,6 +633,19 @@ void flush_timing(hk_ctx* c)
     c->pending.clear();
 }
 
+// Scene::bytes of a scene with these element counts (hk_scene_desc order; arrays 9 and 10 are the wide
+// layouts of the asset and instance nodes, WIDE_NODE_BYTES per node): what stage_bytes sums per plan
+constexpr size_t WIDE_NODE_BYTES = 64;
+constexpr size_t SCENE_ELEM[9] = {sizeof(hk_vertex), sizeof(hk_primitive), sizeof(hk_node), sizeof(hk_alias_entry),
+                                  sizeof(hk_instance), sizeof(hk_node), sizeof(hk_material), sizeof(hk_node),
+                                  sizeof(hk_emissive)};
+static void scene_array_bytes(const uint32_t* count, uint32_t* bytes)
+{
+    for (int k = 0; k < 9; ++k) bytes[k] = (uint32_t)std::min<size_t>((size_t)count[k] * SCENE_ELEM[k], 0xFFFFFFF0u);
+    bytes[9] = (uint32_t)std::min<size_t>((size_t)count[2] * WIDE_NODE_BYTES, 0xFFFFFFF0u);
+    bytes[10] = (uint32_t)std::min<size_t>((size_t)count[5] * WIDE_NODE_BYTES, 0xFFFFFFF0u);
+}
+
 FrameArgs frame_args(hk_ctx* c, const hk_settings* st, const hk_frame_inputs* in)
 {
     FrameArgs A;
@@ -656,14 +669,7 @@ FrameArgs frame_args(hk_ctx* c, const hk_settings* st, const hk_frame_inputs* in
     A.sc.texels = c->texels;
     A.sc.texture_lut = c->tex_lut;
     A.sc.n_textures = c->n_textures;
-    {
-        const size_t elem[9] = {sizeof(hk_vertex), sizeof(hk_primitive), sizeof(hk_node), sizeof(hk_alias_entry),
-                                sizeof(hk_instance), sizeof(hk_node), sizeof(hk_material), sizeof(hk_node),
-                                sizeof(hk_emissive)};
-        for (int k = 0; k < 9; ++k) A.sc.bytes[k] = (uint32_t)std::min<size_t>((size_t)c->count[k] * elem[k], 0xFFFFFFF0u);
-        A.sc.bytes[9] = (uint32_t)std::min<size_t>((size_t)c->count[2] * 64, 0xFFFFFFF0u);
-        A.sc.bytes[10] = (uint32_t)std::min<size_t>((size_t)c->count[5] * 64, 0xFFFFFFF0u);
-    }
+    scene_array_bytes(c->count, A.sc.bytes);
     Frame& F = A.F;
     hk_settings def;
     hk_settings_default(&def);
@@ -1034,48 +1040,19 @@ int hk_get_option(const hk_ctx* c, const char* key, double* value)
 
 const char* hk_option_name(int index) { return index >= 0 && index < OPT_COUNT ? OPTS[index].key : nullptr; }
 
-int hk_scene_upload(hk_ctx* c, const hk_scene_desc* d)
+// Allocation size of a scene array that stage_scene may copy: its last 16-byte chunk is read whole, so the
+// size is rounded up to 16 (hk_alias_entry is 8 bytes; an empty array keeps one zeroed element)
+static size_t staged_alloc_bytes(size_t count, size_t elem) { return ((count ? count : 1) * elem + 15) & ~(size_t)15; }
+
+// Stack bound of closest_hit_ordered for a scene (pushes along a path <= inner subtree starts on it): the inner
+// levels of the TLAS plus those of the deepest instanced BLAS.  false: an instance's node range is outside the
+// asset nodes.
+static bool scene_stack_need(const hk_scene_desc* d, uint32_t* need, uint32_t* blas_depth_out)
 {
-    if (!c || !d) return HK_ERR_INVALID;
-    (void)hipSetDevice(c->device);
-    HK_TRY(c->sch.gb_serialize(true));
-    const hk_array* arr[9] = {&d->vertices, &d->primitives, &d->asset_nodes, &d->alias_table, &d->instances,
-                              &d->instance_nodes, &d->materials, &d->emissive_nodes, &d->emissives};
-    const size_t elem[9] = {sizeof(hk_vertex), sizeof(hk_primitive), sizeof(hk_node), sizeof(hk_alias_entry),
-                            sizeof(hk_instance), sizeof(hk_node), sizeof(hk_material), sizeof(hk_node),
-                            sizeof(hk_emissive)};
-    if (d->instances.count == 0 || d->materials.count == 0)
-        return fail(c, HK_ERR_INVALID, "scene needs at least one instance and one material");
-    c->gen++;
-    for (int i = 0; i < 9; ++i)
-        if (arr[i]->count && !arr[i]->data) return fail(c, HK_ERR_INVALID, "scene array with count but no data");
-    HK_HIP(c, hipStreamSynchronize(c->stream));
-    for (int i = 0; i < 9; ++i) {
-        release(c->buf[i]);
-        size_t bytes = (size_t)(arr[i]->count ? arr[i]->count : 1) * elem[i];
-        HK_HIP(c, hipMalloc(&c->buf[i], bytes));
-        HK_HIP(c, hipMemset(c->buf[i], 0, bytes));
-        if (arr[i]->count) HK_HIP(c, hipMemcpy(c->buf[i], arr[i]->data, arr[i]->count * elem[i], hipMemcpyHostToDevice));
-        c->count[i] = arr[i]->count;
-    }
-    // leaf boxes of the device node copies (see k_fill_blas_leaves) and the wide layout of the
-    // G-buffer traversal: BLAS node -> primitive offset / node range of the mesh that owns it,
-    // from the instances' mesh indices
     const uint32_t n_blas = d->asset_nodes.count, n_tlas = d->instance_nodes.count;
-    std::vector<uint32_t> prim_offset(n_blas, HK_U32_MAX), node_base(n_blas, HK_U32_MAX), node_count(n_blas, 0);
     const hk_instance* inst = (const hk_instance*)d->instances.data;
     const hk_node* blas = (const hk_node*)d->asset_nodes.data;
     const hk_node* tlas = (const hk_node*)d->instance_nodes.data;
-    for (uint32_t k = 0; k < d->instances.count; ++k) {
-        const hk_mesh_index& m = inst[k].mesh;
-        if ((size_t)m.node[0] + m.node[1] > n_blas) return fail(c, HK_ERR_INVALID, "instance mesh node range outside asset nodes");
-        for (uint32_t j = 0; j < m.node[1]; ++j) {
-            prim_offset[m.node[0] + j] = m.primitive;
-            node_base[m.node[0] + j] = m.node[0];
-            node_count[m.node[0] + j] = m.node[1];
-        }
-    }
-    // stack bound of closest_hit_ordered: pushes along a path <= inner subtree starts on it
     auto depth = [](const hk_node* f, uint32_t count) {
         std::vector<uint32_t> dep(count + 1, 0);
         uint32_t best = 0;
@@ -1091,11 +1068,85 @@ int hk_scene_upload(hk_ctx* c, const hk_scene_desc* d)
     uint32_t blas_depth = 0;
     for (uint32_t k = 0; k < d->instances.count; ++k) {
         const hk_mesh_index& m = inst[k].mesh;
+        if ((size_t)m.node[0] + m.node[1] > n_blas) return false;
         uint32_t dd = depth(blas + m.node[0], m.node[1]);
         blas_depth = dd > blas_depth ? dd : blas_depth;
     }
-    c->gb_stack_need = depth(tlas, n_tlas) + blas_depth;
-    c->gb_blas_depth = blas_depth;
+    *need = depth(tlas, n_tlas) + blas_depth;
+    if (blas_depth_out) *blas_depth_out = blas_depth;
+    return true;
+}
+
+static bool scene_desc_ok(const hk_scene_desc* d)
+{
+    const hk_array* arr[9] = {&d->vertices, &d->primitives, &d->asset_nodes, &d->alias_table, &d->instances,
+                              &d->instance_nodes, &d->materials, &d->emissive_nodes, &d->emissives};
+    for (int i = 0; i < 9; ++i)
+        if (arr[i]->count && !arr[i]->data) return false;
+    return true;
+}
+
+int hk_scene_stage_bytes(const hk_scene_desc* d, int plan, uint32_t* bytes, uint32_t* limit)
+{
+    if (!d || (plan != PLAN_LIGHT && plan != PLAN_GBUFFER)) return HK_ERR_INVALID;
+    const uint32_t count[9] = {d->vertices.count,  d->primitives.count,     d->asset_nodes.count,
+                               d->alias_table.count, d->instances.count,    d->instance_nodes.count,
+                               d->materials.count, d->emissive_nodes.count, d->emissives.count};
+    uint32_t b[SCENE_ARRAYS];
+    scene_array_bytes(count, b);
+    if (bytes) *bytes = stage_bytes(b, plan);
+    if (limit) *limit = LDS_SCENE_MAX;
+    return HK_OK;
+}
+
+int hk_scene_gbuffer_stack(const hk_scene_desc* d, uint32_t* need, uint32_t* lds_levels)
+{
+    if (!d || !scene_desc_ok(d)) return HK_ERR_INVALID;
+    uint32_t n = 0;
+    if (!scene_stack_need(d, &n, nullptr)) return HK_ERR_INVALID;
+    if (need) *need = n;
+    if (lds_levels) *lds_levels = (uint32_t)GB_STACK_LDS;
+    return HK_OK;
+}
+
+int hk_scene_upload(hk_ctx* c, const hk_scene_desc* d)
+{
+    if (!c || !d) return HK_ERR_INVALID;
+    (void)hipSetDevice(c->device);
+    HK_TRY(c->sch.gb_serialize(true));
+    const hk_array* arr[9] = {&d->vertices, &d->primitives, &d->asset_nodes, &d->alias_table, &d->instances,
+                              &d->instance_nodes, &d->materials, &d->emissive_nodes, &d->emissives};
+    const size_t* elem = SCENE_ELEM;
+    if (d->instances.count == 0 || d->materials.count == 0)
+        return fail(c, HK_ERR_INVALID, "scene needs at least one instance and one material");
+    c->gen++;
+    for (int i = 0; i < 9; ++i)
+        if (arr[i]->count && !arr[i]->data) return fail(c, HK_ERR_INVALID, "scene array with count but no data");
+    HK_HIP(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < 9; ++i) {
+        release(c->buf[i]);
+        size_t bytes = staged_alloc_bytes(arr[i]->count, elem[i]);
+        HK_HIP(c, hipMalloc(&c->buf[i], bytes));
+        HK_HIP(c, hipMemset(c->buf[i], 0, bytes));
+        if (arr[i]->count) HK_HIP(c, hipMemcpy(c->buf[i], arr[i]->data, arr[i]->count * elem[i], hipMemcpyHostToDevice));
+        c->count[i] = arr[i]->count;
+    }
+    // leaf boxes of the device node copies (see k_fill_blas_leaves) and the wide layout of the
+    // G-buffer traversal: BLAS node -> primitive offset / node range of the mesh that owns it,
+    // from the instances' mesh indices
+    const uint32_t n_blas = d->asset_nodes.count, n_tlas = d->instance_nodes.count;
+    std::vector<uint32_t> prim_offset(n_blas, HK_U32_MAX), node_base(n_blas, HK_U32_MAX), node_count(n_blas, 0);
+    const hk_instance* inst = (const hk_instance*)d->instances.data;
+    for (uint32_t k = 0; k < d->instances.count; ++k) {
+        const hk_mesh_index& m = inst[k].mesh;
+        if ((size_t)m.node[0] + m.node[1] > n_blas) return fail(c, HK_ERR_INVALID, "instance mesh node range outside asset nodes");
+        for (uint32_t j = 0; j < m.node[1]; ++j) {
+            prim_offset[m.node[0] + j] = m.primitive;
+            node_base[m.node[0] + j] = m.node[0];
+            node_count[m.node[0] + j] = m.node[1];
+        }
+    }
+    (void)scene_stack_need(d, &c->gb_stack_need, &c->gb_blas_depth);  // (node ranges checked above)
     release(c->dyn_scratch);
     c->dyn_bytes = 0;
     uint32_t* d_aux = nullptr;
@@ -1113,8 +1164,10 @@ int hk_scene_upload(hk_ctx* c, const hk_scene_desc* d)
     release(c->walk_nodes[0]);
     release(c->walk_nodes[1]);
     release(c->collapse_scratch);
-    HK_HIP(c, hipMalloc(&c->blas_wide, (size_t)(n_blas ? n_blas : 1) * 64));
-    HK_HIP(c, hipMalloc(&c->tlas_wide, (size_t)(n_tlas ? n_tlas : 1) * 64));
+    // (the wide layouts and the walk-node copies below are 64 and 32 bytes per node: whole 16-byte chunks for
+    // stage_scene without rounding)
+    HK_HIP(c, hipMalloc(&c->blas_wide, (size_t)(n_blas ? n_blas : 1) * WIDE_NODE_BYTES));
+    HK_HIP(c, hipMalloc(&c->tlas_wide, (size_t)(n_tlas ? n_tlas : 1) * WIDE_NODE_BYTES));
     launch_build_wide((const hk_node*)c->buf[2], n_blas, d_aux + n_blas, d_aux + 2 * (size_t)n_blas, c->blas_wide,
                       c->stream);
     launch_build_wide((const hk_node*)c->buf[5], n_tlas, nullptr, nullptr, c->tlas_wide, c->stream);

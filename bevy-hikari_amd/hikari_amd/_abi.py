@@ -145,6 +145,8 @@ def lib() -> C.CDLL:
         "hk_get_option": (i32, [vp, C.c_char_p, C.POINTER(C.c_double)]),
         "hk_option_name": (C.c_char_p, [i32]),
         "hk_scene_upload": (i32, [vp, C.POINTER(hk_scene_desc)]),
+        "hk_scene_stage_bytes": (i32, [C.POINTER(hk_scene_desc), i32, C.POINTER(u32), C.POINTER(u32)]),
+        "hk_scene_gbuffer_stack": (i32, [C.POINTER(hk_scene_desc), C.POINTER(u32), C.POINTER(u32)]),
         "hk_set_noise": (i32, [vp, vp, u32, u32]),
         "hk_texture_upload": (i32, [vp, vp, u32]),
         "hk_resize": (i32, [vp, u32, u32, C.c_float, u32, u32]),
@@ -204,7 +206,7 @@ def lib() -> C.CDLL:
 # symbols include/*.h declare (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = [
     "hk_abi_version", "hk_create", "hk_destroy", "hk_last_error", "hk_settings_default", "hk_set_option",
-    "hk_get_option", "hk_option_name", "hk_scene_upload",
+    "hk_get_option", "hk_option_name", "hk_scene_upload", "hk_scene_stage_bytes", "hk_scene_gbuffer_stack",
     "hk_set_noise", "hk_texture_upload", "hk_resize", "hk_resize_striped", "hk_set_band_halo", "hk_band_info", "hk_band_window_grow", "hk_reservoir_rows", "hk_resize_tile", "hk_tile_info", "hk_copy_output_rect", "hk_copy_output_rows", "hk_render_gbuffer", "hk_set_gbuffer_plane", "hk_render_frame",
     "hk_denoise", "hk_tone_sum", "hk_update_instances", "hk_read_scene_array", "hk_post_process", "hk_accumulate", "hk_resolve_accumulation", "hk_output_info", "hk_get_output", "hk_output_device_ptr", "hk_sync", "hk_set_wavefront", "hk_lane_stats", "hk_dump_reservoirs",
     "hk_load_reservoirs", "hk_reset_counters", "hk_read_counters", "hk_enable_kernel_timing", "hk_kernel_timing", "hk_set_kernel_timing_interval",

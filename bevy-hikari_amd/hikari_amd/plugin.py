@@ -39,6 +39,29 @@ def _check(ctx, rc: int, what: str) -> None:
         raise _abi.HikariError(f"{what} failed ({rc}): {msg}")
 
 
+PLAN_LIGHT, PLAN_GBUFFER = 0, 1
+
+
+def scene_stage_bytes(scene, plan: int):
+    """(bytes, limit) of hk_scene_stage_bytes: what the traversal kernels of `plan` (PLAN_LIGHT, PLAN_GBUFFER)
+    stage into LDS for this scene (a Scene or its hk_scene_desc), and the size up to which they stage at all.
+    Host arithmetic only: needs no device."""
+    desc = scene if isinstance(scene, _abi.hk_scene_desc) else (scene.desc if scene.desc is not None else scene.build())
+    b, lim = C.c_uint32(), C.c_uint32()
+    _check(None, _abi.lib().hk_scene_stage_bytes(C.byref(desc), int(plan), C.byref(b), C.byref(lim)),
+           "hk_scene_stage_bytes")
+    return b.value, lim.value
+
+
+def scene_gbuffer_stack(scene):
+    """(need, lds_levels) of hk_scene_gbuffer_stack: the G-buffer walk's stack bound for this scene as
+    hk_scene_upload computes it, and the levels the shallow walk keeps in LDS."""
+    desc = scene if isinstance(scene, _abi.hk_scene_desc) else (scene.desc if scene.desc is not None else scene.build())
+    n, lv = C.c_uint32(), C.c_uint32()
+    _check(None, _abi.lib().hk_scene_gbuffer_stack(C.byref(desc), C.byref(n), C.byref(lv)), "hk_scene_gbuffer_stack")
+    return n.value, lv.value
+
+
 class HikariRenderer:
     """A camera's integrator context (hk_ctx)."""
 

@@ -247,6 +247,15 @@ int hk_set_noise(hk_ctx* ctx, const uint8_t* rgba8, uint32_t count, uint32_t siz
  * Bevy `Aabb`: center xyz, half_extents xyz).  count must equal the uploaded instance count
  * (same order, meshes and materials).  Waits for the stream once (singular-matrix check). */
 int hk_update_instances(hk_ctx* ctx, const float* models, const float* local_aabbs, uint32_t count, void* stream);
+/* LDS staging of a scene, computed on the host with the launchers' own arithmetic (needs no device or context):
+ * the bytes the traversal kernels of `plan` (0: the light passes' arrays, hk_scene_desc's nine; 1: the G-buffer
+ * walk's vertices, primitives, instances and the two wide node layouts) copy into LDS, each array rounded up to
+ * 16 bytes, and the limit up to which a scene is staged at all (option lds_scene).  bytes <= limit: staged. */
+int hk_scene_stage_bytes(const hk_scene_desc* scene, int plan, uint32_t* bytes, uint32_t* limit);
+/* The G-buffer walk's stack bound for a scene as hk_scene_upload computes it (inner levels of the TLAS plus those
+ * of the deepest instanced BLAS) and the levels the shallow walk can keep in LDS: need <= lds_levels takes the
+ * shallow kernel, whose stack follows a staged scene only while bytes + need * 2048 <= limit + 16384. */
+int hk_scene_gbuffer_stack(const hk_scene_desc* scene, uint32_t* need, uint32_t* lds_levels);
 /* copy group-2 scene array `array` (0..8, hk_scene_desc order) back from the device (test/debug) */
 int hk_read_scene_array(hk_ctx* ctx, int array, void* dst, size_t bytes);
 

@@ -20,7 +20,8 @@ def declared_symbols():
 def test_headers_declare_expected_entry_points():
     names = declared_symbols()
     for required in ("hk_create", "hk_destroy", "hk_scene_upload", "hk_resize", "hk_render_frame", "hk_denoise",
-                     "hk_tone_sum", "hk_get_output", "hk_trace", "hk_last_error", "hks_build"):
+                     "hk_tone_sum", "hk_get_output", "hk_trace", "hk_last_error", "hks_build", "hk_scene_stage_bytes",
+                     "hk_scene_gbuffer_stack"):
         assert required in names
 
 

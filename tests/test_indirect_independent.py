@@ -6,7 +6,8 @@ kernels were written by the same hands from the same reading of the WGSL, so a m
 pass both.  tests/indirect_python.py restates `indirect_lit_ambient` (one bounce and MULTIPLE_BOUNCES)
 and `spatial_reuse` (indirect and EMISSIVE_LIT) from light.wgsl, tests/denoise_python.py restates
 denoise.wgsl in float32 (demodulation, the four à-trous levels, FIREFLY_FILTERING), both without the
-oracle's code.  Here the oracle renders frames 0..5 of the cornell, scene.rs and city.rs layouts; for
+oracle's code.  Here the oracle renders frames 0..5 of the cornell, scene.rs and city.rs layouts and of three
+rungs of tests/scene_ladder.py (three emitters, no emitter, a single emissive triangle; at 16x12); for
 each frame the restatements run on the oracle's G-buffer and the reservoir buffers as they were before
 the frame (history carried by the oracle, so every frame is an independent check) and every stored word
 must equal the oracle's: the channels' render and variance planes, all reservoir buffers the passes
@@ -25,8 +26,11 @@ import pytest
 import denoise_python as dnp
 import direct_python as dp
 import indirect_python as ip
+import scene_ladder as sl
 
 W, H = 24, 20
+# the ladder rungs (tests/scene_ladder.py) at a smaller frame: the three of them together cost about one example scene
+LADDER_SIZE = (16, 12)
 
 
 def _gbuffer(o, w, h):
@@ -76,12 +80,14 @@ def _check_channel(o, ch, bufs, spatial_pair_ids, tag):
 
 
 @pytest.mark.parametrize("variant", ["default", "multi"])
-@pytest.mark.parametrize("scene_fn", ["cornell", "scene", "city"])
+@pytest.mark.parametrize("scene_fn", ["cornell", "scene", "city", "emitters_3", "no_emitters", "one_triangle"])
 def test_indirect_spatial_denoise_match_python_restatement(scene_fn, variant):
     import oracle as orc
     from hikari_amd import HikariSettings, Taa, Upscale, examples, frame_inputs, load_noise
     from oracle import Oracle
-    scene, cam, lights = examples.SCENES[scene_fn]()
+    global W, H
+    W, H = LADDER_SIZE if scene_fn in sl.RUNGS else (24, 20)
+    scene, cam, lights = sl.example_or_rung(scene_fn)
     desc = scene.build()
     sc = dp.Scene(scene.arrays(), orc.lib())
     noise = load_noise().reshape(16, 64, 64, 4)
