@@ -16,7 +16,7 @@ ROOT = Path(__file__).resolve().parents[2]
 for p in (ROOT / "bevy-hikari_amd", ROOT / "oracle", ROOT / "tests"):
     sys.path.insert(0, str(p))
 
-from parity import canon_plane, canon_reservoirs  # noqa: E402
+from parity import canon_plane, canon_reservoirs, passes  # noqa: E402
 
 W, H, FRAMES = 32, 24, 6
 VARIANTS = {
@@ -52,10 +52,7 @@ def render(src_factory, variant):
     frames = []
     for f in range(FRAMES):
         fi = frame_inputs(f, cam, lights, W, H)
-        src.render_gbuffer(fi)
-        src.render_frame(s, fi)
-        src.denoise(s, fi)
-        src.tone_sum(s)
+        passes(src, s, fi)
         frames.append(digest_frame(src))
     return frames, src.output(10)
 

@@ -21,6 +21,8 @@ import math
 
 import numpy as np
 
+from parity import canon_frame, passes
+
 SEED = 0x4C414444  # "LADD"
 
 # rung -> emitters: triangles per slab; boxes: triangles per box (the last one is the size axis); materials: unused
@@ -203,20 +205,12 @@ def ladder_settings(bounces: int = 1):
                           denoise=True, indirect_bounces=bounces)
 
 
-def passes(x, s, fi):
-    x.render_gbuffer(fi)
-    x.render_frame(s, fi)
-    x.denoise(s, fi)
-    x.tone_sum(s)
-
-
 def reference(name: str, bounces: int = 1, emissive: bool = True, frames: int = FRAMES):
     """The oracle's frames of a rung at SIZE under ladder_settings, computed once per process and shared by every
     test that compares against them: per frame the canonical words of planes 0..16 and of the ten reservoir buffers,
     and after the last frame the ray counters."""
     from hikari_amd import frame_inputs, load_noise
     from oracle import Oracle
-    from parity import canon_plane, canon_reservoirs
     key = (name, bounces, emissive, frames)
     if key not in _reference:
         scene, cam, lights = built(name, emissive)
@@ -226,8 +220,7 @@ def reference(name: str, bounces: int = 1, emissive: bool = True, frames: int = 
         out = []
         for f in range(frames):
             passes(o, s, frame_inputs(f, cam, lights, w, h))
-            out.append(([canon_plane(oid, o.output(oid)) for oid in range(17)],
-                        [canon_reservoirs(o.reservoirs(rid)) for rid in range(10)]))
+            out.append(canon_frame(o))
         _reference[key] = (out, o.counters())
         o.close()
     return _reference[key]

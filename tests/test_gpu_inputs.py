@@ -16,25 +16,14 @@ import numpy as np
 import pytest
 
 import inputs_cases as ic
-from parity import canon_plane, mismatch_report
-from test_gpu_motion import RACY, _compare, _orbit, _pair
-from test_gpu_parity import _compare_frame
+from parity import RACY, compare_frame, orbit_camera, pair, passes, run_static
 
 pytestmark = pytest.mark.gpu
 
-POST_OUTPUTS = (18, 19)  # OUT_UPSCALED, OUT_TAA (RGBA16F, as the tone-mapped plane)
+WITH_POST = tuple(range(17)) + (18, 19)  # and OUT_UPSCALED, OUT_TAA (RGBA16F, as the tone-mapped plane)
 
 
-def _passes(x, s, fi, post=False):
-    x.render_gbuffer(fi)
-    x.render_frame(s, fi)
-    x.denoise(s, fi)
-    x.tone_sum(s)
-    if post:
-        x.post_process(s, fi)
-
-
-def _compare_sizes(r, o):
+def _check_sizes(r, o):
     """hk_output_info against the oracle's plane sizes, outputs 0..19 (17, the sub-frame accumulator, is the
     runtime's own: the oracle has none)."""
     for oid in range(20):
@@ -44,13 +33,6 @@ def _compare_sizes(r, o):
             assert oid == 17
             continue
         assert r.output_info(oid) == (w, h, b), (oid, r.output_info(oid), (w, h, b))
-
-
-def _compare_post(r, o, frame, errors):
-    for oid in POST_OUTPUTS:
-        m = mismatch_report(canon_plane(10, r.output(oid)), canon_plane(10, o.output(oid)), f"frame {frame} output {oid}")
-        if m:
-            errors.append(m)
 
 
 FRACTIONAL = [(1.5, (63, 47), "cornell_textured", None),
@@ -84,9 +66,7 @@ def test_fractional_upscale_ratio_bit_exact(hk_options, case):
         hk_options.update(variant)
     st = HikariSettings(upscale=Upscale.smaa_tu4x(ratio), taa=Taa.Jasmine, emissive_spatial_reuse=True,
                         indirect_bounces=2, denoise=True)
-    scene, cam, lights, r, o = _pair(scene_fn, w, h, st, threads=0)
-    if variant == "wavefront":
-        r.set_wavefront(True)
+    scene, cam, lights, r, o = pair(scene_fn, w, h, st, threads=0, wavefront=variant == "wavefront")
     s = st.to_c()
     sw, sh, _ = r.output_info(4)
     assert (sw, sh) != (w, h) and (w % sw or h % sh)  # the integrator grid is smaller and no divisor of S
@@ -94,10 +74,9 @@ def test_fractional_upscale_ratio_bit_exact(hk_options, case):
     for f in range(6):
         fi = frame_inputs(f, cam, lights, w, h)
         for x in (r, o):
-            _passes(x, s, fi, post=True)
-        _compare_sizes(r, o)
-        _compare_frame(r, o, f, errors)
-        _compare_post(r, o, f, errors)
+            passes(x, s, fi, post=True)
+        _check_sizes(r, o)
+        compare_frame(r, o, f, errors, outputs=WITH_POST)
         if errors:
             break
     assert not errors, "\n".join(errors[:20])
@@ -112,18 +91,18 @@ def test_fractional_ratio_moving_camera():
     from hikari_amd import HikariSettings, Upscale, frame_inputs
     w, h = 63, 47
     st = HikariSettings(upscale=Upscale.smaa_tu4x(1.5), indirect_spatial_reuse=False, denoise=True)
-    scene, cam, lights, r, o = _pair("cornell", w, h, st, threads=1)
+    scene, cam, lights, r, o = pair("cornell", w, h, st, threads=1)
     s = st.to_c()
     errors = []
     prev = None
     moved = 0
     for f in range(4):
-        c = _orbit(cam, f, angle_step=ic.ORBIT_2_DEGREES)
+        c = orbit_camera(cam, f, angle_step=ic.ORBIT_2_DEGREES)
         fi = frame_inputs(f, c, lights, w, h, previous_camera=prev)
         prev = copy.deepcopy(c)
         for x in (r, o):
-            _passes(x, s, fi)
-        _compare(r, o, f, errors)
+            passes(x, s, fi)
+        compare_frame(r, o, f, errors, racy=RACY)
         vel = r.output(15).view(np.float32).reshape(h, w, 4)[..., :2]
         moved += int((vel != 0).any(axis=-1).sum())
         if errors:
@@ -147,23 +126,9 @@ def test_edge_settings_bit_exact(hk_options, case, launch, scene_fn):
     reservoirs and counters.  The interval-0 and reuse-count-0 cases also with the fused and with the separate
     (4 waves per SIMD) direct / emissive launches forced, so the host's per-frame variant pick
     (validation_frame: interval 0 -> every frame validates) meets the kernels' `number % 0 == 0`."""
-    from hikari_amd import frame_inputs
     if launch is not None:
         hk_options.update(ic.EDGE_LAUNCH_OPTIONS[launch])
-    w, h = ic.EDGE_SIZE
-    st = ic.edge_settings(case)
-    scene, cam, lights, r, o = _pair(scene_fn, w, h, st, threads=0)
-    s = st.to_c()
-    errors = []
-    for f in range(ic.EDGE_FRAMES):
-        fi = frame_inputs(f, cam, lights, w, h)
-        for x in (r, o):
-            _passes(x, s, fi)
-        _compare_frame(r, o, f, errors)
-        if errors:
-            break
-    assert not errors, "\n".join(errors[:20])
-    assert r.counters() == o.counters()
+    run_static(scene_fn, *ic.EDGE_SIZE, ic.edge_settings(case), ic.EDGE_FRAMES, threads=0)
 
 
 @pytest.mark.parametrize("jitter", [0, 2], ids=["static", "taa_smaa_jitter"])
@@ -176,7 +141,7 @@ def test_orthographic_view_bit_exact(scene_fn, jitter):
     from hikari_amd import HikariSettings, Upscale, frame_inputs
     w, h = 64, 48
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, emissive_spatial_reuse=True, denoise=True)
-    scene, cam, lights, r, o = _pair(scene_fn, w, h, st, threads=0)
+    scene, cam, lights, r, o = pair(scene_fn, w, h, st, threads=0)
     cam = ic.orthographic_camera(scene_fn, cam)
     s = st.to_c()
     errors = []
@@ -185,9 +150,8 @@ def test_orthographic_view_bit_exact(scene_fn, jitter):
         fi = frame_inputs(f, cam, lights, w, h, jitter=jitter)
         assert fi.view.projection[15] == 1.0
         for x in (r, o):
-            _passes(x, s, fi, post=True)
-        _compare_frame(r, o, f, errors)
-        _compare_post(r, o, f, errors)
+            passes(x, s, fi, post=True)
+        compare_frame(r, o, f, errors, outputs=WITH_POST)
         positions.append(r.output(11).tobytes())
         if errors:
             break
@@ -205,18 +169,19 @@ def test_orthographic_view_bit_exact_orbiting():
     from hikari_amd import Camera, HikariSettings, Upscale, frame_inputs
     w, h = 64, 48
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=False, denoise=True)
-    scene, cam, lights, r, o = _pair("cornell", w, h, st, threads=1)
+    scene, cam, lights, r, o = pair("cornell", w, h, st, threads=1)
     s = st.to_c()
     errors = []
     prev = None
     moved = 0
     for f in range(3):
-        c = Camera.orthographic(_orbit(cam, f, angle_step=ic.ORBIT_2_DEGREES).transform, ic.ORTHO_HEIGHT["cornell"])
+        c = Camera.orthographic(orbit_camera(cam, f, angle_step=ic.ORBIT_2_DEGREES).transform,
+                                ic.ORTHO_HEIGHT["cornell"])
         fi = frame_inputs(f, c, lights, w, h, previous_camera=prev)
         prev = copy.deepcopy(c)
         for x in (r, o):
-            _passes(x, s, fi)
-        _compare(r, o, f, errors, racy=RACY)
+            passes(x, s, fi)
+        compare_frame(r, o, f, errors, racy=RACY)
         vel = r.output(15).view(np.float32).reshape(h, w, 4)[..., :2]
         moved += int((vel != 0).any(axis=-1).sum())
         if errors:

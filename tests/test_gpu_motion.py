@@ -17,55 +17,10 @@ import copy
 import numpy as np
 import pytest
 
-from parity import canon_plane, canon_reservoirs, mismatch_report
+from parity import (RACY, canon_plane, canon_reservoirs, compare_frame, mismatch_report, orbit_camera, pair, passes,
+                    plane_agreement, renderer, run_static)
 
 pytestmark = pytest.mark.gpu
-
-RACY = (4, 5, 8, 9)  # previous-spatial scatter targets (light.wgsl:1092-1095)
-RACY_MIN_EXACT = 0.97
-
-
-def _pair(scene_fn, w, h, settings, threads=1):
-    from hikari_amd import HikariRenderer, examples, load_noise
-    from oracle import Oracle
-    scene, cam, lights = examples.SCENES[scene_fn]()
-    desc = scene.build()
-    r = HikariRenderer(0)
-    r.set_noise()
-    r.upload_scene(scene)
-    r.resize(w, h, settings.upscale.ratio())
-    o = Oracle(desc, load_noise(), w, h, settings.upscale.ratio(), threads=threads, textures=scene.textures)
-    return scene, cam, lights, r, o
-
-
-def _compare(r, o, frame, errors, outputs=range(0, 17), stats=None, racy=RACY, rids=range(10)):
-    for oid in outputs:
-        m = mismatch_report(canon_plane(oid, r.output(oid)), canon_plane(oid, o.output(oid)), f"frame {frame} output {oid}")
-        if m:
-            errors.append(m)
-    for rid in rids:
-        g = canon_reservoirs(r.reservoirs(rid))
-        c = canon_reservoirs(o.reservoirs(rid)[: len(g)])
-        if rid in racy:
-            exact = float((g == c).all(axis=1).mean())
-            if stats is not None:
-                stats.append((frame, rid, exact))
-            if exact < RACY_MIN_EXACT:
-                errors.append(f"frame {frame} reservoir {rid}: only {exact:.4f} of records exact")
-        else:
-            m = mismatch_report(g, c, f"frame {frame} reservoir {rid}")
-            if m:
-                errors.append(m)
-
-
-def _orbit(cam, f, radius_step=0.05, angle_step=0.04):
-    """The camera moved along an orbit around the Cornell box's centre: frame f's camera."""
-    from hikari_amd import Camera, Transform
-    t = cam.transform.translation
-    a = angle_step * f
-    c, s = np.cos(a), np.sin(a)
-    eye = (float(c * t[0] + s * t[2]), float(t[1] + 0.02 * f), float(-s * t[0] + c * t[2]) + radius_step * f)
-    return Camera(Transform.from_xyz(*eye).looking_at((0.0, 1.0, 0.0)))
 
 
 @pytest.mark.parametrize("size", [(64, 64), (96, 72)])
@@ -76,21 +31,18 @@ def test_moving_camera_bit_exact(size):
     from hikari_amd import HikariSettings, Upscale, frame_inputs
     w, h = size
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=False, denoise=True)
-    scene, cam, lights, r, o = _pair("cornell", w, h, st)
+    scene, cam, lights, r, o = pair("cornell", w, h, st, threads=1)
     s = st.to_c()
     errors, stats = [], []
     prev = None
     moved = 0
     for f in range(7):
-        c = _orbit(cam, f)
+        c = orbit_camera(cam, f)
         fi = frame_inputs(f, c, lights, w, h, previous_camera=prev)
         prev = copy.deepcopy(c)
         for x in (r, o):
-            x.render_gbuffer(fi)
-            x.render_frame(s, fi)
-            x.denoise(s, fi)
-            x.tone_sum(s)
-        _compare(r, o, f, errors, stats=stats)
+            passes(x, s, fi)
+        compare_frame(r, o, f, errors, racy=RACY, stats=stats)
         vel = r.output(15).view(np.float32).reshape(h, w, 4)[..., :2]
         moved += int((vel != 0).any(axis=-1).sum())
         if errors:
@@ -110,7 +62,7 @@ def test_moving_camera_1080p_bit_exact():
     from hikari_amd import HikariSettings, Taa, Upscale, examples, frame_inputs
     w, h = 1920, 1080
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, taa=Taa.None_, indirect_spatial_reuse=False, denoise=False)
-    scene, cam, lights, r, o = _pair("cornell", w, h, st)
+    scene, cam, lights, r, o = pair("cornell", w, h, st, threads=1)
     s = st.to_c()
     target = examples.ORBIT_TARGETS["cornell"]
     errors, stats = [], []
@@ -122,7 +74,7 @@ def test_moving_camera_1080p_bit_exact():
             x.render_gbuffer(fi)
             x.render_frame(s, fi)
             x.tone_sum(s)
-        _compare(r, o, f, errors, outputs=(0, 1, 2, 3, 4, 5, 6, 10, 11, 12, 13, 14, 15), stats=stats)
+        compare_frame(r, o, f, errors, outputs=(0, 1, 2, 3, 4, 5, 6, 10, 11, 12, 13, 14, 15), racy=RACY, stats=stats)
         vel = r.output(15).view(np.float32).reshape(h, w, 4)[..., :2]
         moved += int((vel != 0).any(axis=-1).sum())
         if errors:
@@ -141,28 +93,21 @@ def test_moving_camera_spatial_reuse_within_tolerance():
     from hikari_amd import HikariSettings, Upscale, frame_inputs
     w, h = 64, 64
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=True, denoise=True)
-    scene, cam, lights, r, o = _pair("cornell", w, h, st)
+    scene, cam, lights, r, o = pair("cornell", w, h, st, threads=1)
     s = st.to_c()
     errors = []
     prev = None
     for f in range(6):
-        c = _orbit(cam, f)
+        c = orbit_camera(cam, f)
         fi = frame_inputs(f, c, lights, w, h, previous_camera=prev)
         prev = copy.deepcopy(c)
         for x in (r, o):
-            x.render_gbuffer(fi)
-            x.render_frame(s, fi)
-            x.denoise(s, fi)
-            x.tone_sum(s)
+            passes(x, s, fi)
         # exact: albedo, direct/emissive variance + render, G-buffer planes
-        _compare(r, o, f, errors, outputs=(0, 1, 2, 4, 5, 11, 12, 13, 14, 15), stats=[])
+        compare_frame(r, o, f, errors, outputs=(0, 1, 2, 4, 5, 11, 12, 13, 14, 15), racy=RACY)
         for oid in (6, 9, 10):  # indirect render (spatial output), denoised indirect, tone-mapped
-            a = canon_plane(oid, r.output(oid)).reshape(h, w, 4)
-            b = canon_plane(oid, o.output(oid)).reshape(h, w, 4)
-            exact = float((a == b).all(axis=-1).mean())
-            fa = a.view(np.float16).astype(np.float32)[..., :3]
-            fb = b.view(np.float16).astype(np.float32)[..., :3]
-            rel = float(np.abs(fa - fb).sum() / max(np.abs(fb).sum(), 1e-6))
+            exact, rel = plane_agreement(canon_plane(oid, r.output(oid)).reshape(h, w, 4),
+                                         canon_plane(oid, o.output(oid)).reshape(h, w, 4))
             if exact < 0.95 or rel > 0.02:
                 errors.append(f"frame {f} output {oid}: {exact:.4f} of pixels exact, mean relative difference {rel:.4f}")
         if errors:
@@ -187,7 +132,7 @@ def test_moving_instances_bit_exact(scene_fn):
     from hikari_amd import Camera, HikariSettings, Transform, Upscale, frame_inputs
     w, h = 64, 48
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=False, denoise=True)
-    scene, cam, lights, r, o = _pair(scene_fn, w, h, st)
+    scene, cam, lights, r, o = pair(scene_fn, w, h, st, threads=1)
     if scene_fn == "city":
         k = [i for i, (m, _, _) in enumerate(scene.instances) if len(scene.meshes[m].positions) == 37 * 19][-1]
         cam = Camera(Transform.from_xyz(0.6, 1.4, 2.2).looking_at((0.0, 1.0, 0.0)))
@@ -207,11 +152,8 @@ def test_moving_instances_bit_exact(scene_fn):
             o.set_scene(desc)
         fi = frame_inputs(f, cam, lights, w, h)
         for x in (r, o):
-            x.render_gbuffer(fi)
-            x.render_frame(s, fi)
-            x.denoise(s, fi)
-            x.tone_sum(s)
-        _compare(r, o, f, errors)
+            passes(x, s, fi)
+        compare_frame(r, o, f, errors, racy=RACY)
         vel = r.output(15).view(np.float32).reshape(h, w, 4)[..., :2]
         ids = r.output(14).view(np.float32).reshape(h, w, 2)[..., 0]
         moving = (vel != 0).any(axis=-1)
@@ -232,18 +174,15 @@ def test_taa_jitter_bit_exact(jitter):
     from hikari_amd import HikariSettings, Upscale, frame_inputs
     w, h = 64, 48
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=True, denoise=True)
-    scene, cam, lights, r, o = _pair("cornell", w, h, st, threads=0)
+    scene, cam, lights, r, o = pair("cornell", w, h, st, threads=0)
     s = st.to_c()
     errors = []
     positions = []
     for f in range(6):
         fi = frame_inputs(f, cam, lights, w, h, jitter=jitter)
         for x in (r, o):
-            x.render_gbuffer(fi)
-            x.render_frame(s, fi)
-            x.denoise(s, fi)
-            x.tone_sum(s)
-        _compare(r, o, f, errors, racy=())
+            passes(x, s, fi)
+        compare_frame(r, o, f, errors)
         vel = r.output(15).view(np.float32).reshape(h, w, 4)[..., :2]
         assert (vel == 0).all()
         positions.append(r.output(11).tobytes())
@@ -258,19 +197,16 @@ def test_host_gbuffer_planes_bit_exact():
     over with hk_set_gbuffer_plane (here: another context's k_gbuffer output of a moving camera),
     full_screen_albedo as its own pass (k_albedo), separate direct / emissive launches; every
     plane bit-exact against the oracle."""
-    from hikari_amd import HikariRenderer, HikariSettings, Upscale, frame_inputs
+    from hikari_amd import HikariSettings, Upscale, frame_inputs
     w, h = 64, 48
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=False, denoise=True)
-    scene, cam, lights, src, o = _pair("cornell", w, h, st)
-    r = HikariRenderer(0)
-    r.set_noise()
-    r.upload_scene(scene)
-    r.resize(w, h, 1.0)
+    scene, cam, lights, src, o = pair("cornell", w, h, st, threads=1)
+    r = renderer(scene, (w, h))
     s = st.to_c()
     errors = []
     prev = None
     for f in range(5):
-        c = _orbit(cam, f)
+        c = orbit_camera(cam, f)
         fi = frame_inputs(f, c, lights, w, h, previous_camera=prev)
         prev = copy.deepcopy(c)
         src.render_gbuffer(fi)
@@ -281,7 +217,7 @@ def test_host_gbuffer_planes_bit_exact():
             x.render_frame(s, fi)
             x.denoise(s, fi)
             x.tone_sum(s)
-        _compare(r, o, f, errors)
+        compare_frame(r, o, f, errors, racy=RACY)
         if errors:
             break
     assert not errors, "\n".join(errors[:20])
@@ -298,31 +234,16 @@ def test_forced_kernel_variants_bit_exact(hk_options, lds):
     merged direct+indirect launch (k_light_merged, merge=1: the default only for small frames without
     spatial reuse; here with spatial reuse after it) and the persistent-wave indirect pass
     (k_indirect_persist, persistent_indirect=1, an opt-in), each with and without LDS scene staging."""
-    from hikari_amd import HikariSettings, Upscale, frame_inputs
+    from hikari_amd import HikariSettings, Upscale
     hk_options["lds_scene"] = int(lds)
-    w, h = 64, 48
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0)
-    s = st.to_c()
     for env in ({"direct_w4_min_px": 0, "fuse": 0}, {"fuse": 0}, {"fuse_min_px": 0, "merge": 0},
                 {"fuse_min_px": 0, "merge": 0, "compact_emitter": 1},
                 {"fuse_min_px": 0, "merge": 0, "compact_shadow": 1},
                 {"merge": 1}, {"persistent_indirect": 1, "merge": 0}):
         hk_options.clear()
         hk_options.update(lds_scene=int(lds), **env)
-        scene, cam, lights, r, o = _pair("cornell", w, h, st, threads=0)
-        errors = []
-        for f in range(6):
-            fi = frame_inputs(f, cam, lights, w, h)
-            for x in (r, o):
-                x.render_gbuffer(fi)
-                x.render_frame(s, fi)
-                x.denoise(s, fi)
-                x.tone_sum(s)
-            _compare(r, o, f, errors, racy=())
-            if errors:
-                break
-        assert not errors, f"{env}: " + "\n".join(errors[:20])
-        assert r.counters() == o.counters()
+        run_static("cornell", 64, 48, st, 6, threads=0, label=f"{env}: ")
 
 
 @pytest.mark.parametrize("launch", ["fused", "separate"])
@@ -343,12 +264,12 @@ def test_background_elision_bit_exact(hk_options, launch):
         hk_options["direct_w4_min_px"] = 0
     w, h = 64, 48
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=False, denoise=True)
-    scene, cam, lights, r, o = _pair("cornell", w, h, st)
+    scene, cam, lights, r, o = pair("cornell", w, h, st, threads=1)
     s = st.to_c()
     errors = []
     prev = None
     for f in range(12):
-        c = _orbit(cam, min(max(f - 3, 0), 2))  # frames 4, 5 move; 0-3 and 6-11 are static
+        c = orbit_camera(cam, min(max(f - 3, 0), 2))  # frames 4, 5 move; 0-3 and 6-11 are static
         fi = frame_inputs(f, c, lights, w, h, previous_camera=prev)
         prev = copy.deepcopy(c)
         if f == 11:
@@ -360,16 +281,13 @@ def test_background_elision_bit_exact(hk_options, launch):
             for rid in RACY:
                 r.load_reservoirs(rid, np.frombuffer(rng.bytes(w * h * RESERVOIR_DTYPE.itemsize), RESERVOIR_DTYPE))
         for x in (r, o):
-            x.render_gbuffer(fi)
-            x.render_frame(s, fi)
-            x.denoise(s, fi)
-            x.tone_sum(s)
+            passes(x, s, fi)
         if f < 11:
             # frames 4-5 move: their spatial-pair scatter is racy (light.wgsl:1092-1095), and
             # with spatial reuse off nothing reads those records afterwards
-            _compare(r, o, f, errors, racy=RACY if f >= 4 else ())
+            compare_frame(r, o, f, errors, racy=RACY if f >= 4 else ())
         else:
-            _compare(r, o, f, errors, racy=(), rids=[k for k in range(10) if k not in RACY])
+            compare_frame(r, o, f, errors, rids=[k for k in range(10) if k not in RACY])
             depth = r.output(11).view(np.float32).reshape(h * w, 4)[:, 3]
             bg = depth < np.finfo(np.float32).eps
             assert bg.sum() > 0
@@ -398,7 +316,7 @@ def test_background_elision_spatial_pairs_bit_exact(hk_options, jitter):
     w, h = 64, 48
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, emissive_spatial_reuse=True, indirect_spatial_reuse=True,
                         denoise=True)
-    scene, cam, lights, r, o = _pair("cornell", w, h, st, threads=0)
+    scene, cam, lights, r, o = pair("cornell", w, h, st, threads=0)
     s = st.to_c()
     errors = []
     rng = np.random.default_rng(9)
@@ -410,11 +328,8 @@ def test_background_elision_spatial_pairs_bit_exact(hk_options, jitter):
                 o.load_reservoirs(rid, garbage)
         fi = frame_inputs(f, cam, lights, w, h, jitter=jitter)
         for x in (r, o):
-            x.render_gbuffer(fi)
-            x.render_frame(s, fi)
-            x.denoise(s, fi)
-            x.tone_sum(s)
-        _compare(r, o, f, errors, racy=())
+            passes(x, s, fi)
+        compare_frame(r, o, f, errors)
         if errors:
             break
     assert not errors, "\n".join(errors[:20])

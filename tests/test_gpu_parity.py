@@ -7,41 +7,10 @@ Scenes: cornell (examples/cornell.rs) at small sizes; frames 0..N so that valida
 import numpy as np
 import pytest
 
-from parity import canon_plane, canon_reservoirs, mismatch_report
+from parity import (RACY, assert_instance_update_matches_host, canon_plane, compare_frame, core_agreement, decomposed,
+                    hip_runtime, mismatch_report, moved, pair, passes, renderer, run_frames, run_static, summed_counters)
 
 pytestmark = pytest.mark.gpu
-
-OUTPUTS = list(range(0, 17))
-
-
-def _setup(width, height, settings, scene_fn="cornell"):
-    from hikari_amd import HikariRenderer, examples, load_noise
-    from oracle import Oracle
-    scene, cam, lights = examples.SCENES[scene_fn]()
-    desc = scene.build()
-    r = HikariRenderer(0)
-    r.set_noise()
-    r.upload_scene(scene)
-    r.resize(width, height, settings.upscale.ratio())
-    o = Oracle(desc, load_noise(), width, height, settings.upscale.ratio(), textures=scene.textures)
-    return scene, cam, lights, r, o
-
-
-def _compare_frame(r, o, frame, errors):
-    for oid in OUTPUTS:
-        a = canon_plane(oid, r.output(oid))
-        b = canon_plane(oid, o.output(oid))
-        m = mismatch_report(a, b, f"frame {frame} output {oid}")
-        if m:
-            errors.append(m)
-    for rid in range(10):
-        # the reference allocates S.x*S.y records but indexes them with the s stride
-        # (light.rs:344,352 vs light.wgsl:1061): compare the indexed prefix
-        g = r.reservoirs(rid)
-        m = mismatch_report(canon_reservoirs(g), canon_reservoirs(o.reservoirs(rid)[: len(g)]),
-                            f"frame {frame} reservoir {rid}")
-        if m:
-            errors.append(m)
 
 
 @pytest.fixture(params=["1", "0", "2"], ids=["lds_default", "lds_off", "lds_all"])
@@ -56,27 +25,8 @@ def test_cornell_frames_bit_exact(size, lds_mode):
     """(256, 256): BASELINE configs[0] (examples/cornell.rs 256x256, all passes incl. spatial reuse
     and the denoiser).  (63, 47): odd sizes — partial 16x16 tiles on both edges, and the tone pass's
     tile kernel (k_tone; even widths take the 2-pixel-run kernel)."""
-    from hikari_amd import HikariSettings, Upscale, frame_inputs
-    w, h = size
-    st = HikariSettings(upscale=Upscale.SMAA_TU_1_0)
-    scene, cam, lights, r, o = _setup(w, h, st)
-    s = st.to_c()
-    errors = []
-    for f in range(7):
-        fi = frame_inputs(f, cam, lights, w, h)
-        r.render_gbuffer(fi)
-        o.render_gbuffer(fi)
-        r.render_frame(s, fi)
-        o.render_frame(s, fi)
-        r.denoise(s, fi)
-        o.denoise(s, fi)
-        r.tone_sum(s)
-        o.tone_sum(s)
-        _compare_frame(r, o, f, errors)
-        if errors:
-            break
-    assert not errors, "\n".join(errors[:20])
-    assert r.counters() == o.counters()
+    from hikari_amd import HikariSettings, Upscale
+    run_static("cornell", size[0], size[1], HikariSettings(upscale=Upscale.SMAA_TU_1_0), 7)
 
 
 # uneven 8-band split of city 3840x2160 (cost-balanced bands as bench.py's calibration produces them:
@@ -95,36 +45,24 @@ def test_full_size_bench_workloads_bit_exact(config, frames, uneven):
     equal bands and with uneven (cost-balanced) ones, and the 8-tile one (4 row bands x 2 column bands of
     1920 x 540, hk_resize_tile: each tile's core rectangle, and the tiles' ray counts summing to the frame's)."""
     import bench
-    from hikari_amd import HikariRenderer, HikariSettings, Upscale, frame_inputs
-    from hikari_amd.bands import band_of, halo_rows, tile_of
+    from hikari_amd import HikariSettings, Upscale, frame_inputs
+    from hikari_amd.bands import halo_rows
     cfg = bench.CONFIGS[config]
     w, h = cfg["width"], cfg["height"]
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=cfg["spatial"], denoise=cfg["denoise"])
-    scene, cam, lights, r, o = _setup(w, h, st, cfg["scene"])
+    scene, cam, lights, r, o = pair(cfg["scene"], w, h, st)
     s = st.to_c()
     # city 4K: also BASELINE configs[3]'s own decomposition, 8 row bands of 270 rows + halo (one context
     # per band, as the 8 ranks of bench.py --gpus 8 hold them), core rows against the whole-frame oracle
     bands = []
     if config == "city-4k":
-        for k in range(8):
-            b = tile_of(k, 8, w, h) if uneven == "tiles" else band_of(k, 8, h, CITY_UNEVEN if uneven else None)
-            rb = HikariRenderer(0)
-            rb.set_noise()
-            rb.upload_scene(scene)
-            rb.set_band_halo(halo_rows(cfg["spatial"], cfg["denoise"]))
-            if uneven == "tiles":
-                rb.resize_tile(w, h, b.x0, b.cols, b.y0, b.rows)
-            else:
-                rb.resize(w, h, 1.0, b.y0, b.rows)
-            bands.append((b, rb))
+        bands = decomposed(scene, 8, w, h, "tiles" if uneven == "tiles" else "bands",
+                           halo_rows(cfg["spatial"], cfg["denoise"]), CITY_UNEVEN if uneven is True else None)
     errors = []
     for f in range(frames):
         fi = frame_inputs(f, cam, lights, w, h)
         for x in [r, o] + [rb for _, rb in bands]:
-            x.render_gbuffer(fi)
-            x.render_frame(s, fi)
-            x.denoise(s, fi)
-            x.tone_sum(s)
+            passes(x, s, fi)
         whole = canon_plane(10, o.output(10))
         for b, rb in bands:
             row0, rows, core0, core_rows = rb.band_info()
@@ -140,22 +78,14 @@ def test_full_size_bench_workloads_bit_exact(config, frames, uneven):
             m = mismatch_report(mine, ref, f"frame {f} band {b.y0}+{b.rows} output 10")
             if m:
                 errors.append(m)
-        for oid in OUTPUTS:
-            m = mismatch_report(canon_plane(oid, r.output(oid)), canon_plane(oid, o.output(oid)), f"frame {f} output {oid}")
-            if m:
-                errors.append(m)
+        compare_frame(r, o, f, errors, rids=())
         if errors:
             break
-    for rid in range(10):
-        g = r.reservoirs(rid)
-        m = mismatch_report(canon_reservoirs(g), canon_reservoirs(o.reservoirs(rid)[: len(g)]), f"reservoir {rid}")
-        if m:
-            errors.append(m)
+    compare_frame(r, o, "last", errors, outputs=())  # the reservoir buffers after the last frame only
     assert not errors, "\n".join(errors[:20])
     assert r.counters() == o.counters()
     if uneven == "tiles":  # the tiles count their own pixels' rays: together the frames' rays, once each
-        total = {k: sum(rb.counters()[k] for _, rb in bands) for k in ("traverse_top", "traverse_emitter", "primary")}
-        assert total == o.counters(), (total, o.counters())
+        assert summed_counters(bands) == o.counters()
 
 
 @pytest.mark.parametrize("denoise,mode", [(True, "forced"), (False, "forced"), (True, "serial")],
@@ -174,19 +104,16 @@ def test_frame_pipelining_bit_exact(hk_options, denoise, mode):
         hk_options["pipeline_heavy_min_px"] = 1e12
     w, h = 96, 72
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=True, denoise=denoise)
-    scene, cam, lights, r, o = _setup(w, h, st)
+    scene, cam, lights, r, o = pair("cornell", w, h, st)
     s = st.to_c()
     errors = []
     frames = 9
     for f in range(frames):
         fi = frame_inputs(f, cam, lights, w, h)
         for x in (r, o):
-            x.render_gbuffer(fi)
-            x.render_frame(s, fi)
-            x.denoise(s, fi)
-            x.tone_sum(s)
+            passes(x, s, fi)
         if f < 3 or f == frames - 1:  # frames 3..7 run back to back, no readback in between
-            _compare_frame(r, o, f, errors)
+            compare_frame(r, o, f, errors)
         if errors:
             break
     assert not errors, "\n".join(errors[:20])
@@ -202,18 +129,15 @@ def test_heavy_frame_schedule_switches_bit_exact(hk_options):
     w, h = 96, 72
     heavy = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=True, denoise=True)
     light = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=False, denoise=False)
-    scene, cam, lights, r, o = _setup(w, h, heavy)
+    scene, cam, lights, r, o = pair("cornell", w, h, heavy)
     errors = []
     for f, st in enumerate([heavy, heavy, light, light, heavy, light, heavy, heavy]):
         s = st.to_c()
         fi = frame_inputs(f, cam, lights, w, h)
         for x in (r, o):
-            x.render_gbuffer(fi)
-            x.render_frame(s, fi)
-            x.denoise(s, fi)
-            x.tone_sum(s)
+            passes(x, s, fi)
         if f % 2 == 1 or f == 7:
-            _compare_frame(r, o, f, errors)
+            compare_frame(r, o, f, errors)
         if errors:
             break
     assert not errors, "\n".join(errors[:20])
@@ -229,27 +153,17 @@ def test_device_pointer_after_sync_is_current(hk_options):
 
     from hikari_amd import HikariSettings, Upscale, frame_inputs
     hk_options["pipeline_min_px"] = 0
-    # the HIP runtime libhikari_amd.so itself uses (torch may bring a second copy into the process)
-    maps = [ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln]
-    path = next((m for m in maps if m.startswith("/opt/rocm")), maps[0] if maps else "libamdhip64.so")
-    hip = ctypes.CDLL(path)
-    hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
-    hip.hipStreamSynchronize.argtypes = [ctypes.c_void_p]
-    hip.hipStreamCreate.argtypes = [ctypes.POINTER(ctypes.c_void_p)]
-    hip.hipStreamDestroy.argtypes = [ctypes.c_void_p]
+    hip = hip_runtime()
     w, h = 96, 72
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=True, denoise=True)
-    scene, cam, lights, r, o = _setup(w, h, st)
+    scene, cam, lights, r, o = pair("cornell", w, h, st)
     s = st.to_c()
     stream = ctypes.c_void_p()
     assert hip.hipStreamCreate(ctypes.byref(stream)) == 0  # the reader's own stream
     for f in range(6):
         fi = frame_inputs(f, cam, lights, w, h)
         for x in (r, o):
-            x.render_gbuffer(fi)
-            x.render_frame(s, fi)
-            x.denoise(s, fi)
-            x.tone_sum(s)
+            passes(x, s, fi)
         r.sync(stream)
         for oid in (10, 7, 8, 9, 11, 15):  # tone-mapped, denoised x3, G-buffer position, velocity
             cw, ch, b = r.output_info(oid)
@@ -266,31 +180,15 @@ def test_device_pointer_after_sync_is_current(hk_options):
 def test_fallback_paths_bit_exact(hk_options):
     """The paths the defaults switch off stay exact: one stream (no channel fork), walk nodes
     without leaf collapse, the G-buffer stack with its scratch overflow levels."""
-    from hikari_amd import HikariSettings, Upscale, frame_inputs
+    from hikari_amd import HikariSettings, Upscale
     hk_options.update(channel_streams=0, leaf_collapse=0, gbuffer_deep=1)
-    w, h = 64, 48
-    st = HikariSettings(upscale=Upscale.SMAA_TU_1_0)
-    scene, cam, lights, r, o = _setup(w, h, st)
-    s = st.to_c()
-    errors = []
-    for f in range(4):
-        fi = frame_inputs(f, cam, lights, w, h)
-        for x in (r, o):
-            x.render_gbuffer(fi)
-            x.render_frame(s, fi)
-            x.denoise(s, fi)
-            x.tone_sum(s)
-        _compare_frame(r, o, f, errors)
-        if errors:
-            break
-    assert not errors, "\n".join(errors[:20])
-    assert r.counters() == o.counters()
+    run_static("cornell", 64, 48, HikariSettings(upscale=Upscale.SMAA_TU_1_0), 4)
 
 
 def test_trace_matches_oracle():
     from hikari_amd import HikariSettings, Upscale
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0)
-    scene, cam, lights, r, o = _setup(16, 16, st)
+    scene, cam, lights, r, o = pair("cornell", 16, 16, st)
     rng = np.random.default_rng(7)
     n = 20000
     org = rng.uniform([-1.2, -0.2, -1.2], [1.2, 2.2, 1.2], (n, 3))
@@ -316,8 +214,8 @@ def test_gpu_row_bands_match_whole_frame(spatial, denoise, world, H):
     passes on core +-36, spatial reuse +-16, demodulation +-15, the a-trous levels +-7/3/1/0) are
     strict parts of the frame, over 5 frames of reservoir history.  spatial = "indirect": indirect
     spatial reuse alone (the bench configs), where the direct / emissive launch runs on core +-16 only."""
-    from hikari_amd import HikariRenderer, HikariSettings, Upscale, examples, frame_inputs, load_noise
-    from hikari_amd.bands import band_of, halo_rows
+    from hikari_amd import HikariSettings, Upscale, examples, frame_inputs, load_noise
+    from hikari_amd.bands import halo_rows
     from oracle import Oracle
     W = 64
     scene, cam, lights = examples.cornell()
@@ -326,36 +224,18 @@ def test_gpu_row_bands_match_whole_frame(spatial, denoise, world, H):
                         emissive_spatial_reuse=spatial is True, denoise=denoise)
     s = st.to_c()
     o = Oracle(desc, load_noise(), W, H, 1.0)
-    ranks = []
-    for k in range(world):
-        b = band_of(k, world, H)
-        r = HikariRenderer(0)
-        r.set_noise()
-        r.upload_scene(scene)
-        r.set_band_halo(halo_rows(bool(spatial), denoise))
-        r.resize(W, H, 1.0, b.y0, b.rows)
-        ranks.append((b, r))
+    ranks = decomposed(scene, world, W, H, "bands", halo_rows(bool(spatial), denoise))
     for f in range(5):
         fi = frame_inputs(f, cam, lights, W, H)
-        o.render_gbuffer(fi)
-        o.render_frame(s, fi)
-        o.denoise(s, fi)
-        o.tone_sum(s)
-        for b, r in ranks:
-            r.render_gbuffer(fi)
-            r.render_frame(s, fi)
-            r.denoise(s, fi)
-            r.tone_sum(s)
+        for x in [o] + [r for _, r in ranks]:
+            passes(x, s, fi)
     whole = o.output(10)
-    total = {"traverse_top": 0, "traverse_emitter": 0, "primary": 0}
     for b, r in ranks:
         row0, rows, core0, core_rows = r.band_info()
         assert row0 + core0 == b.y0 and core_rows == b.rows
         mine = r.output(10)[core0: core0 + core_rows]
         assert np.array_equal(canon_plane(10, mine), canon_plane(10, whole[b.y0: b.y0 + b.rows])), b
-        for k, v in r.counters().items():
-            total[k] += v
-    assert total == o.counters()
+    assert summed_counters(ranks) == o.counters()
 
 
 @pytest.mark.parametrize("refill", [True, False], ids=["refill", "zero_fill"])
@@ -368,8 +248,8 @@ def test_gpu_row_bands_settings_toggle(refill):
     Without the refill (zero_fill) hk_render_frame zero-fills the new rows (hk_resize's state): exact before the first
     widening; afterwards the new rows' ReSTIR chains restart and the denoiser spreads the difference over the core rows
     (measured 47-78 % of pixels exact, mean relative difference <= 5.5e-3: profiles/r06/c2), held to <= 1e-2."""
-    from hikari_amd import HikariRenderer, HikariSettings, Upscale, examples, frame_inputs, load_noise
-    from hikari_amd.bands import band_of, halo_rows, refill_windows_local
+    from hikari_amd import HikariSettings, Upscale, examples, frame_inputs, load_noise
+    from hikari_amd.bands import halo_rows, refill_windows_local
     from oracle import Oracle
     W, H, world = 64, 192, 3
     scene, cam, lights = examples.cornell()
@@ -381,24 +261,13 @@ def test_gpu_row_bands_settings_toggle(refill):
     # (emissive spatial reuse, denoise) per frame: denoise on at 4, emissive spatial reuse on at 6, off at 8, on at 9
     plan = [(False, False)] * 4 + [(False, True)] * 2 + [(True, True)] * 2 + [(False, True), (True, True), (True, True)]
     o = Oracle(desc, load_noise(), W, H, 1.0)
-    ranks = []
-    for k in range(world):
-        b = band_of(k, world, H)
-        r = HikariRenderer(0)
-        r.set_noise()
-        r.upload_scene(scene)
-        r.set_band_halo(halo_rows(True, True))
-        r.resize(W, H, 1.0, b.y0, b.rows)
-        ranks.append((b, r))
+    ranks = decomposed(scene, world, W, H, "bands", halo_rows(True, True))
     errors, worst, moved = [], [], []
     previous = None
     for f, (emissive, denoise) in enumerate(plan):
         s = settings(emissive, denoise)
         fi = frame_inputs(f, cam, lights, W, H)
-        o.render_gbuffer(fi)
-        o.render_frame(s, fi)
-        o.denoise(s, fi)
-        o.tone_sum(s)
+        passes(o, s, fi)
         for _, r in ranks:
             r.render_gbuffer(fi)
         if refill and (emissive, denoise) != previous:
@@ -410,17 +279,11 @@ def test_gpu_row_bands_settings_toggle(refill):
             r.tone_sum(s)
         whole = canon_plane(10, o.output(10)).reshape(H, W, 4)
         for b, r in ranks:
-            row0, rows, core0, core_rows = r.band_info()
-            a = canon_plane(10, r.output(10)[core0: core0 + core_rows]).reshape(core_rows, W, 4)
-            c = whole[b.y0: b.y0 + b.rows]
-            exact = float((a == c).all(axis=-1).mean())
-            fa = a.view(np.float16).astype(np.float32)[..., :3]
-            fc = c.view(np.float16).astype(np.float32)[..., :3]
-            rel = float(np.abs(fa - fc).sum() / max(np.abs(fc).sum(), 1e-6))
+            exact, rel = core_agreement(r, b, whole)
             worst.append((f, b.y0, round(exact, 4), round(rel, 5)))
             if (refill or f < 4) and exact < 1.0:
                 errors.append(f"frame {f} band {b.y0}: {exact:.4f} of pixels exact")
-            if not np.isfinite(fa).all() or rel > 0.01:
+            if not rel <= 0.01:  # (inf or NaN for a value that is not finite)
                 errors.append(f"frame {f} band {b.y0}: {exact:.4f} of pixels exact, mean relative difference {rel:.4f}")
     assert not errors, "\n".join(errors) + f"\n{worst}"
     if refill:
@@ -436,8 +299,8 @@ def test_gpu_tiles_match_whole_frame(world, spatial, denoise):
     whole-frame oracle render bit-exactly on their own rectangles over 5 frames, and their ray counters add up to the
     whole frame's (each pixel counted by the tile that owns it).  The tiles' rows + halo and columns + halo are strict
     parts of the frame, so every pass runs on a proper row and column window (pass_window)."""
-    from hikari_amd import HikariRenderer, HikariSettings, Upscale, examples, frame_inputs, load_noise
-    from hikari_amd.bands import halo_rows, tile_of
+    from hikari_amd import HikariSettings, Upscale, examples, frame_inputs, load_noise
+    from hikari_amd.bands import halo_rows
     from oracle import Oracle
     W, H = 128, 192
     scene, cam, lights = examples.cornell()
@@ -446,28 +309,14 @@ def test_gpu_tiles_match_whole_frame(world, spatial, denoise):
                         emissive_spatial_reuse=spatial is True, denoise=denoise)
     s = st.to_c()
     o = Oracle(desc, load_noise(), W, H, 1.0)
-    ranks = []
-    for k in range(world):
-        t = tile_of(k, world, W, H)
-        r = HikariRenderer(0)
-        r.set_noise()
-        r.upload_scene(scene)
-        r.set_band_halo(halo_rows(True, True))
-        r.resize_tile(W, H, t.x0, t.cols, t.y0, t.rows)
-        ranks.append((t, r))
+    ranks = decomposed(scene, world, W, H, "tiles", halo_rows(True, True))
     errors = []
     for f in range(5):
         fi = frame_inputs(f, cam, lights, W, H)
-        o.render_gbuffer(fi)
-        o.render_frame(s, fi)
-        o.denoise(s, fi)
-        o.tone_sum(s)
+        passes(o, s, fi)
         whole = o.output(10)
         for t, r in ranks:
-            r.render_gbuffer(fi)
-            r.render_frame(s, fi)
-            r.denoise(s, fi)
-            r.tone_sum(s)
+            passes(r, s, fi)
             row0, rows, core0, core_rows = r.band_info()
             assert row0 + core0 == t.y0 and core_rows == t.rows
             mine = np.ascontiguousarray(r.output(10)[core0: core0 + core_rows, t.x0: t.x0 + t.cols])
@@ -475,23 +324,17 @@ def test_gpu_tiles_match_whole_frame(world, spatial, denoise):
             if not np.array_equal(canon_plane(10, mine), canon_plane(10, ref)):
                 errors.append(f"frame {f} tile {t}")
     assert not errors, "\n".join(errors)
-    total = {"traverse_top": 0, "traverse_emitter": 0, "primary": 0}
-    for _, r in ranks:
-        for k, v in r.counters().items():
-            total[k] += v
-    assert total == o.counters()
+    assert summed_counters(ranks) == o.counters()
 
 
 def test_gpu_tile_rect_copy():
     """hk_copy_output_rect: a tile's core rectangle of the tone-mapped plane copied packed and into a pitched
     whole-frame buffer equals those pixels of hk_get_output."""
-    from hikari_amd import HikariRenderer, HikariSettings, Upscale, examples, frame_inputs
+    from hikari_amd import HikariSettings, Upscale, examples, frame_inputs
     W, H = 128, 96
     scene, cam, lights = examples.cornell()
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0).to_c()
-    r = HikariRenderer(0)
-    r.set_noise()
-    r.upload_scene(scene)
+    r = renderer(scene)
     r.set_band_halo(16)
     r.resize_tile(W, H, 64, 64, 48, 48)
     fi = frame_inputs(0, cam, lights, W, H)
@@ -518,8 +361,8 @@ def test_gpu_row_bands_moving_camera_within_tolerance():
     nature, so the tone-mapped core rows must match the whole-frame oracle on >= 95 % of
     pixels with a mean relative difference <= 2 %, over 5 frames with spatial reuse and the denoiser."""
     import math
-    from hikari_amd import HikariRenderer, HikariSettings, Upscale, examples, frame_inputs, load_noise
-    from hikari_amd.bands import band_of, halo_rows
+    from hikari_amd import HikariSettings, Upscale, examples, frame_inputs, load_noise
+    from hikari_amd.bands import halo_rows
     from oracle import Oracle
     W, H, world = 64, 192, 3
     scene, cam, lights = examples.cornell()
@@ -527,15 +370,7 @@ def test_gpu_row_bands_moving_camera_within_tolerance():
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=True, denoise=True)
     s = st.to_c()
     o = Oracle(desc, load_noise(), W, H, 1.0, threads=1)
-    ranks = []
-    for k in range(world):
-        b = band_of(k, world, H)
-        r = HikariRenderer(0)
-        r.set_noise()
-        r.upload_scene(scene)
-        r.set_band_halo(halo_rows(True, True))
-        r.resize(W, H, 1.0, b.y0, b.rows)
-        ranks.append((b, r))
+    ranks = decomposed(scene, world, W, H, "bands", halo_rows(True, True))
     target = examples.ORBIT_TARGETS["cornell"]
     yaw = math.radians(2.0)
     errors = []
@@ -543,19 +378,10 @@ def test_gpu_row_bands_moving_camera_within_tolerance():
         fi = frame_inputs(f, examples.orbit(cam, target, f, yaw), lights, W, H,
                           previous_camera=examples.orbit(cam, target, f - 1, yaw) if f else None)
         for x in [o] + [r for _, r in ranks]:
-            x.render_gbuffer(fi)
-            x.render_frame(s, fi)
-            x.denoise(s, fi)
-            x.tone_sum(s)
+            passes(x, s, fi)
         whole = canon_plane(10, o.output(10)).reshape(H, W, 4)
         for b, r in ranks:
-            row0, rows, core0, core_rows = r.band_info()
-            a = canon_plane(10, r.output(10)[core0: core0 + core_rows]).reshape(core_rows, W, 4)
-            c = whole[b.y0: b.y0 + b.rows]
-            exact = float((a == c).all(axis=-1).mean())
-            fa = a.view(np.float16).astype(np.float32)[..., :3]
-            fc = c.view(np.float16).astype(np.float32)[..., :3]
-            rel = float(np.abs(fa - fc).sum() / max(np.abs(fc).sum(), 1e-6))
+            exact, rel = core_agreement(r, b, whole)
             if exact < 0.95 or rel > 0.02:
                 errors.append(f"frame {f} band {b.y0}: {exact:.4f} of pixels exact, mean relative difference {rel:.4f}")
     assert not errors, "\n".join(errors)
@@ -566,7 +392,7 @@ def test_gpu_interleaved_stripes_match_whole_frame(world):
     """Interleaved 8-row stripe contexts (bench.py's decomposition for frames without neighbour
     reads, run on one GPU) reassemble the whole-frame oracle render bit-exactly, count exactly
     the whole frame's rays, and refuse the passes that read neighbours."""
-    from hikari_amd import HikariRenderer, HikariSettings, Upscale, examples, frame_inputs, load_noise
+    from hikari_amd import HikariSettings, Upscale, examples, frame_inputs, load_noise
     from hikari_amd._abi import HikariError
     from hikari_amd.bands import stripe_gather_rows
     from oracle import Oracle
@@ -576,50 +402,27 @@ def test_gpu_interleaved_stripes_match_whole_frame(world):
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=False, denoise=False)
     s = st.to_c()
     o = Oracle(desc, load_noise(), W, H, 1.0)
-    ranks = []
-    for k in range(world):
-        r = HikariRenderer(0)
-        r.set_noise()
-        r.upload_scene(scene)
-        r.resize_striped(W, H, k, world)
-        ranks.append(r)
+    ranks = decomposed(scene, world, W, H, "stripes")
     for f in range(5):
         fi = frame_inputs(f, cam, lights, W, H)
         o.render_gbuffer(fi)
         o.render_frame(s, fi)
         o.tone_sum(s)
-        for r in ranks:
-            r.render_gbuffer(fi)
-            r.render_frame(s, fi)
-            r.denoise(s, fi)  # denoise off: a no-op, allowed
-            r.tone_sum(s)
+        for _, r in ranks:
+            passes(r, s, fi)  # denoise off: a no-op, allowed
     pad, index = stripe_gather_rows(world, H)
     gathered = np.zeros((world * pad, W, 8), np.uint8)
-    total = {"traverse_top": 0, "traverse_emitter": 0, "primary": 0}
-    for k, r in enumerate(ranks):
+    for k, r in ranks:
         row0, rows, core0, core_rows = r.band_info()
         assert row0 == 0 and core0 == 0 and rows == core_rows
         gathered[k * pad: k * pad + rows] = r.output(10)
-        for name, v in r.counters().items():
-            total[name] += v
     assert np.array_equal(canon_plane(10, gathered[index]), canon_plane(10, o.output(10)))
-    assert total == o.counters()
+    assert summed_counters(ranks) == o.counters()
     spatial = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=True, denoise=True).to_c()
     with pytest.raises(HikariError):
-        ranks[0].render_frame(spatial, frame_inputs(5, cam, lights, W, H))
+        ranks[0][1].render_frame(spatial, frame_inputs(5, cam, lights, W, H))
     with pytest.raises(HikariError):
-        ranks[0].denoise(spatial, frame_inputs(5, cam, lights, W, H))
-
-
-def _gpu_factory(w, h, ratio=1.0):
-    def make(scene, desc):
-        from hikari_amd import HikariRenderer
-        r = HikariRenderer(0)
-        r.set_noise()
-        r.upload_scene(scene)
-        r.resize(w, h, ratio)
-        return r
-    return make
+        ranks[0][1].denoise(spatial, frame_inputs(5, cam, lights, W, H))
 
 
 @pytest.mark.parametrize("variant", ["default_ratio1", "emissive_spatial_multibounce", "no_temporal_no_spatial",
@@ -632,35 +435,10 @@ def test_gpu_matches_golden_digests(variant):
     import make_golden_path  # noqa: F401
     from make_golden import FRAMES, H, W, render
     gold = json.loads((Path(__file__).parent / "golden" / "cornell_golden.json").read_text())
-    frames, _ = render(_gpu_factory(W, H), variant)
+    frames, _ = render(lambda scene, desc: renderer(scene, (W, H)), variant)
     for f, (a, b) in enumerate(zip(frames, gold["variants"][variant]["digests"])):
         bad = [k for k in b if a[k] != b[k]]
         assert not bad, f"{variant} frame {f}: {bad}"
-
-
-def _run_pair(scene_fn, w, h, settings, frames):
-    from hikari_amd import HikariRenderer, examples, frame_inputs, load_noise
-    from oracle import Oracle
-    scene, cam, lights = examples.SCENES[scene_fn]()
-    desc = scene.build()
-    ratio = settings.upscale.ratio()
-    r = _gpu_factory(w, h, ratio)(scene, desc)
-    o = Oracle(desc, load_noise(), w, h, ratio, textures=scene.textures)
-    s = settings.to_c()
-    errors = []
-    for f in range(frames):
-        fi = frame_inputs(f, cam, lights, w, h)
-        for x in (r, o):
-            x.render_gbuffer(fi)
-            x.render_frame(s, fi)
-            x.denoise(s, fi)
-            x.tone_sum(s)
-        _compare_frame(r, o, f, errors)
-        if errors:
-            break
-    assert not errors, "\n".join(errors[:20])
-    assert r.counters() == o.counters()
-    return r, o
 
 
 @pytest.mark.parametrize("ratio_setting", ["SMAA_TU_1_0", "SMAA_TU_2_0"])
@@ -668,14 +446,14 @@ def test_textured_materials_bit_exact(ratio_setting):
     """Textured pipeline (light.wgsl:748-794): sRGB / linear textures, all address modes and
     filters, on base colour, emissive, metallic-roughness and occlusion slots."""
     from hikari_amd import HikariSettings, Upscale
-    _run_pair("cornell_textured", 64, 48, HikariSettings(upscale=getattr(Upscale, ratio_setting),
-                                                         emissive_spatial_reuse=True, indirect_bounces=2), 5)
+    run_static("cornell_textured", 64, 48, HikariSettings(upscale=getattr(Upscale, ratio_setting),
+                                                          emissive_spatial_reuse=True, indirect_bounces=2), 5)
 
 
 def test_upscale_ratio_two_half_resolution_integrator():
     """SMAA_TU_2_0 (the default): integrator at s = ceil(S/2), jittered deferred lookups."""
     from hikari_amd import HikariSettings, Upscale
-    _run_pair("cornell", 64, 48, HikariSettings(upscale=Upscale.SMAA_TU_2_0), 5)
+    run_static("cornell", 64, 48, HikariSettings(upscale=Upscale.SMAA_TU_2_0), 5)
 
 
 @pytest.mark.parametrize("scene_fn,size", [("scene", (64, 40)), ("city", (48, 32))])
@@ -683,7 +461,7 @@ def test_proxy_scenes_with_directional_light(scene_fn, size):
     """City-proxy scenes: 140K-triangle BLASes, a directional light (cone sampling, any-hit
     shadow rays) and an emissive sphere."""
     from hikari_amd import HikariSettings, Upscale
-    _run_pair(scene_fn, size[0], size[1], HikariSettings(upscale=Upscale.SMAA_TU_1_0), 4)
+    run_static(scene_fn, size[0], size[1], HikariSettings(upscale=Upscale.SMAA_TU_1_0), 4)
 
 
 def test_hardware_f16_conversion_matches_software_rne():
@@ -718,13 +496,13 @@ def test_gbuffer_ordered_traversal_matches_oracle(scene_fn, size):
     the oracle's restatement of the same rule, on every G-buffer plane."""
     from hikari_amd import HikariSettings, Upscale, frame_inputs
     w, h = size
-    scene, cam, lights, r, o = _setup(w, h, HikariSettings(upscale=Upscale.SMAA_TU_1_0), scene_fn)
+    scene, cam, lights, r, o = pair(scene_fn, w, h, HikariSettings(upscale=Upscale.SMAA_TU_1_0))
     fi = frame_inputs(0, cam, lights, w, h)
     r.render_gbuffer(fi)
     o.render_gbuffer(fi)
-    for oid in range(11, 16):
-        m = mismatch_report(canon_plane(oid, r.output(oid)), canon_plane(oid, o.output(oid)), f"output {oid}")
-        assert not m, m
+    errors = []
+    compare_frame(r, o, 0, errors, outputs=range(11, 16), rids=())
+    assert not errors, "\n".join(errors)
     assert r.counters()["primary"] == o.counters()["primary"] == w * h
 
 
@@ -734,15 +512,11 @@ def test_subframe_accumulation_matches_numpy():
     from hikari_amd import HikariSettings, Upscale, _abi, frame_inputs
     w, h = 48, 32
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0)
-    scene, cam, lights, r, o = _setup(w, h, st)
+    scene, cam, lights, r, o = pair("cornell", w, h, st)
     s = st.to_c()
     acc = np.zeros((h, w, 4), np.float32)
     for f in range(5):
-        fi = frame_inputs(f, cam, lights, w, h)
-        r.render_gbuffer(fi)
-        r.render_frame(s, fi)
-        r.denoise(s, fi)
-        r.tone_sum(s)
+        passes(r, s, frame_inputs(f, cam, lights, w, h))
         r.accumulate(reset=(f == 0))
         t = r.output(_abi.OUT_TONE_MAPPED).view(np.float16).reshape(h, w, 4).astype(np.float32)
         acc = (acc + t).astype(np.float32)
@@ -771,64 +545,21 @@ def test_fast_reciprocal_is_exact():
     assert r.selftest_rcp(0, 0x80000000) == 0
 
 
-def _moved(scene_fn, seed):
-    """The scene with every instance moved/rotated/scaled by a seeded transform."""
-    from hikari_amd import examples
-    scene, cam, lights = examples.SCENES[scene_fn]()
-    rng = np.random.default_rng(seed)
-    for k, (mesh, mat, m) in enumerate(scene.instances):
-        a = rng.uniform(-0.4, 0.4)
-        c, s_ = np.cos(a), np.sin(a)
-        rot = np.array([[c, 0, s_, 0], [0, 1, 0, 0], [-s_, 0, c, 0], [0, 0, 0, 1]])
-        sc = np.diag([rng.uniform(0.8, 1.2), rng.uniform(0.8, 1.2), rng.uniform(0.8, 1.2), 1.0])
-        t = np.eye(4)
-        t[:3, 3] = rng.uniform(-0.2, 0.2, 3)
-        scene.instances[k] = (mesh, mat, t @ rot @ sc @ m)
-    return scene, cam, lights
-
-
-NODE_DT = np.dtype([("min", "<f4", 3), ("entry", "<u4"), ("max", "<f4", 3), ("exit", "<u4")])
-
-
 @pytest.mark.parametrize("scene_fn", ["cornell", "city"])
 def test_gpu_instance_update_matches_host_rebuild(scene_fn):
     """hk_update_instances (GPU re-run of prepare_instances: instance records, TLAS build,
     emissive records + alias tables, light BVH) equals the host builder's buffers for the same
     transforms, and the next frame renders bit-exactly like the oracle on the host-built scene."""
-    import ctypes as C
-    from hikari_amd import HikariRenderer, HikariSettings, Upscale, examples, frame_inputs, load_noise
+    from hikari_amd import HikariSettings, Upscale, examples, frame_inputs, load_noise
     from oracle import Oracle
     scene0, cam, lights = examples.SCENES[scene_fn]()
     d0 = scene0.build()
-    r = HikariRenderer(0)
-    r.set_noise()
-    r.upload_scene(scene0)
-    scene1, _, _ = _moved(scene_fn, 7)
+    r = renderer(scene0)
+    scene1, _, _ = moved(examples.SCENES[scene_fn](), 7)
     d1 = scene1.build()
     r.update_instances(scene1.instance_models(), scene1.instance_local_aabbs())
-
-    def host(idx, dt):
-        a = getattr(d1, ("vertices", "primitives", "asset_nodes", "alias_table", "instances", "instance_nodes",
-                         "materials", "emissive_nodes", "emissives")[idx])
-        buf = (C.c_uint8 * (a.count * dt.itemsize)).from_address(a.data)
-        return np.frombuffer(bytes(buf), dt)
-
-    inst_dt = np.dtype((np.void, 176))
-    for idx, dt in ((4, inst_dt), (3, np.dtype((np.void, 8))), (8, np.dtype((np.void, 64))), (7, NODE_DT)):
-        h = host(idx, dt)
-        g = r.scene_array(idx, dt, len(h))
-        assert h.tobytes() == g.tobytes(), f"array {idx} differs"
-    # TLAS: identical except that the device copy carries the instance box in each leaf
-    h = host(5, NODE_DT)
-    g = r.scene_array(5, NODE_DT, len(h))
-    assert np.array_equal(h["entry"], g["entry"]) and np.array_equal(h["exit"], g["exit"])
-    inner = h["entry"] < 0x80000000
-    assert h[inner].tobytes() == g[inner].tobytes()
-    inst = np.frombuffer(host(4, inst_dt).tobytes(), np.float32).reshape(-1, 44)
-    leaf_ids = h["entry"][~inner] - 0x80000000
-    assert np.array_equal(g["min"][~inner], inst[leaf_ids, 0:3]) and np.array_equal(g["max"][~inner], inst[leaf_ids, 4:7])
+    assert_instance_update_matches_host(r, d1)
     # and the frame
-    from test_gpu_motion import _compare as compare_with_motion
     w, hgt = 48, 32
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=False)
     r.resize(w, hgt, 1.0)
@@ -843,11 +574,8 @@ def test_gpu_instance_update_matches_host_rebuild(scene_fn):
     for f in range(2):
         fi = frame_inputs(f, cam, lights, w, hgt)
         for x in (r, o):
-            x.render_gbuffer(fi)
-            x.render_frame(s, fi)
-            x.denoise(s, fi)
-            x.tone_sum(s)
-        compare_with_motion(r, o, f, errors)
+            passes(x, s, fi)
+        compare_frame(r, o, f, errors, racy=RACY)
     assert not errors, "\n".join(errors[:10])
 
 
@@ -863,20 +591,10 @@ def test_post_process_smaa_taa_bit_exact(ratio_setting, taa, pipelined, hk_optio
         hk_options["pipeline_min_px"] = 0
     w, h = 62, 41
     st = HikariSettings(upscale=getattr(Upscale, ratio_setting), taa=getattr(Taa, taa))
-    scene, cam, lights, r, o = _setup(w, h, st)
-    s = st.to_c()
-    for f in range(4):
-        fi = frame_inputs(f, cam, lights, w, h)
-        for x in (r, o):
-            x.render_gbuffer(fi)
-            x.render_frame(s, fi)
-            x.denoise(s, fi)
-            x.tone_sum(s)
-            x.post_process(s, fi)
-        outs = [_abi.OUT_TONE_MAPPED, _abi.OUT_UPSCALED] + ([_abi.OUT_TAA] if taa == "Jasmine" else [])
-        for oid in outs:
-            m = mismatch_report(canon_plane(10, r.output(oid)), canon_plane(10, o.output(oid)), f"frame {f} output {oid}")
-            assert not m, m
+    scene, cam, lights, r, o = pair("cornell", w, h, st)
+    outs = [_abi.OUT_TONE_MAPPED, _abi.OUT_UPSCALED] + ([_abi.OUT_TAA] if taa == "Jasmine" else [])
+    run_frames(r, o, st.to_c(), (frame_inputs(f, cam, lights, w, h) for f in range(4)), post=True, counters=False,
+               outputs=outs, rids=())
 
 
 @pytest.mark.parametrize("mode", ["no_view", "no_temporal_reuse"])
@@ -885,22 +603,8 @@ def test_spatial_reuse_without_view_planes_bit_exact(hk_options, mode):
     (hk_device.h store_res_view): forced with spatial_view_planes=0, and taken by the runtime when the temporal
     pass does not store its records (temporal_reuse = false: the records in `cur` are older than any view
     plane).  Every plane and reservoir bit-exact against the oracle over 6 frames."""
-    from hikari_amd import HikariSettings, Upscale, frame_inputs
+    from hikari_amd import HikariSettings, Upscale
     if mode == "no_view":
         hk_options["spatial_view_planes"] = 0
-    w, h = 64, 64
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, temporal_reuse=mode != "no_temporal_reuse")
-    scene, cam, lights, r, o = _setup(w, h, st)
-    s = st.to_c()
-    errors = []
-    for f in range(6):
-        fi = frame_inputs(f, cam, lights, w, h)
-        for x in (r, o):
-            x.render_gbuffer(fi)
-            x.render_frame(s, fi)
-            x.denoise(s, fi)
-            x.tone_sum(s)
-        _compare_frame(r, o, f, errors)
-        if errors:
-            break
-    assert not errors, "\n".join(errors[:20])
+    run_static("cornell", 64, 64, st, 6, counters=False)

@@ -13,56 +13,9 @@ import ctypes
 import numpy as np
 import pytest
 
-from parity import canon_plane, canon_reservoirs, mismatch_report
+from parity import RACY, canon_plane, compare_frame, hip_runtime, mismatch_report, moved, pair, passes, renderer
 
 pytestmark = pytest.mark.gpu
-
-
-def _pair(scene_fn, w, h, settings, options=None):
-    from hikari_amd import HikariRenderer, examples, load_noise
-    from oracle import Oracle
-    scene, cam, lights = examples.SCENES[scene_fn]()
-    desc = scene.build()
-    r = HikariRenderer(0, options=options)
-    r.set_noise()
-    r.upload_scene(scene)
-    r.resize(w, h, settings.upscale.ratio())
-    o = Oracle(desc, load_noise(), w, h, settings.upscale.ratio(), textures=scene.textures)
-    return scene, cam, lights, r, o
-
-
-RACY = (4, 5, 8, 9)  # previous-spatial scatter targets under motion (light.wgsl:1092-1095; test_gpu_motion.py)
-
-
-def _compare(r, o, frame, errors, racy=()):
-    for oid in range(0, 17):
-        m = mismatch_report(canon_plane(oid, r.output(oid)), canon_plane(oid, o.output(oid)), f"frame {frame} output {oid}")
-        if m:
-            errors.append(m)
-    for rid in range(10):
-        g = canon_reservoirs(r.reservoirs(rid))
-        c = canon_reservoirs(o.reservoirs(rid)[: len(g)])
-        if rid in racy:  # written by the reference's racy scatter: the motion tests' tolerance
-            exact = float((g == c).all(axis=1).mean())
-            if exact < 0.97:
-                errors.append(f"frame {frame} reservoir {rid}: only {exact:.4f} of records exact")
-            continue
-        m = mismatch_report(g, c, f"frame {frame} reservoir {rid}")
-        if m:
-            errors.append(m)
-
-
-def _hip():
-    maps = [ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln]
-    path = next((m for m in maps if m.startswith("/opt/rocm")), maps[0] if maps else "libamdhip64.so")
-    hip = ctypes.CDLL(path)
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-    hip.hipFree.argtypes = [ctypes.c_void_p]
-    hip.hipStreamSynchronize.argtypes = [ctypes.c_void_p]
-    hip.hipStreamCreate.argtypes = [ctypes.POINTER(ctypes.c_void_p)]
-    hip.hipStreamDestroy.argtypes = [ctypes.c_void_p]
-    return hip
 
 
 def test_gbuffer_reuse_bit_exact():
@@ -77,12 +30,12 @@ def test_gbuffer_reuse_bit_exact():
     from hikari_amd import HikariSettings, Upscale, frame_inputs
     w, h = 96, 72
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=False, denoise=True)
-    scene, cam, lights, r, o = _pair("cornell", w, h, st, options={"pipeline_min_px": 0})
+    scene, cam, lights, r, o = pair("cornell", w, h, st, options={"pipeline_min_px": 0})
     s = st.to_c()
-    moved = copy.deepcopy(cam)
-    moved.transform.translation = np.array([0.05, 1.02, 4.0])
+    cam1 = copy.deepcopy(cam)
+    cam1.transform.translation = np.array([0.05, 1.02, 4.0])
     # (camera, previous camera, jitter) per frame
-    plan = [(cam, None, 0)] * 5 + [(moved, cam, 0)] + [(moved, None, 0)] * 4 + [(moved, None, 1)] * 3
+    plan = [(cam, None, 0)] * 5 + [(cam1, cam, 0)] + [(cam1, None, 0)] * 4 + [(cam1, None, 1)] * 3
     # frame 5 has motion vectors, so its slot is not reusable either: frame 7 traces again
     expect_reused = [False, False, True, True, True, False, False, False, True, True, False, False, False]
     errors = []
@@ -90,32 +43,24 @@ def test_gbuffer_reuse_bit_exact():
     for f, (c, prev, jitter) in enumerate(plan):
         fi = frame_inputs(f, c, lights, w, h, previous_camera=prev, jitter=jitter)
         for x in (r, o):
-            x.render_gbuffer(fi)
-            x.render_frame(s, fi)
-            x.denoise(s, fi)
-            x.tone_sum(s)
+            passes(x, s, fi)
         now = r.primary_reused()
         assert (now > reused) == expect_reused[f], f"frame {f}: reused {now - reused} rays"
         if expect_reused[f]:
             assert now - reused == w * h
         reused = now
-        _compare(r, o, f, errors, racy=RACY if f >= 5 else ())
+        compare_frame(r, o, f, errors, racy=RACY if f >= 5 else ())
         if errors:
             break
     assert not errors, "\n".join(errors[:20])
     assert r.counters() == o.counters()
     # off: the same frames traced every time
-    scene, cam, lights, r2, o2 = _pair("cornell", w, h, st, options={"pipeline_min_px": 0, "gbuffer_reuse": 0})
+    scene, cam, lights, r2, o2 = pair("cornell", w, h, st, options={"pipeline_min_px": 0, "gbuffer_reuse": 0})
     for f, (c, prev, jitter) in enumerate(plan):
-        fi = frame_inputs(f, c, lights, w, h, previous_camera=prev, jitter=jitter)
-        r2.render_gbuffer(fi)
-        r2.render_frame(s, fi)
-        r2.denoise(s, fi)
-        r2.tone_sum(s)
+        passes(r2, s, frame_inputs(f, c, lights, w, h, previous_camera=prev, jitter=jitter))
     assert r2.primary_reused() == 0
-    for oid in range(0, 17):
-        m = mismatch_report(canon_plane(oid, r.output(oid)), canon_plane(oid, r2.output(oid)), f"reuse on/off output {oid}")
-        assert not m, m
+    compare_frame(r, r2, "12, reuse on / off", errors, rids=())
+    assert not errors, "\n".join(errors)
 
 
 @pytest.mark.parametrize("denoise", [True, False], ids=["denoise", "tone_only"])
@@ -126,10 +71,10 @@ def test_foreign_stream_copies_keep_frames_exact(denoise):
     frame's plane bit for bit (oracle), so the copy waited for the frame's tail and the tone-sum two frames
     later waited for the copy; the frames themselves stay exact."""
     from hikari_amd import HikariSettings, Upscale, _abi, frame_inputs
-    hip = _hip()
+    hip = hip_runtime()
     w, h = 96, 72
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=denoise, denoise=denoise)
-    scene, cam, lights, r, o = _pair("cornell", w, h, st, options={"pipeline_min_px": 0})
+    scene, cam, lights, r, o = pair("cornell", w, h, st, options={"pipeline_min_px": 0})
     s = st.to_c()
     stream = ctypes.c_void_p()
     assert hip.hipStreamCreate(ctypes.byref(stream)) == 0
@@ -143,15 +88,9 @@ def test_foreign_stream_copies_keep_frames_exact(denoise):
     frames = 8
     for f in range(frames):
         fi = frame_inputs(f, cam, lights, w, h)
-        r.render_gbuffer(fi)
-        r.render_frame(s, fi)
-        r.denoise(s, fi)
-        r.tone_sum(s)
+        passes(r, s, fi)
         r.copy_output_rows(_abi.OUT_TONE_MAPPED, y0, rows, bufs[f & 1].value, False, stream.value)
-        o.render_gbuffer(fi)
-        o.render_frame(s, fi)
-        o.denoise(s, fi)
-        o.tone_sum(s)
+        passes(o, s, fi)
         want[f] = canon_plane(10, o.output(10)[y0:y0 + rows])
         if f >= 1 and f % 3 == 0:  # read the previous frame's copy back (its buffer is rewritten next frame)
             assert hip.hipStreamSynchronize(stream) == 0
@@ -166,7 +105,7 @@ def test_foreign_stream_copies_keep_frames_exact(denoise):
         m = mismatch_report(g, want[f], f"frame {f} copied rows")
         assert not m, m
     errors = []
-    _compare(r, o, frames - 1, errors)
+    compare_frame(r, o, frames - 1, errors)
     assert not errors, "\n".join(errors[:20])
     for b in bufs:
         hip.hipFree(b)
@@ -178,10 +117,10 @@ def test_foreign_copies_of_the_internal_variance():
     that plane, so the next hk_denoise (which rewrites it) waits for the copy.  Each frame's copy must hold that
     frame's plane (the oracle's), with frames queued pipelined behind the copies."""
     from hikari_amd import HikariSettings, Upscale, _abi, frame_inputs
-    hip = _hip()
+    hip = hip_runtime()
     w, h = 96, 72
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=True, denoise=True)
-    scene, cam, lights, r, o = _pair("cornell", w, h, st, options={"pipeline_min_px": 0})
+    scene, cam, lights, r, o = pair("cornell", w, h, st, options={"pipeline_min_px": 0})
     s = st.to_c()
     stream = ctypes.c_void_p()
     assert hip.hipStreamCreate(ctypes.byref(stream)) == 0
@@ -192,10 +131,7 @@ def test_foreign_copies_of_the_internal_variance():
     want = []
     for f in range(4):
         fi = frame_inputs(f, cam, lights, w, h)
-        r.render_gbuffer(fi)
-        r.render_frame(s, fi)
-        r.denoise(s, fi)
-        r.tone_sum(s)
+        passes(r, s, fi)
         r.copy_output_rows(_abi.OUT_DENOISE_INTERNAL_VARIANCE, 0, h, bufs[f].value, False, stream.value)
         o.render_gbuffer(fi)
         o.render_frame(s, fi)
@@ -222,28 +158,20 @@ def test_resize_between_pipelined_frames_bit_exact():
     from hikari_amd import HikariSettings, Upscale, frame_inputs, load_noise
     from oracle import Oracle
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=True, denoise=True)
-    scene, cam, lights, r, o = _pair("cornell", 64, 64, st, options={"pipeline_min_px": 0})
+    scene, cam, lights, r, o = pair("cornell", 64, 64, st, options={"pipeline_min_px": 0})
     desc = scene.build()
     s = st.to_c()
-
-    def frame(x, f, w, h):
-        fi = frame_inputs(f, cam, lights, w, h)
-        x.render_gbuffer(fi)
-        x.render_frame(s, fi)
-        x.denoise(s, fi)
-        x.tone_sum(s)
-
     for f in range(4):
-        frame(r, f, 64, 64)
+        passes(r, s, frame_inputs(f, cam, lights, 64, 64))
     errors = []
     for first, (w, h) in ((4, (63, 47)), (8, (64, 64))):
         r.resize(w, h, st.upscale.ratio())
         r.reset_counters()
         o = Oracle(desc, load_noise(), w, h, st.upscale.ratio(), textures=scene.textures)
         for f in range(first, first + 4):
-            frame(r, f, w, h)
-            frame(o, f, w, h)
-            _compare(r, o, f, errors)
+            for x in (r, o):
+                passes(x, s, frame_inputs(f, cam, lights, w, h))
+            compare_frame(r, o, f, errors)
         assert not errors, "\n".join(errors[:20])
         assert r.counters() == o.counters(), f"frames {first}-{first + 3} at {w}x{h}"
 
@@ -268,20 +196,15 @@ def test_band_with_host_planes_under_motion_runs_whole_band():
     camera: the planes carry non-zero velocity, so temporal reprojection reads other rows and every pass
     must run on the whole band.  The band's outputs with the default per-pass row windows equal those with
     band_full_windows = 1 (spatial reuse off: nothing reads the racy scatter targets)."""
-    from hikari_amd import HikariRenderer, HikariSettings, Upscale, examples, frame_inputs
+    from hikari_amd import HikariSettings, Upscale, examples, frame_inputs
     w, h = 64, 192
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=False, denoise=True)
     scene, cam, lights = examples.SCENES["cornell"]()
     s = st.to_c()
-    src = HikariRenderer(0)
-    src.set_noise()
-    src.upload_scene(scene)
-    src.resize(w, h, 1.0)
+    src = renderer(scene, (w, h))
     bands = []
     for full in (0, 1):
-        b = HikariRenderer(0, options={"band_full_windows": full})
-        b.set_noise()
-        b.upload_scene(scene)
+        b = renderer(scene, options={"band_full_windows": full})
         b.set_band_halo(40)
         b.resize(w, h, 1.0, 64, 64)
         bands.append(b)
@@ -316,25 +239,19 @@ def test_gbuffer_stack_bound_after_instance_updates(scene_fn):
     the G-buffer planes of the default walk equal those of the same walk with all 16 LDS levels
     (gbuffer_stack_full), of the deep variant with its scratch stack (gbuffer_deep), of both without the
     small-frame scene staging (gbuffer_lds_max_px = 0: node loads from global memory), and the oracle's."""
-    from hikari_amd import HikariRenderer, examples, frame_inputs, load_noise
+    from hikari_amd import examples, frame_inputs, load_noise
     from oracle import Oracle
-    from test_gpu_parity import _moved
     w, h = 128, 72
     scene, cam, lights = examples.SCENES[scene_fn]()
-    ctx = []
-    for opts in ({}, {"gbuffer_stack_full": 1}, {"gbuffer_deep": 1}, {"gbuffer_lds_max_px": 0},
-                 {"gbuffer_lds_max_px": 0, "gbuffer_deep": 1}):
-        r = HikariRenderer(0, options=opts)
-        r.set_noise()
-        r.upload_scene(scene)
-        r.resize(w, h, 1.0)
-        ctx.append(r)
+    ctx = [renderer(scene, (w, h), options=opts)
+           for opts in ({}, {"gbuffer_stack_full": 1}, {"gbuffer_deep": 1}, {"gbuffer_lds_max_px": 0},
+                        {"gbuffer_lds_max_px": 0, "gbuffer_deep": 1})]
     for f, seed in enumerate((3, 11, 19)):
-        moved, _, _ = _moved(scene_fn, seed)
+        scene1, _, _ = moved(examples.SCENES[scene_fn](), seed)
         for r in ctx:
-            r.update_instances(moved.instance_models(), moved.instance_local_aabbs())
+            r.update_instances(scene1.instance_models(), scene1.instance_local_aabbs())
             r.render_gbuffer(frame_inputs(f, cam, lights, w, h))
-        o = Oracle(moved.build(), load_noise(), w, h, 1.0)
+        o = Oracle(scene1.build(), load_noise(), w, h, 1.0)
         o.render_gbuffer(frame_inputs(f, cam, lights, w, h))
         for oid in (0, 11, 12, 13, 14):  # albedo, position, normal, depth gradient, ids (velocity: see motion tests)
             planes = [canon_plane(oid, r.output(oid)) for r in ctx]

@@ -9,48 +9,19 @@ import numpy as np
 import pytest
 
 import scene_ladder as sl
-from parity import canon_plane, canon_reservoirs, mismatch_report
+from parity import (NODE_DT, RACY, assert_instance_update_matches_host, canon_plane, compare_frame, host_scene_array,
+                    moved, pair, passes, renderer, run_frames)
 
 pytestmark = pytest.mark.gpu
 
 
-def _renderer(name, options=None):
-    from hikari_amd import HikariRenderer
-    scene, cam, lights = sl.built(name)
-    r = HikariRenderer(0, options=options)
-    r.set_noise()
-    r.upload_scene(scene)
-    r.resize(*sl.SIZE, 1.0)
-    return scene, cam, lights, r
-
-
-def _compare_frame(r, ref, frame, errors, outputs=range(17), rids=range(10)):
-    """test_gpu_parity._compare_frame against a stored oracle frame (planes, reservoirs)."""
-    planes, reservoirs = ref
-    for oid in outputs:
-        m = mismatch_report(canon_plane(oid, r.output(oid)), planes[oid], f"frame {frame} output {oid}")
-        if m:
-            errors.append(m)
-    for rid in rids:
-        g = canon_reservoirs(r.reservoirs(rid))
-        m = mismatch_report(g, reservoirs[rid][: len(g)], f"frame {frame} reservoir {rid}")
-        if m:
-            errors.append(m)
-
-
-def _frames_against_reference(name, r, cam, lights, bounces=1):
+def _rung_against_reference(name, bounces=1, wavefront=False):
+    """A renderer of the rung over the ladder's frames against the stored oracle frames and counters."""
     from hikari_amd import frame_inputs
-    frames, counters = sl.reference(name, bounces)
-    s = sl.ladder_settings(bounces).to_c()
-    w, h = sl.SIZE
-    errors = []
-    for f in range(sl.FRAMES):
-        sl.passes(r, s, frame_inputs(f, cam, lights, w, h))
-        _compare_frame(r, frames[f], f, errors)
-        if errors:
-            break
-    assert not errors, "\n".join(errors[:20])
-    assert r.counters() == counters
+    scene, cam, lights = sl.built(name)
+    r = renderer(scene, sl.SIZE, wavefront=wavefront)
+    run_frames(r, sl.reference(name, bounces), sl.ladder_settings(bounces).to_c(),
+               (frame_inputs(f, cam, lights, *sl.SIZE) for f in range(sl.FRAMES)))
 
 
 @pytest.mark.parametrize("lds", [1, 0, 2], ids=["lds_default", "lds_off", "lds_all"])
@@ -60,8 +31,7 @@ def test_ladder_rung_bit_exact(hk_options, name, lds):
     0..16, reservoir buffers 0..9 and the ray counters, with the scene staged where the defaults stage it, nowhere,
     and in every traversal kernel."""
     hk_options["lds_scene"] = lds
-    scene, cam, lights, r = _renderer(name)
-    _frames_against_reference(name, r, cam, lights)
+    _rung_against_reference(name)
 
 
 @pytest.mark.parametrize("variant", list(sl.LAUNCH_VARIANTS))
@@ -74,10 +44,7 @@ def test_ladder_launch_variants_bit_exact(hk_options, name, variant):
     role stages (the IndStash behind the staged scene) and the compacted fused kernels."""
     hk_options["lds_scene"] = 2
     hk_options.update(sl.LAUNCH_VARIANTS[variant])
-    scene, cam, lights, r = _renderer(name)
-    if variant == "wavefront":
-        r.set_wavefront(True)
-    _frames_against_reference(name, r, cam, lights, bounces=2 if variant == "bounces_2" else 1)
+    _rung_against_reference(name, bounces=2 if variant == "bounces_2" else 1, wavefront=variant == "wavefront")
 
 
 _gbuffer_reference = {}
@@ -110,7 +77,8 @@ def test_ladder_gbuffer_walks_bit_exact(name, case):
     staging, without it, with all 16 stack levels asked for, with the deep (scratch) stack, and under an
     orthographic view."""
     from hikari_amd import Camera, frame_inputs
-    scene, cam, lights, r = _renderer(name, GBUFFER_CASES[case])
+    scene, cam, lights = sl.built(name)
+    r = renderer(scene, sl.SIZE, options=GBUFFER_CASES[case])
     if case == "orthographic":
         cam = Camera.orthographic(cam.transform, 3.0)
     planes, counters = _gbuffer_oracle(name, cam)
@@ -118,8 +86,8 @@ def test_ladder_gbuffer_walks_bit_exact(name, case):
     fi = frame_inputs(0, cam, lights, w, h)
     assert (fi.view.projection[15] == 1.0) == (case == "orthographic")
     r.render_gbuffer(fi)
-    errors = [m for m in (mismatch_report(canon_plane(oid, r.output(oid)), planes[oid], f"output {oid}")
-                          for oid in range(11, 16)) if m]
+    errors = []
+    compare_frame(r, (planes, ()), 0, errors, outputs=range(11, 16), rids=())
     assert not errors, "\n".join(errors)
     assert r.counters()["primary"] == counters["primary"] == w * h
     depth = planes[11].view(np.float32).reshape(h, w, 4)[..., 3]
@@ -132,7 +100,8 @@ def test_ladder_trace_matches_oracle(name):
     any-hit / closest-hit early distances and excluded instances (test_trace_matches_oracle on cornell)."""
     from hikari_amd import load_noise
     from oracle import Oracle
-    scene, cam, lights, r = _renderer(name)
+    scene, cam, lights = sl.built(name)
+    r = renderer(scene, sl.SIZE)
     o = Oracle(scene.desc, load_noise(), 16, 16, 1.0)
     rng = np.random.default_rng(7)
     n = 20000
@@ -151,64 +120,23 @@ def test_ladder_trace_matches_oracle(name):
     assert hit > (0.001 if name == "one_triangle" else 0.25), hit
 
 
-NODE_DT = np.dtype([("min", "<f4", 3), ("entry", "<u4"), ("max", "<f4", 3), ("exit", "<u4")])
-ARRAYS = ("vertices", "primitives", "asset_nodes", "alias_table", "instances", "instance_nodes", "materials",
-          "emissive_nodes", "emissives")
-
-
-def _moved(name, seed):
-    """The rung with every instance moved / rotated / scaled by a seeded transform (test_gpu_parity._moved)."""
-    scene, cam, lights = sl.build(name)
-    rng = np.random.default_rng(seed)
-    for k, (mesh, mat, m) in enumerate(scene.instances):
-        a = rng.uniform(-0.4, 0.4)
-        c, s_ = np.cos(a), np.sin(a)
-        rot = np.array([[c, 0, s_, 0], [0, 1, 0, 0], [-s_, 0, c, 0], [0, 0, 0, 1]])
-        sc = np.diag([rng.uniform(0.8, 1.2), rng.uniform(0.8, 1.2), rng.uniform(0.8, 1.2), 1.0])
-        t = np.eye(4)
-        t[:3, 3] = rng.uniform(-0.2, 0.2, 3)
-        scene.instances[k] = (mesh, mat, t @ rot @ sc @ m)
-    return scene, cam, lights
-
-
 @pytest.mark.parametrize("name", ["emitters_3", "no_emitters", "light_at_limit"])
 def test_ladder_instance_update_matches_host_rebuild(name):
     """hk_update_instances on a rung (test_gpu_instance_update_matches_host_rebuild): the device's instance, alias,
     emissive, light-BVH and TLAS arrays against the host builder's for seeded transforms — a light BVH over three
     emitters, and the empty-emissive branch — then two frames against the oracle on the host-built scene."""
-    import ctypes as C
-
     from hikari_amd import HikariSettings, Upscale, frame_inputs, load_noise
     from oracle import Oracle
-    from test_gpu_motion import _compare as compare_with_motion
-    scene0, cam, lights, r = _renderer(name)
-    scene1, _, _ = _moved(name, 7)
+    scene0, cam, lights = sl.built(name)
+    r = renderer(scene0, sl.SIZE)
+    scene1, _, _ = moved(sl.build(name), 7)
     d1 = scene1.build()
     r.update_instances(scene1.instance_models(), scene1.instance_local_aabbs())
-
-    def host(idx, dt):
-        a = getattr(d1, ARRAYS[idx])
-        return np.frombuffer(C.string_at(a.data, a.count * dt.itemsize) if a.count else b"", dt)
-
-    inst_dt = np.dtype((np.void, 176))
     emitters = len(sl.RUNGS[name]["emitters"])
-    assert len(host(8, np.dtype((np.void, 64)))) == emitters
-    assert len(host(7, NODE_DT)) == (3 * emitters - 2 if emitters else 0)
-    for idx, dt in ((4, inst_dt), (3, np.dtype((np.void, 8))), (8, np.dtype((np.void, 64))), (7, NODE_DT)):
-        h = host(idx, dt)
-        if len(h) == 0:
-            continue  # an empty array of the scene: nothing to read back (the frames below cover the branch)
-        g = r.scene_array(idx, dt, len(h))
-        assert h.tobytes() == g.tobytes(), f"array {idx} differs"
-    # TLAS: identical except that the device copy carries the instance box in each leaf
-    h = host(5, NODE_DT)
-    g = r.scene_array(5, NODE_DT, len(h))
-    assert np.array_equal(h["entry"], g["entry"]) and np.array_equal(h["exit"], g["exit"])
-    inner = h["entry"] < 0x80000000
-    assert h[inner].tobytes() == g[inner].tobytes()
-    inst = np.frombuffer(host(4, inst_dt).tobytes(), np.float32).reshape(-1, 44)
-    leaf_ids = h["entry"][~inner] - 0x80000000
-    assert np.array_equal(g["min"][~inner], inst[leaf_ids, 0:3]) and np.array_equal(g["max"][~inner], inst[leaf_ids, 4:7])
+    assert len(host_scene_array(d1, 8, np.dtype((np.void, 64)))) == emitters
+    assert len(host_scene_array(d1, 7, NODE_DT)) == (3 * emitters - 2 if emitters else 0)
+    # an empty array of the scene: nothing to read back (the frames below cover the branch)
+    assert_instance_update_matches_host(r, d1, skip_empty=True)
     # and the frames: the oracle sees the uploaded scene, then the moved one (motion vectors reproject from the
     # uploaded models); single-threaded with spatial reuse off, as the reprojection scatter is a write race
     w, hgt = sl.SIZE
@@ -220,8 +148,8 @@ def test_ladder_instance_update_matches_host_rebuild(name):
     for f in range(2):
         fi = frame_inputs(f, cam, lights, w, hgt)
         for x in (r, o):
-            sl.passes(x, s, fi)
-        compare_with_motion(r, o, f, errors)
+            passes(x, s, fi)
+        compare_frame(r, o, f, errors, racy=RACY)
     assert not errors, "\n".join(errors[:10])
     assert r.counters() == o.counters()
 
@@ -230,13 +158,10 @@ def test_ladder_two_rounds_moving_camera():
     """The two-round rung under the examples' orbit camera (examples.orbit, 0.5 degrees per frame about the scene's
     centre), spatial reuse off and the oracle single-threaded: test_gpu_motion's comparison — everything outside
     the racy spatial-pair scatter targets bit-exact, those within its tolerance — and motion vectors present."""
-    from hikari_amd import HikariSettings, Upscale, examples, frame_inputs, load_noise
-    from oracle import Oracle
-    from test_gpu_motion import _compare as compare_with_motion
-    scene, cam, lights, r = _renderer("two_rounds")
+    from hikari_amd import HikariSettings, Upscale, examples, frame_inputs
     w, h = sl.SIZE
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=False, denoise=True)
-    o = Oracle(scene.desc, load_noise(), w, h, 1.0, threads=1)
+    scene, cam, lights, r, o = pair(sl.built("two_rounds"), w, h, st, threads=1)
     s = st.to_c()
     target = (0.0, 1.0, 0.0)
     errors = []
@@ -245,8 +170,8 @@ def test_ladder_two_rounds_moving_camera():
         fi = frame_inputs(f, examples.orbit(cam, target, f), lights, w, h,
                           previous_camera=examples.orbit(cam, target, f - 1) if f else None)
         for x in (r, o):
-            sl.passes(x, s, fi)
-        compare_with_motion(r, o, f, errors)
+            passes(x, s, fi)
+        compare_frame(r, o, f, errors, racy=RACY)
         vel = r.output(15).view(np.float32).reshape(h, w, 4)[..., :2]
         moved += int((vel != 0).any(axis=-1).sum())
         if errors:
