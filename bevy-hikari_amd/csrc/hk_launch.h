@@ -7,6 +7,7 @@
 
 #include "hk_device.h"
 #include "../../include/hk_post.h"
+#include "../../include/hk_fsr.h"
 
 namespace hk {
 
@@ -154,6 +155,17 @@ struct PostArgs {
 void launch_smaa(const PostArgs& P, hipStream_t st);
 void launch_smaa_extrapolate(const PostArgs& P, hipStream_t st);
 void launch_taa(const PostArgs& P, hipStream_t st);
+
+// FSR1 (hk_fsr.hip over include/hk_fsr.h): EASU reads `in` (RGBA16F at s) with `easu`, RCAS reads `in` (RGBA16F at S,
+// EASU's output) with `rcas`; both write `out` at S
+struct FsrArgs {
+    hk_pp_tex in;
+    hk_pp_out out;
+    hk_fsr_easu_con easu;
+    float rcas;
+};
+void launch_fsr_easu(const FsrArgs& A, bool tiled, hipStream_t st);
+void launch_fsr_rcas(const FsrArgs& A, hipStream_t st);
 
 bool lane_stats_take(unsigned long long out[2 * LANE_SLOTS], hipStream_t st);
 void launch_gbuffer(const FrameArgs& A, const ViewArgs& V, uint2* albedo, uint32_t stack_need, hipStream_t st);

@@ -61,6 +61,7 @@ enum Opt {
     OPT_PERSISTENT_INDIRECT,
     OPT_COMPACT_EMITTER,
     OPT_COMPACT_SHADOW,
+    OPT_FSR_TILED,           // EASU with its input footprint staged in LDS (hk_fsr.hip)
     OPT_COUNT
 };
 struct OptDef {
@@ -76,7 +77,7 @@ constexpr OptDef OPTS[OPT_COUNT] = {
     {"lds_scene", 1, 0, 2},                {"gbuffer_stack_full", 0, 0, 1}, {"gbuffer_deep", 0, 0, 1},
     {"gbuffer_lds_max_px", 6e5, 0.0, 1e12},
     {"direct_w4_min_px", 4e5, 0.0, 1e12},  {"fused_w4", 1, 0, 1},          {"persistent_indirect", 0, 0, 1},
-    {"compact_emitter", 0, 0, 1},          {"compact_shadow", 0, 0, 1},
+    {"compact_emitter", 0, 0, 1},          {"compact_shadow", 0, 0, 1},    {"fsr_tiled", 1, 0, 1},
 };
 
 // One slot of the planes k_gbuffer double-buffers (hk_ctx::g / g_prev: swapped on each hk_render_gbuffer) so a
@@ -356,6 +357,8 @@ struct hk_ctx {
     uint2* upscale = nullptr;     // upscale_output[0] (SMAA TU4x), U = ceil(S * 2 / ratio)
     uint2* taa_buf[2] = {};       // taa_output[2]
     uint32_t upscale_wh[2] = {0, 0}, taa_wh[2] = {0, 0};
+    uint2* fsr_buf[2] = {};       // upscale_output[0..1] under FSR1 (EASU, RCAS), S
+    float fsr_sharpness = 0.0f;   // Upscale::Fsr1::sharpness (hk_set_fsr1_sharpness)
     float4* accum = nullptr;      // sub-frame accumulator (hk_accumulate), allocated on first use
     uint2* accum_out = nullptr;
     uint32_t accum_n = 0;
@@ -517,6 +520,7 @@ std::vector<Target> targets(hk_ctx* c)
     for (auto& b : c->tone_buf) add(b, 's');
     add(c->upscale, 0);
     for (auto& b : c->taa_buf) add(b, 0);
+    for (auto& b : c->fsr_buf) add(b, 0);
     add(c->accum, 0);
     add(c->accum_out, 0);
     add(c->wf_queue1, 0);
@@ -1991,7 +1995,7 @@ int hk_post_process(hk_ctx* c, const hk_settings* st, const hk_frame_inputs* in,
     int rc = check_ready(c, false);
     if (rc) return rc;
     if (!st || !in) return fail(c, HK_ERR_INVALID, "null settings or frame inputs");
-    if (c->S_rows != (int32_t)c->S[1]) return fail(c, HK_ERR_STATE, "hk_post_process needs a whole-frame context");
+    if (c->S_rows != (int32_t)c->S[1]) return fail(c, HK_ERR_STATE, "hk_post_process (SMAA TU4x, TAA, FSR1) needs a whole-frame context");
     (void)hipSetDevice(c->device);
     hipStream_t s = pick(c, stream);
     HK_TRY(c->sch.gb_join(s));
@@ -1999,9 +2003,10 @@ int hk_post_process(hk_ctx* c, const hk_settings* st, const hk_frame_inputs* in,
     const uint32_t head = c->head;
     HK_TRY(c->sch.ext_wait(s, c->upscale));
     HK_TRY(c->sch.ext_wait(s, c->taa_buf[head]));
+    for (auto& b : c->fsr_buf) HK_TRY(c->sch.ext_wait(s, b));
     // post_process.rs:663-731 sizes: ceil(S * scale), scale = 1 / ratio, x 2 after SMAA TU4x
     float scale = 1.0f / c->ratio;
-    const bool smaa = st->upscale == 0u, taa = st->taa == 0u;
+    const bool smaa = st->upscale == 0u, fsr = st->upscale == 1u, taa = st->taa == 0u;
     PostArgs P;
     P.frame.number = in->frame_number;
     for (int k = 0; k < 4; ++k) P.frame.clear_color[k] = st->clear_color[k];
@@ -2048,6 +2053,27 @@ int hk_post_process(hk_ctx* c, const hk_settings* st, const hk_frame_inputs* in,
         P.in.previous_render = tex(c->taa_buf[1u - head], T0, T1, 1, 4);
         P.in.output = hk_pp_out{(uint16_t*)c->taa_buf[head], T0, T1};
         timed(c, "taa_jasmine", s, [&] { launch_taa(P, s); });
+        taa_input = tex(c->taa_buf[head], T0, T1, 1, 4);
+    }
+    if (fsr) {
+        // post_process.rs:1279-1308: EASU from the TAA output (the tone-mapped plane when TAA is off) at s to
+        // upscale_output[0] at S, RCAS from there to upscale_output[1]
+        if ((uint64_t)S0 * S1 >= (1ull << 31)) return fail(c, HK_ERR_INVALID, "FSR1 output above 2^31 pixels");
+        for (auto& b : c->fsr_buf)
+            if (!b) {
+                HK_HIP(c, hipMalloc(&b, (size_t)S0 * S1 * sizeof(uint2)));
+                HK_HIP(c, hipMemset(b, 0, (size_t)S0 * S1 * sizeof(uint2)));
+            }
+        FsrArgs A;
+        A.in = taa_input;
+        A.out = hk_pp_out{(uint16_t*)c->fsr_buf[0], S0, S1};
+        hk_fsr_easu_constants(&A.easu, (float)A.in.w, (float)A.in.h, (float)S0, (float)S1);
+        A.rcas = hk_fsr_rcas_constant(c->fsr_sharpness);
+        const bool tiled = c->on(OPT_FSR_TILED);
+        timed(c, "fsr_easu", s, [&] { launch_fsr_easu(A, tiled, s); });
+        A.in = tex(c->fsr_buf[0], S0, S1, 1, 4);
+        A.out = hk_pp_out{(uint16_t*)c->fsr_buf[1], S0, S1};
+        timed(c, "fsr_rcas", s, [&] { launch_fsr_rcas(A, s); });
     }
     // the next k_gbuffer overwrites the previous-frame planes read here
     HK_HIP(c, hipEventRecord(c->sch.ev_post, s));
@@ -2119,6 +2145,8 @@ static void* output_ptr(hk_ctx* c, int id, uint32_t* w, uint32_t* h, uint32_t* b
     case HK_OUT_UPSCALED: p = c->upscale; W = c->upscale_wh[0]; H = c->upscale_wh[1]; break;
     case HK_OUT_TAA: p = c->taa_buf[c->head]; W = c->taa_wh[0]; H = c->taa_wh[1]; break;
     case HK_OUT_ACCUMULATED: p = c->accum_out; break;
+    case HK_OUT_FSR_EASU: S_plane(c->fsr_buf[0], 8); break;
+    case HK_OUT_FSR_RCAS: S_plane(c->fsr_buf[1], 8); break;
     case HK_OUT_GBUF_POSITION: S_plane(c->g.position, 16); break;
     case HK_OUT_GBUF_NORMAL: S_plane(c->g.normal, 4); break;
     case HK_OUT_GBUF_DEPTH_GRADIENT: S_plane(c->g.depth_gradient, 8); break;
@@ -2156,6 +2184,14 @@ int hk_lane_stats(hk_ctx* c, const char** names, unsigned long long* active, uns
         if (iterations) iterations[i] = c->lane_its[i];
     }
     return n;
+}
+
+int hk_set_fsr1_sharpness(hk_ctx* c, float sharpness)
+{
+    if (!c) return HK_ERR_INVALID;
+    if (!std::isfinite(sharpness)) return fail(c, HK_ERR_INVALID, "FSR1 sharpness must be finite");
+    c->fsr_sharpness = sharpness;  // not clamped (lib.rs:507-511)
+    return HK_OK;
 }
 
 int hk_set_wavefront(hk_ctx* c, int enable)

@@ -35,6 +35,8 @@ OUT_ACCUMULATED = 17
 OUT_UPSCALED = 18
 OUT_TAA = 19
 OUT_TONE_MAPPED_PREVIOUS = 20
+OUT_FSR_EASU = 21  # FSR1: upscale_output[0], S
+OUT_FSR_RCAS = 22  # FSR1: upscale_output[1], S (the displayed frame)
 OUT_DENOISE_INTERNAL_VARIANCE = 16
 RESERVOIR_BUFFERS = 10
 
@@ -166,6 +168,7 @@ def lib() -> C.CDLL:
         "hk_tone_sum": (i32, [vp, C.POINTER(hk_settings), vp]),
         "hk_accumulate": (i32, [vp, i32, vp]),
         "hk_post_process": (i32, [vp, C.POINTER(hk_settings), C.POINTER(hk_frame_inputs), vp]),
+        "hk_set_fsr1_sharpness": (i32, [vp, C.c_float]),
         "hk_update_instances": (i32, [vp, vp, vp, u32, vp]),
         "hk_read_scene_array": (i32, [vp, i32, vp, C.c_size_t]),
         "hk_resolve_accumulation": (i32, [vp, vp]),
@@ -208,7 +211,7 @@ EXPORTED_SYMBOLS = [
     "hk_abi_version", "hk_create", "hk_destroy", "hk_last_error", "hk_settings_default", "hk_set_option",
     "hk_get_option", "hk_option_name", "hk_scene_upload", "hk_scene_stage_bytes", "hk_scene_gbuffer_stack",
     "hk_set_noise", "hk_texture_upload", "hk_resize", "hk_resize_striped", "hk_set_band_halo", "hk_band_info", "hk_band_window_grow", "hk_reservoir_rows", "hk_resize_tile", "hk_tile_info", "hk_copy_output_rect", "hk_copy_output_rows", "hk_render_gbuffer", "hk_set_gbuffer_plane", "hk_render_frame",
-    "hk_denoise", "hk_tone_sum", "hk_update_instances", "hk_read_scene_array", "hk_post_process", "hk_accumulate", "hk_resolve_accumulation", "hk_output_info", "hk_get_output", "hk_output_device_ptr", "hk_sync", "hk_set_wavefront", "hk_lane_stats", "hk_dump_reservoirs",
+    "hk_denoise", "hk_tone_sum", "hk_update_instances", "hk_read_scene_array", "hk_post_process", "hk_set_fsr1_sharpness", "hk_accumulate", "hk_resolve_accumulation", "hk_output_info", "hk_get_output", "hk_output_device_ptr", "hk_sync", "hk_set_wavefront", "hk_lane_stats", "hk_dump_reservoirs",
     "hk_load_reservoirs", "hk_reset_counters", "hk_read_counters", "hk_enable_kernel_timing", "hk_kernel_timing", "hk_set_kernel_timing_interval",
     "hk_trace", "hk_selftest_f16", "hk_selftest_div", "hk_selftest_rcp", "hks_create", "hks_destroy", "hks_last_error", "hks_add_mesh", "hks_add_material",
     "hks_add_instance", "hks_build", "hks_get_desc",

@@ -225,9 +225,14 @@ class HikariRenderer:
         return out
 
     def post_process(self, settings: _abi.hk_settings, inputs: _abi.hk_frame_inputs, stream=None) -> None:
-        """SMAA TU4x + TAA Jasmine after tone mapping (hk_post_process)."""
+        """SMAA TU4x or FSR1 (settings.upscale) and TAA Jasmine after tone mapping (hk_post_process); FSR1 leaves the
+        display-size frame in OUT_FSR_RCAS."""
         _check(self.ctx, self._L.hk_post_process(self.ctx, C.byref(settings), C.byref(inputs), _stream(stream)),
                "hk_post_process")
+
+    def set_fsr1_sharpness(self, sharpness: float) -> None:
+        """`Upscale::Fsr1 { sharpness }` for the following post_process calls (hk_set_fsr1_sharpness)."""
+        _check(self.ctx, self._L.hk_set_fsr1_sharpness(self.ctx, float(sharpness)), "hk_set_fsr1_sharpness")
 
     def accumulate(self, reset: bool = False, stream=None) -> None:
         """Add the tone-mapped output to the sub-frame accumulator (hk_accumulate)."""
@@ -368,6 +373,7 @@ class HikariPlugin:
 
     def resize(self, width: int, height: int, band_y0: int = 0, band_rows: int = 0):
         self.renderer.resize(width, height, self.settings.upscale.ratio(), band_y0, band_rows)
+        self.renderer.set_fsr1_sharpness(self.settings.upscale.sharpness())
 
     def frame(self, camera, lights, gbuffer: bool = True, stream=None) -> None:
         """One frame.  The previous frame's camera is the PreviousViewUniform of the motion vectors

@@ -105,7 +105,8 @@ typedef struct hk_settings {
     uint32_t denoise;
     uint32_t taa;           /* 0 = Jasmine, 1 = None (hk_post_process) */
     float upscale_ratio;    /* Upscale::ratio(), clamped to [1, 2] (lib.rs:501-505) */
-    uint32_t upscale;       /* 0 = SmaaTu4x (default), 1 = Fsr1 (not provided: hk_post_process skips it) */
+    uint32_t upscale;       /* 0 = SmaaTu4x (default), 1 = Fsr1: hk_post_process runs EASU + RCAS after the TAA, with the
+                               sharpness of hk_set_fsr1_sharpness (Upscale::Fsr1::sharpness is not in this record) */
 } hk_settings;
 
 /* The parts of Bevy's `View` uniform the integrator reads (light.wgsl:714-727). */
@@ -175,7 +176,9 @@ typedef enum hk_output_id {
     HK_OUT_TAA = 19,              /* RGBA16F: TAA Jasmine output of this frame (taa_output[head]) */
     HK_OUT_TONE_MAPPED_PREVIOUS = 20, /* RGBA16F, s: the previous frame's tone-mapped output (tone_mapping_output
                                        * [1 - head]), intact until this frame's successor's tone-sum */
-    HK_OUT_COUNT = 21
+    HK_OUT_FSR_EASU = 21,         /* RGBA16F, S: FSR1 EASU output (upscale_output[0] under Upscale::Fsr1) */
+    HK_OUT_FSR_RCAS = 22,         /* RGBA16F, S: FSR1 RCAS output (upscale_output[1]): the frame the overlay presents */
+    HK_OUT_COUNT = 23
 } hk_output_id;
 
 /* Reservoir buffer ids 0..9 as allocated by light.rs:350-361; the channel pairs
@@ -227,6 +230,8 @@ void hk_settings_default(hk_settings* out);
  *                            compacted batch (long walks first) on frames without emissive validation
  *   compact_shadow (0)       shadow walks of a workgroup as one compacted batch (fused launch, indirect pass)
  *                            (both measured slower than the per-pixel walks: DESIGN §4)
+ *   fsr_tiled (1)            FSR1 EASU with each workgroup's input footprint staged in LDS as f32 (0: every tap from
+ *                            global memory); tests force both variants with it
  * hk_set_option returns HK_ERR_INVALID for an unknown key, a value outside the key's range, or a fractional value
  * for any key but the pixel-count thresholds (*_px). */
 int hk_set_option(hk_ctx* ctx, const char* key, double value);
@@ -263,8 +268,16 @@ int hk_read_scene_array(hk_ctx* ctx, int array, void* dst, size_t bytes);
  * (smaa.wgsl `smaa_tu4x` + `smaa_tu4x_extrapolate`, when settings->upscale == 0) then TAA Jasmine
  * (taa.wgsl, when settings->taa == 0).  Reads the previous frame's tone-mapped output and G-buffer
  * position / velocity planes (the reference's ping-pong textures, prepass.rs:309-317, head =
- * frame_number % 2).  Whole-frame contexts only. */
+ * frame_number % 2).  With settings->upscale == 1 (Upscale::Fsr1) the TAA runs at s and FSR1 follows
+ * (post_process.rs:1279-1308; include/hk_fsr.h): EASU upscales the TAA output (the tone-mapped plane when the
+ * TAA is off) from s to S into HK_OUT_FSR_EASU, RCAS sharpens that into HK_OUT_FSR_RCAS, the displayed frame.
+ * Both planes are allocated by the first such call (until then they have no hk_output_info).  Whole-frame
+ * contexts only. */
 int hk_post_process(hk_ctx* ctx, const hk_settings* settings, const hk_frame_inputs* inputs, void* stream);
+/* Upscale::Fsr1::sharpness of the context (lib.rs:478-513): stops of sharpness reduction, 0 (the default) = maximum
+ * sharpness; RCAS scales its lobe by exp2(-sharpness).  Not clamped, as the reference does not; a non-finite value
+ * returns HK_ERR_INVALID.  Takes effect at the next hk_post_process. */
+int hk_set_fsr1_sharpness(hk_ctx* ctx, float sharpness);
 
 /* Sub-frame accumulation (N integrator sub-frames per displayed frame, each
  * exactly one reference frame): hk_accumulate adds the current tone-mapped output (HK_OUT_TONE_MAPPED)
