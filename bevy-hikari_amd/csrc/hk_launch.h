@@ -8,6 +8,7 @@
 #include "hk_device.h"
 #include "../../include/hk_post.h"
 #include "../../include/hk_fsr.h"
+#include "../../include/hk_overlay.h"
 
 namespace hk {
 
@@ -166,6 +167,18 @@ struct FsrArgs {
 };
 void launch_fsr_easu(const FsrArgs& A, bool tiled, hipStream_t st);
 void launch_fsr_rcas(const FsrArgs& A, hipStream_t st);
+
+// Present (hk_overlay.hip over include/hk_overlay.h): `in` and `albedo` (RGBA16F planes) drawn into the viewport of the
+// target at `data` (row pitch in bytes).  run: the 16-byte row-run kernel where the viewport's runs are aligned, with
+// the per-pixel kernel on each row's tail; otherwise the per-pixel kernel throughout.  col0 / cols: the launcher's.
+struct OverlayArgs {
+    hk_pp_tex in, albedo;
+    uint8_t* data;
+    uint32_t pitch;
+    hk_overlay_view view;
+    uint32_t col0, cols;  // the viewport columns one launch covers
+};
+void launch_overlay(const OverlayArgs& A, bool run, hipStream_t st);
 
 bool lane_stats_take(unsigned long long out[2 * LANE_SLOTS], hipStream_t st);
 void launch_gbuffer(const FrameArgs& A, const ViewArgs& V, uint2* albedo, uint32_t stack_need, hipStream_t st);

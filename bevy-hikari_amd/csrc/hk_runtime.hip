@@ -62,6 +62,7 @@ enum Opt {
     OPT_COMPACT_EMITTER,
     OPT_COMPACT_SHADOW,
     OPT_FSR_TILED,           // EASU with its input footprint staged in LDS (hk_fsr.hip)
+    OPT_PRESENT_RUN,         // hk_present stores 16-byte row runs where the viewport's runs are aligned (hk_overlay.hip)
     OPT_COUNT
 };
 struct OptDef {
@@ -78,6 +79,7 @@ constexpr OptDef OPTS[OPT_COUNT] = {
     {"gbuffer_lds_max_px", 6e5, 0.0, 1e12},
     {"direct_w4_min_px", 4e5, 0.0, 1e12},  {"fused_w4", 1, 0, 1},          {"persistent_indirect", 0, 0, 1},
     {"compact_emitter", 0, 0, 1},          {"compact_shadow", 0, 0, 1},    {"fsr_tiled", 1, 0, 1},
+    {"present_run", 1, 0, 1},
 };
 
 // One slot of the planes k_gbuffer double-buffers (hk_ctx::g / g_prev: swapped on each hk_render_gbuffer) so a
@@ -359,7 +361,9 @@ struct hk_ctx {
     uint32_t upscale_wh[2] = {0, 0}, taa_wh[2] = {0, 0};
     uint2* fsr_buf[2] = {};       // upscale_output[0..1] under FSR1 (EASU, RCAS), S
     float fsr_sharpness = 0.0f;   // Upscale::Fsr1::sharpness (hk_set_fsr1_sharpness)
-    float4* accum = nullptr;      // sub-frame accumulator (hk_accumulate), allocated on first use
+    uint8_t* present_buf = nullptr;  // the context's own present plane (hk_present with data == NULL), packed rows
+    uint32_t present_wh[2] = {0, 0}, present_format = 0;
+    float4* accum = nullptr;     // sub-frame accumulator (hk_accumulate), allocated on first use
     uint2* accum_out = nullptr;
     uint32_t accum_n = 0;
     // counters (top, emitter, primary)
@@ -521,6 +525,7 @@ std::vector<Target> targets(hk_ctx* c)
     add(c->upscale, 0);
     for (auto& b : c->taa_buf) add(b, 0);
     for (auto& b : c->fsr_buf) add(b, 0);
+    add(c->present_buf, 0);
     add(c->accum, 0);
     add(c->accum_out, 0);
     add(c->wf_queue1, 0);
@@ -537,6 +542,7 @@ void free_targets(hk_ctx* c)
     for (const Target& t : targets(c)) release(*t.ptr);
     c->bg_valid[0] = c->bg_valid[1] = c->gb_valid = false;
     c->upscale_wh[0] = c->upscale_wh[1] = c->taa_wh[0] = c->taa_wh[1] = 0;
+    c->present_wh[0] = c->present_wh[1] = 0;
     c->accum_n = 0;
     c->sch.reset();
     c->sized = false;
@@ -2221,6 +2227,109 @@ int hk_get_output(hk_ctx* c, int id, void* dst, size_t bytes, int to_host, void*
     hipStream_t st = pick(c, stream);
     HK_TRY(c->sch.gb_join(st));
     HK_HIP(c, hipMemcpyAsync(dst, p, bytes, to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+    if (to_host) HK_HIP(c, hipStreamSynchronize(st));
+    return HK_OK;
+}
+
+// The present pass (overlay.rs, overlay.wgsl; include/hk_overlay.h).  An "other" call like hk_post_process: on the
+// caller's stream after the G-buffer and tail joins, so the albedo and any input plane hold their final contents.
+// The albedo slot it reads is rewritten by the k_gbuffer after the next one; the next one, pipelined on gb_stream,
+// waits for ev_post (post_pending), the post-process readers' marker, and the one after follows it on that stream.
+static_assert(HK_PRESENT_RGBA8_SRGB == HK_OVERLAY_RGBA8_SRGB && HK_PRESENT_BGRA8_SRGB == HK_OVERLAY_BGRA8_SRGB &&
+                  HK_PRESENT_RGBA16F == HK_OVERLAY_RGBA16F, "hikari_amd.h and hk_overlay.h name the same formats");
+int hk_present(hk_ctx* c, const hk_settings* st, const hk_present_target* t, void* stream)
+{
+    int rc = check_ready(c, false);
+    if (rc) return rc;
+    if (!t) return fail(c, HK_ERR_INVALID, "null present target");
+    if (c->S_rows != (int32_t)c->S[1]) return fail(c, HK_ERR_STATE, "hk_present needs a whole-frame context");
+    if (t->format != HK_PRESENT_RGBA8_SRGB && t->format != HK_PRESENT_BGRA8_SRGB && t->format != HK_PRESENT_RGBA16F)
+        return fail(c, HK_ERR_INVALID, "unknown present format");
+    const uint32_t bpp = t->format == HK_PRESENT_RGBA16F ? 8u : 4u;
+    if (t->width == 0u || t->height == 0u) return fail(c, HK_ERR_INVALID, "present target with a zero dimension");
+    hk_overlay_view V;
+    V.format = t->format;
+    V.vx = t->vp_x, V.vy = t->vp_y, V.vw = t->vp_w, V.vh = t->vp_h;
+    if (t->vp_w == 0u) V.vx = V.vy = 0u, V.vw = t->width, V.vh = t->height;
+    if (V.vh == 0u) return fail(c, HK_ERR_INVALID, "present viewport with a zero dimension");
+    if ((uint64_t)V.vx + V.vw > t->width || (uint64_t)V.vy + V.vh > t->height)
+        return fail(c, HK_ERR_INVALID, "present viewport outside the target");
+    const uint64_t row_bytes = (uint64_t)t->width * bpp;
+    if (row_bytes > 0xFFFFFFFFull) return fail(c, HK_ERR_INVALID, "present target row above 4 GiB");
+    const uint32_t pitch = t->pitch ? t->pitch : (uint32_t)row_bytes;
+    if (pitch < row_bytes || pitch % bpp != 0u)
+        return fail(c, HK_ERR_INVALID, "present pitch below a row or not a multiple of the texel size");
+    if (t->data && (uintptr_t)t->data % bpp != 0u) return fail(c, HK_ERR_INVALID, "present target not aligned to the texel size");
+    if (!t->data && pitch != row_bytes) return fail(c, HK_ERR_INVALID, "the context's own present plane has packed rows (pitch 0)");
+    // the launch's one-dimensional grid of 64 x 4 pixel workgroups
+    if ((((uint64_t)V.vw + 63u) / 64u) * (((uint64_t)V.vh + 3u) / 4u) >= (1ull << 31))
+        return fail(c, HK_ERR_INVALID, "present viewport too large");
+    int id = t->input;
+    if (id == -1) {
+        // overlay.rs:227-231
+        if (!st) return fail(c, HK_ERR_INVALID, "null settings (present input -1 is chosen from them)");
+        id = st->upscale == 1u ? HK_OUT_FSR_RCAS : (st->taa == 0u ? HK_OUT_TAA : HK_OUT_UPSCALED);
+    }
+    switch (id) {
+    case HK_OUT_ALBEDO: case HK_OUT_RENDER_DIRECT: case HK_OUT_RENDER_EMISSIVE: case HK_OUT_RENDER_INDIRECT:
+    case HK_OUT_DENOISED_DIRECT: case HK_OUT_DENOISED_EMISSIVE: case HK_OUT_DENOISED_INDIRECT: case HK_OUT_TONE_MAPPED:
+    case HK_OUT_ACCUMULATED: case HK_OUT_UPSCALED: case HK_OUT_TAA: case HK_OUT_TONE_MAPPED_PREVIOUS: case HK_OUT_FSR_EASU:
+    case HK_OUT_FSR_RCAS: break;
+    default: return fail(c, HK_ERR_INVALID, "present input is not an RGBA16F output plane");
+    }
+    uint32_t iw = 0, ih = 0;
+    const void* in = output_ptr(c, id, &iw, &ih, nullptr);
+    if (!in || iw == 0u || ih == 0u) return fail(c, HK_ERR_STATE, "present input plane not produced yet (hk_post_process)");
+    if ((uint64_t)iw * ih >= (1ull << 31)) return fail(c, HK_ERR_INVALID, "present input above 2^31 texels");
+    (void)hipSetDevice(c->device);
+    hipStream_t s = pick(c, stream);
+    HK_TRY(c->sch.gb_join(s));
+    uint8_t* data = (uint8_t*)t->data;
+    if (!data) {
+        if (!c->present_buf || c->present_wh[0] != t->width || c->present_wh[1] != t->height || c->present_format != t->format) {
+            release(c->present_buf);
+            c->present_wh[0] = c->present_wh[1] = 0;
+            HK_HIP(c, hipMalloc(&c->present_buf, (size_t)pitch * t->height));
+            HK_HIP(c, hipMemset(c->present_buf, 0, (size_t)pitch * t->height));
+            c->present_wh[0] = t->width, c->present_wh[1] = t->height, c->present_format = t->format;
+        }
+        data = c->present_buf;
+    }
+    OverlayArgs A;
+    A.in.data = in, A.in.w = iw, A.in.h = ih, A.in.f16 = 1, A.in.comps = 4;
+    A.albedo.data = c->g.albedo, A.albedo.w = c->S[0], A.albedo.h = c->S[1], A.albedo.f16 = 1, A.albedo.comps = 4;
+    A.data = data, A.pitch = pitch, A.view = V, A.col0 = 0u, A.cols = V.vw;
+    const bool run = c->on(OPT_PRESENT_RUN);
+    timed(c, "present", s, [&] { launch_overlay(A, run, s); });
+    // one marker for every post-process reader: it now also stands after the earlier ones
+    if (c->sch.post_pending) HK_HIP(c, hipStreamWaitEvent(s, c->sch.ev_post, 0));
+    HK_HIP(c, hipEventRecord(c->sch.ev_post, s));
+    c->sch.post_pending = true;
+    HK_HIP(c, hipGetLastError());
+    return HK_OK;
+}
+
+int hk_present_info(const hk_ctx* c, uint32_t* w, uint32_t* h, uint32_t* bytes_per_texel, uint32_t* format)
+{
+    if (!c) return HK_ERR_INVALID;
+    if (!c->present_buf || c->present_wh[0] == 0u) return HK_ERR_STATE;
+    if (w) *w = c->present_wh[0];
+    if (h) *h = c->present_wh[1];
+    if (bytes_per_texel) *bytes_per_texel = c->present_format == HK_PRESENT_RGBA16F ? 8u : 4u;
+    if (format) *format = c->present_format;
+    return HK_OK;
+}
+
+int hk_get_present(hk_ctx* c, void* dst, size_t bytes, int to_host, void* stream)
+{
+    if (!c || !dst) return HK_ERR_INVALID;
+    if (!c->present_buf || c->present_wh[0] == 0u)
+        return fail(c, HK_ERR_STATE, "no present plane yet (hk_present with data == NULL)");
+    const size_t need = (size_t)c->present_wh[0] * c->present_wh[1] * (c->present_format == HK_PRESENT_RGBA16F ? 8u : 4u);
+    if (bytes != need) return fail(c, HK_ERR_INVALID, "present plane size mismatch");
+    (void)hipSetDevice(c->device);
+    hipStream_t st = pick(c, stream);  // the plane was written on hk_present's stream: stream order
+    HK_HIP(c, hipMemcpyAsync(dst, c->present_buf, bytes, to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
     if (to_host) HK_HIP(c, hipStreamSynchronize(st));
     return HK_OK;
 }

@@ -9,10 +9,10 @@ from .plugin import (HikariPlugin, HikariRenderer, PLAN_GBUFFER, PLAN_LIGHT, RES
                      scene_stage_bytes)
 from .scene import (AmbientLight, Camera, DirectionalLight, Mesh, Scene, StandardMaterial, Texture, Transform,
                     frame_inputs, jitter_mode, load_glb, load_noise, make_lights, plane_mesh, texture_array, uv_sphere_mesh)
-from .settings import HikariSettings, HikariUniversalSettings, Taa, Upscale
+from .settings import HikariSettings, HikariUniversalSettings, PresentFormat, Taa, Upscale
 
 __all__ = [
     "HikariError", "HikariPlugin", "HikariRenderer", "RESERVOIR_DTYPE", "AmbientLight", "Camera", "DirectionalLight",
     "Mesh", "Scene", "StandardMaterial", "Texture", "texture_array", "Transform", "frame_inputs", "jitter_mode", "load_glb", "load_noise", "make_lights",
-    "plane_mesh", "uv_sphere_mesh", "scene_stage_bytes", "scene_gbuffer_stack", "PLAN_LIGHT", "PLAN_GBUFFER", "HikariSettings", "HikariUniversalSettings", "Taa", "Upscale", "_abi",
+    "plane_mesh", "uv_sphere_mesh", "scene_stage_bytes", "scene_gbuffer_stack", "PLAN_LIGHT", "PLAN_GBUFFER", "HikariSettings", "HikariUniversalSettings", "PresentFormat", "Taa", "Upscale", "_abi",
 ]

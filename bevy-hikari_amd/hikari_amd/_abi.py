@@ -110,6 +110,16 @@ class hk_frame_inputs(C.Structure):
                 ("previous_view_proj", C.c_float * 16)]
 
 
+PRESENT_RGBA8_SRGB, PRESENT_BGRA8_SRGB, PRESENT_RGBA16F = 0, 1, 2
+
+
+class hk_present_target(C.Structure):
+    """include/hikari_amd.h hk_present_target (the view target of hk_present)."""
+    _fields_ = [("data", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("pitch", C.c_uint32),
+                ("format", C.c_uint32), ("vp_x", C.c_uint32), ("vp_y", C.c_uint32), ("vp_w", C.c_uint32),
+                ("vp_h", C.c_uint32), ("input", C.c_int32)]
+
+
 class hk_counters(C.Structure):
     _fields_ = [("traverse_top", C.c_uint64), ("traverse_emitter", C.c_uint64), ("primary", C.c_uint64),
                 ("primary_reused", C.c_uint64)]
@@ -169,6 +179,9 @@ def lib() -> C.CDLL:
         "hk_accumulate": (i32, [vp, i32, vp]),
         "hk_post_process": (i32, [vp, C.POINTER(hk_settings), C.POINTER(hk_frame_inputs), vp]),
         "hk_set_fsr1_sharpness": (i32, [vp, C.c_float]),
+        "hk_present": (i32, [vp, C.POINTER(hk_settings), C.POINTER(hk_present_target), vp]),
+        "hk_present_info": (i32, [vp] + [C.POINTER(u32)] * 4),
+        "hk_get_present": (i32, [vp, vp, C.c_size_t, i32, vp]),
         "hk_update_instances": (i32, [vp, vp, vp, u32, vp]),
         "hk_read_scene_array": (i32, [vp, i32, vp, C.c_size_t]),
         "hk_resolve_accumulation": (i32, [vp, vp]),
@@ -211,7 +224,7 @@ EXPORTED_SYMBOLS = [
     "hk_abi_version", "hk_create", "hk_destroy", "hk_last_error", "hk_settings_default", "hk_set_option",
     "hk_get_option", "hk_option_name", "hk_scene_upload", "hk_scene_stage_bytes", "hk_scene_gbuffer_stack",
     "hk_set_noise", "hk_texture_upload", "hk_resize", "hk_resize_striped", "hk_set_band_halo", "hk_band_info", "hk_band_window_grow", "hk_reservoir_rows", "hk_resize_tile", "hk_tile_info", "hk_copy_output_rect", "hk_copy_output_rows", "hk_render_gbuffer", "hk_set_gbuffer_plane", "hk_render_frame",
-    "hk_denoise", "hk_tone_sum", "hk_update_instances", "hk_read_scene_array", "hk_post_process", "hk_set_fsr1_sharpness", "hk_accumulate", "hk_resolve_accumulation", "hk_output_info", "hk_get_output", "hk_output_device_ptr", "hk_sync", "hk_set_wavefront", "hk_lane_stats", "hk_dump_reservoirs",
+    "hk_denoise", "hk_tone_sum", "hk_update_instances", "hk_read_scene_array", "hk_post_process", "hk_set_fsr1_sharpness", "hk_present", "hk_present_info", "hk_get_present", "hk_accumulate", "hk_resolve_accumulation", "hk_output_info", "hk_get_output", "hk_output_device_ptr", "hk_sync", "hk_set_wavefront", "hk_lane_stats", "hk_dump_reservoirs",
     "hk_load_reservoirs", "hk_reset_counters", "hk_read_counters", "hk_enable_kernel_timing", "hk_kernel_timing", "hk_set_kernel_timing_interval",
     "hk_trace", "hk_selftest_f16", "hk_selftest_div", "hk_selftest_rcp", "hks_create", "hks_destroy", "hks_last_error", "hks_add_mesh", "hks_add_material",
     "hks_add_instance", "hks_build", "hks_get_desc",

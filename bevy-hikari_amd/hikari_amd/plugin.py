@@ -5,7 +5,8 @@ The reference's per-frame render-graph work for a `hikari` camera is
     LightNode::run (light.rs:590-702)                  -> render_frame()
     PostProcessNode::run denoise block (post_process.rs:1190-1224) -> denoise()
     tone_mapping dispatch (post_process.rs:1226-1234)  -> tone_sum()
-`HikariPlugin.frame()` runs them in that order, like the `hikari` sub-graph (lib.rs:238-367).
+`HikariPlugin.frame()` runs them in that order, like the `hikari` sub-graph (lib.rs:238-367).  After the renderer's
+post_process(), `present()` is the `Overlay` phase item's draw into the view target (overlay.rs, overlay.wgsl).
 """
 from __future__ import annotations
 
@@ -16,7 +17,7 @@ import numpy as np
 
 from . import _abi
 from .scene import Scene, load_noise, texture_array
-from .settings import HikariSettings, HikariUniversalSettings
+from .settings import HikariSettings, HikariUniversalSettings, PresentFormat
 
 RESERVOIR_DTYPE = np.dtype([("radiance", "<u4", 2), ("random", "<u4", 2), ("visible_position", "<f4", 4),
                             ("sample_position", "<f4", 4), ("visible_normal", "<u4"), ("sample_normal", "<u4"),
@@ -234,6 +235,37 @@ class HikariRenderer:
         """`Upscale::Fsr1 { sharpness }` for the following post_process calls (hk_set_fsr1_sharpness)."""
         _check(self.ctx, self._L.hk_set_fsr1_sharpness(self.ctx, float(sharpness)), "hk_set_fsr1_sharpness")
 
+    def present(self, settings, width: int, height: int, format="rgba8_srgb", viewport=None, input: int = -1,
+                dst_ptr: Optional[int] = None, pitch: int = 0, stream=None):
+        """The overlay's draw (hk_present): the displayed plane (input -1: chosen from `settings` as overlay.rs:227-231
+        does; else an RGBA16F output id) into `viewport` = (x, y, w, h) (None: all) of a width x height target of
+        `format` (a PresentFormat, its number or its lower-case name).  dst_ptr None: the context's own present plane,
+        returned as an (height, width, 4) array, uint8 for the 8-bit formats and uint16 (f16 bits) for RGBA16F;
+        otherwise device memory of the caller's with row pitch `pitch` bytes (0: packed), and None is returned.
+        `settings`: an hk_settings record, or None with an explicit input."""
+        t = _abi.hk_present_target()
+        t.data, t.width, t.height, t.pitch = dst_ptr, int(width), int(height), int(pitch)
+        t.format = int(PresentFormat.of(format))
+        t.vp_x, t.vp_y, t.vp_w, t.vp_h = (0, 0, 0, 0) if viewport is None else [int(v) for v in viewport]
+        t.input = int(input)
+        _check(self.ctx, self._L.hk_present(self.ctx, None if settings is None else C.byref(settings), C.byref(t),
+                                            _stream(stream)), "hk_present")
+        return self.get_present(stream) if dst_ptr is None else None
+
+    def present_info(self):
+        """(width, height, bytes per texel, PresentFormat) of the context's own present plane."""
+        v = [C.c_uint32() for _ in range(4)]
+        _check(self.ctx, self._L.hk_present_info(self.ctx, *[C.byref(x) for x in v]), "hk_present_info")
+        return v[0].value, v[1].value, v[2].value, PresentFormat(v[3].value)
+
+    def get_present(self, stream=None) -> np.ndarray:
+        """The context's own present plane as (height, width, 4) uint8, or uint16 for RGBA16F (hk_get_present)."""
+        w, h, b, _ = self.present_info()
+        out = np.empty((h, w, 4), np.uint8 if b == 4 else np.uint16)
+        _check(self.ctx, self._L.hk_get_present(self.ctx, out.ctypes.data, out.nbytes, 1, _stream(stream)),
+               "hk_get_present")
+        return out
+
     def accumulate(self, reset: bool = False, stream=None) -> None:
         """Add the tone-mapped output to the sub-frame accumulator (hk_accumulate)."""
         _check(self.ctx, self._L.hk_accumulate(self.ctx, int(reset), _stream(stream)), "hk_accumulate")
@@ -394,3 +426,12 @@ class HikariPlugin:
             r.denoise(s, fi, stream)
         r.tone_sum(s, stream)
         self.frame_number += 1
+
+    def present(self, width: int = None, height: int = None, hdr: bool = False, viewport=None, stream=None):
+        """The `Overlay` draw into a window-sized view target (overlay.rs:333-395): the plane the settings display,
+        into `viewport` (camera.viewport; None: the whole target) of a target of width x height (default: the
+        physical size, as a window's) — Rgba8UnormSrgb, or Rgba16Float when the view is `hdr`.  Returns the target as
+        an (height, width, 4) array (HikariRenderer.present)."""
+        r = self.renderer
+        return r.present(self.settings.to_c(), r.width if width is None else width, r.height if height is None else height,
+                         PresentFormat.RGBA16F if hdr else PresentFormat.RGBA8_SRGB, viewport, stream=stream)

@@ -45,6 +45,22 @@ Upscale.SMAA_TU_1_0 = Upscale.smaa_tu4x(1.0)
 Upscale.SMAA_TU_2_0 = Upscale.smaa_tu4x(2.0)
 
 
+class PresentFormat(enum.IntEnum):
+    """The view target's texture format (hk_present_target.format): `TextureFormat::bevy_default()` is
+    Rgba8UnormSrgb or Bgra8UnormSrgb by platform, `ViewTarget::TEXTURE_FORMAT_HDR` is Rgba16Float (overlay.rs:111-116)."""
+
+    RGBA8_SRGB = 0
+    BGRA8_SRGB = 1
+    RGBA16F = 2
+
+    @staticmethod
+    def of(value) -> "PresentFormat":
+        """A PresentFormat, its number, or its name in lower case ("rgba8_srgb", "bgra8_srgb", "rgba16f")."""
+        if isinstance(value, str):
+            return PresentFormat[value.upper()]
+        return PresentFormat(value)
+
+
 def srgb_to_linear(c: float) -> float:
     """Bevy `Color::rgb` is sRGB; conversion used by `as_linear_rgba_f32`."""
     return c / 12.92 if c <= 0.04045 else ((c + 0.055) / 1.055) ** 2.4

@@ -23,6 +23,7 @@
  *                               temporal pass and (if enabled) the spatial pass
  *   hk_denoise                  the denoise block of `PostProcessNode::run` (post_process.rs:1190-1224)
  *   hk_tone_sum                 the `tone_mapping` dispatch (post_process.rs:1226-1234)
+ *   hk_present                  the `Overlay` phase item's draw into the view target (overlay.rs:290-395, overlay.wgsl)
  *   hk_get_output               reading `LightTextures` / `denoise_render` / tone-mapping output
  *   hk_trace                    stand-alone ray query over the TLAS/BLAS (light.wgsl:442-486)
  *
@@ -232,6 +233,9 @@ void hk_settings_default(hk_settings* out);
  *                            (both measured slower than the per-pixel walks: DESIGN §4)
  *   fsr_tiled (1)            FSR1 EASU with each workgroup's input footprint staged in LDS as f32 (0: every tap from
  *                            global memory); tests force both variants with it
+ *   present_run (1)        hk_present stores 16-byte row runs (4 texels, RGBA16F 2) where the viewport's first texel
+ *                            and the pitch are 16-byte aligned, each row's tail per texel (0: every texel on its own);
+ *                            tests force both variants with it
  * hk_set_option returns HK_ERR_INVALID for an unknown key, a value outside the key's range, or a fractional value
  * for any key but the pixel-count thresholds (*_px). */
 int hk_set_option(hk_ctx* ctx, const char* key, double value);
@@ -278,6 +282,39 @@ int hk_post_process(hk_ctx* ctx, const hk_settings* settings, const hk_frame_inp
  * sharpness; RCAS scales its lobe by exp2(-sharpness).  Not clamped, as the reference does not; a non-finite value
  * returns HK_ERR_INVALID.  Takes effect at the next hk_post_process. */
 int hk_set_fsr1_sharpness(hk_ctx* ctx, float sharpness);
+
+/* Present: the reference's last stage, the `Overlay` phase item's draw (overlay.rs, overlay.wgsl; include/hk_overlay.h
+ * states every step).  The displayed plane is drawn through the linear sampler into the camera's viewport of a view
+ * target: Rgba8UnormSrgb / Bgra8UnormSrgb, or Rgba16Float under HDR, which also undoes tone_mapping.wgsl's Reinhard
+ * curve (overlay.rs:111-116).  A texel whose sample holds a NaN takes the albedo's sample instead (HK_OUT_ALBEDO, at S).
+ * Texels outside the viewport are not written.
+ * input -1 chooses the plane as overlay.rs:227-231 does from `settings`: Fsr1 -> HK_OUT_FSR_RCAS, SmaaTu4x with
+ * Taa::None -> HK_OUT_UPSCALED, SmaaTu4x with Jasmine -> HK_OUT_TAA; another RGBA16F HK_OUT_* id shows that plane
+ * (debug views; `settings` may then be NULL).
+ * Errors: HK_ERR_STATE when the input plane does not exist yet (no hk_post_process that produces it) or the context
+ * is a band; HK_ERR_INVALID for an unknown format, an input that is not RGBA16F, a zero dimension, a viewport outside
+ * the target, a pitch below a row or not a multiple of the texel size, `data` not aligned to the texel size, or a
+ * pitch with data == NULL (the context's plane has packed rows).  A failed call launches nothing.
+ * Ordering: like hk_post_process, the call runs on `stream` after the frame's G-buffer and tail (device-side waits),
+ * and the following hk_render_gbuffer calls wait for it before they overwrite the albedo slot it reads; a
+ * caller-owned target is the caller's to order: it is written on `stream`, in stream order. */
+enum { HK_PRESENT_RGBA8_SRGB = 0, HK_PRESENT_BGRA8_SRGB = 1, HK_PRESENT_RGBA16F = 2 };
+typedef struct hk_present_target {
+    void*    data;            /* device memory; NULL: the context's own present plane */
+    uint32_t width, height;   /* texels of the whole target */
+    uint32_t pitch;           /* bytes per row; 0 = width * bytes per texel */
+    uint32_t format;          /* HK_PRESENT_* */
+    uint32_t vp_x, vp_y, vp_w, vp_h;  /* camera.viewport; vp_w == 0: the whole target */
+    int32_t  input;           /* -1: overlay.rs:227-231's choice; else an RGBA16F HK_OUT_* id */
+} hk_present_target;
+int hk_present(hk_ctx* ctx, const hk_settings* settings, const hk_present_target* target, void* stream);
+/* The context's own present plane (hk_present with data == NULL): allocated by the first such call, reallocated when
+ * the size or the format changes, released by hk_resize; both return HK_ERR_STATE before it exists.  It is
+ * deliberately not an HK_OUT_* id: its texel size and format follow the last call.  hk_get_present copies all of it
+ * (bytes = width * height * bytes per texel, rows packed) on `stream`, in stream order after the hk_present that
+ * wrote it; to_host != 0 waits for the copy. */
+int hk_present_info(const hk_ctx* ctx, uint32_t* width, uint32_t* height, uint32_t* bytes_per_texel, uint32_t* format);
+int hk_get_present(hk_ctx* ctx, void* dst, size_t bytes, int to_host, void* stream);
 
 /* Sub-frame accumulation (N integrator sub-frames per displayed frame, each
  * exactly one reference frame): hk_accumulate adds the current tone-mapped output (HK_OUT_TONE_MAPPED)
@@ -379,7 +416,9 @@ int hk_get_output(hk_ctx* ctx, int output_id, void* dst, size_t bytes, int to_ho
  * hk_sync(ctx, stream) (the frame's G-buffer and tail may still run on the context's own streams).
  * The planes are read-only for the caller: the light passes skip background stores whose targets
  * already hold their constant words (background store elision), which a foreign write would break;
- * planes and reservoirs are written through hk_set_gbuffer_plane / hk_load_reservoirs only. */
+ * planes and reservoirs are written through hk_set_gbuffer_plane / hk_load_reservoirs only.
+ * hk_present follows the same rule from the inside: it reads the albedo and its input plane on `stream` after the
+ * context's own streams (the waits of hk_sync), and the next hk_render_gbuffer waits for it. */
 const void* hk_output_device_ptr(hk_ctx* ctx, int output_id);
 /* Make `stream` wait (device-side) for all work the context queued on its own streams. */
 int hk_sync(hk_ctx* ctx, void* stream);
