@@ -152,6 +152,8 @@ struct Scene {
 // traversal kernel, so each dependent node / triangle / instance load of a walk is an LDS read
 // (~50 cycles) instead of an L2 hit (~200).  A plan lists the arrays a kernel reads.
 constexpr uint32_t LDS_SCENE_MAX = 32768;
+// what one workgroup may allocate, static and dynamic together (64 KiB of a gfx950 CU's 160 KiB)
+constexpr uint32_t LDS_WORKGROUP_MAX = 65536;
 enum : int { PLAN_LIGHT = 0, PLAN_GBUFFER = 1 };
 __host__ __device__ constexpr bool plan_has(int plan, int k)
 {
@@ -955,6 +957,11 @@ struct LaneStats {
 // nodes — p + 1, p + 2, ... too, from consecutive node loads.  At most one of them is a leaf,
 // whose work (triangle test / instance entry) then follows.  Same visits, tests and results as
 // one node per iteration (WALK_STEPS 2: cornell 1080p 0.619 -> 0.604 ms/frame).
+// ANY_HIT false is the closest-hit query (max_distance F32_MAX, early_distance 0, nothing excluded: the bounce
+// walks): intersects_triangle returns a distance > F32_EPSILON or F32_MAX, so no hit is nearer than an early
+// distance of 0 and neither early exit can be taken, and no instance index equals DONT_EXCLUDE; the loop then
+// carries no stop flag, no early-distance compares and no exclude compare.  Same visits and results.
+template <bool ANY_HIT = true>
 HKD Hit traverse_top(const Scene& sc, const Ray& ray, float max_distance, float early_distance, uint32_t exclude)
 {
     Hit hit;
@@ -993,7 +1000,7 @@ HKD Hit traverse_top(const Scene& sc, const Ray& ray, float max_distance, float 
                     hit.uv = uv;
                     hit.primitive_index = primitive_index;
                     intersected = true;
-                    stop = d < early_distance;  // traverse_bottom's early return
+                    if constexpr (ANY_HIT) stop = d < early_distance;  // traverse_bottom's early return
                 }
             }
             if (stop || index >= count) {  // back in traverse_top after traverse_bottom
@@ -1004,12 +1011,14 @@ HKD Hit traverse_top(const Scene& sc, const Ray& ray, float max_distance, float 
                 tr = ray;
                 if (intersected) {
                     hit.instance_index = cur_instance;
-                    if (hit.distance < early_distance) return hit;
+                    if constexpr (ANY_HIT) {
+                        if (hit.distance < early_distance) return hit;
+                    }
                 }
             }
         } else {
             const uint32_t instance_index = leaf_entry - HK_BVH_LEAF_FLAG;
-            if (leaf_pass && instance_index != exclude) {
+            if (leaf_pass && (!ANY_HIT || instance_index != exclude)) {
                 const hk_instance& in = sc.instances[instance_index];
                 const uint32_t bot_count = in.mesh.node[1];
                 prim_offset = in.mesh.primitive;
@@ -1029,6 +1038,11 @@ HKD Hit traverse_top(const Scene& sc, const Ray& ray, float max_distance, float 
         }
     }
     return hit;
+}
+// the closest hit along a ray (light.wgsl's traverse_top(ray, F32_MAX, 0.0)): the bounce walks
+HKD Hit traverse_top_closest(const Scene& sc, const Ray& ray)
+{
+    return traverse_top<false>(sc, ray, HK_F32_MAX, 0.0f, DONT_EXCLUDE);
 }
 
 // ------------------------------------------------------------------ G-buffer visibility
@@ -1625,11 +1639,24 @@ HKD f4 noise_random(const uchar4* noise, uint32_t number, int32_t x, int32_t y)
 // serialise tens of thousands of same-address atomics per kernel at the memory side.
 constexpr uint32_t COUNTER_SHARDS = 1024;
 constexpr uint32_t COUNTER_STRIDE = 8;  // u64 per shard line (64 B)
+// The wave's sum without cross-lane permutes: a wave that counted nothing (most of a frame's: the all-background
+// waves) leaves on one ballot; per-lane counts are small, so the sum is taken by bit planes (the lanes that have
+// bit b set, counted on the scalar unit, times 2^b) over the low WAVE_COUNT_PLANES bits, and only a wave in which
+// some lane counted 2^WAVE_COUNT_PLANES or more runs the shuffle tree.  Integer sums: the same totals either way.
+constexpr int WAVE_COUNT_PLANES = 4;
 HKD void wave_count(unsigned long long* dst, uint32_t v)
 {
-    unsigned long long s = v;
+    if (__ballot(v != 0u) == 0ull) return;
+    unsigned long long s;
+    if (__ballot(v >> WAVE_COUNT_PLANES) == 0ull) {
+        s = 0ull;
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        for (int b = 0; b < WAVE_COUNT_PLANES; b++) s += (unsigned long long)__popcll(__ballot((v >> b) & 1u)) << b;
+    } else {
+        s = v;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    }
     uint32_t shard = ((blockIdx.x + blockIdx.y * gridDim.x) * 4u + (threadIdx.x >> 6)) % COUNTER_SHARDS;
     if ((threadIdx.x & 63) == 0 && s) atomicAdd(dst + (size_t)shard * COUNTER_STRIDE, s);
 }

@@ -726,6 +726,7 @@ HKD void store_background_pair(const ChannelArgs& C, int32_t idx)
 HKD void finish_counts(const FrameArgs& A, int32_t x, int32_t y, uint32_t n_top, uint32_t n_emitter)
 {
     if (!counted(A.F, x, y)) n_top = n_emitter = 0;
+    if (__ballot((n_top | n_emitter) != 0u) == 0ull) return;  // a wave without walks (all background): one test for both
     wave_count(A.cnt.top, n_top);
     wave_count(A.cnt.emitter, n_emitter);
 }
@@ -1230,7 +1231,7 @@ HKD float indirect_multi_bounces(const Scene& sc, const Frame& F, Sample& s, uin
         Ray& ray = B.ray;
         HitInfo& info = B.info;
         n_top++;
-        Hit hit = traverse_top(sc, ray, HK_F32_MAX, 0.0f, DONT_EXCLUDE);
+        Hit hit = traverse_top_closest(sc, ray);
         info = hit_info(sc, ray, hit);
         if (n == 0u) {
             s.sample_position = info.position;
@@ -1351,7 +1352,7 @@ HKD bool indirect_begin(const FrameArgs& A, const Scene& sc, const ChannelArgs& 
             hit = wf_load_hit(*W, idx);
         } else {
             n_top++;
-            hit = traverse_top(sc, B.ray, HK_F32_MAX, 0.0f, DONT_EXCLUDE);
+            hit = traverse_top_closest(sc, B.ray);
         }
         if constexpr (STAGE == IND_TRACE) {
             wf_store_hit(*W, idx, hit);
@@ -2717,6 +2718,9 @@ void launch_indirect(const FrameArgs& A, const ChannelArgs& C, bool multi, hipSt
         },
         lds != 0u);
 }
+uint32_t indirect_stash_bytes() { return (uint32_t)sizeof(IndStash); }
+// the largest staged scene with the stash behind it is within a workgroup's LDS (k_indirect, k_light_merged)
+static_assert(LDS_SCENE_MAX + sizeof(IndStash) <= LDS_WORKGROUP_MAX, "staged scene + stash exceed a workgroup's LDS");
 bool light_lds_direct(const FrameArgs& A) { return lds_plan_bytes(A, PLAN_LIGHT, false) != 0u; }
 void launch_light_merged(const FrameArgs& A, const ChannelArgs& C0, const ChannelArgs& C1, const ChannelArgs& C2,
                          hipStream_t st)
@@ -2979,6 +2983,16 @@ __global__ __launch_bounds__(256) void k_rcp_check(uint32_t lo, uint32_t hi, uns
 void launch_rcp_check(uint32_t lo, uint32_t hi, unsigned long long* bad, hipStream_t st)
 {
     hipLaunchKernelGGL(k_rcp_check, dim3(8192), dim3(256), 0, st, lo, hi, bad);
+}
+// wave_count on given per-thread counts (a thread past n counts nothing)
+__global__ __launch_bounds__(256) void k_count_check(const uint32_t* values, uint32_t n, unsigned long long* sum)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    wave_count(sum, i < n ? values[i] : 0u);
+}
+void launch_count_check(const uint32_t* values, uint32_t n, unsigned long long* sum, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_count_check, dim3((n + 255u) / 256u), dim3(256), 0, st, values, n, sum);
 }
 
 __global__ __launch_bounds__(256) void k_f16(const float* in, uint32_t n, uint16_t* out)

@@ -186,6 +186,8 @@ void launch_direct_fused(const FrameArgs& A, const ChannelArgs& C0, const Channe
 void launch_albedo(const FrameArgs& A, uint2* albedo, hipStream_t st);
 void launch_direct(const FrameArgs& A, const ChannelArgs& C, bool emissive_lit, hipStream_t st);
 void launch_indirect(const FrameArgs& A, const ChannelArgs& C, bool multi, hipStream_t st);
+// the indirect pass's pixel stash per workgroup (IndStash: static in k_indirect, behind the scene in k_light_merged)
+uint32_t indirect_stash_bytes();
 // the wavefront indirect pass (one bounce): gen + compaction, bounce trace, bin scan, scatter by
 // material, material-sorted shade; W.ctl must be zeroed on `st` before
 void launch_indirect_wavefront(const FrameArgs& A, const ChannelArgs& C, const WfArgs& W, hipStream_t st);
@@ -208,6 +210,7 @@ void launch_accumulate(const uint2* tone, float4* acc, uint32_t n, int reset, hi
 void launch_resolve(const float4* acc, uint32_t n, float count, uint2* out, hipStream_t st);
 void launch_div_check(float d, float r, uint32_t lo, uint32_t hi, unsigned long long* bad, hipStream_t st);
 void launch_rcp_check(uint32_t lo, uint32_t hi, unsigned long long* bad, hipStream_t st);
+void launch_count_check(const uint32_t* values, uint32_t n, unsigned long long* sum, hipStream_t st);
 void launch_f16(const float* in, uint32_t n, uint16_t* out, hipStream_t st);
 void launch_trace(const Scene& sc, const float* rays, const float* max_d, const float* early_d, const uint32_t* excl,
                   uint32_t n, uint32_t* hits, unsigned long long* top, hipStream_t st);

@@ -1109,6 +1109,19 @@ int hk_scene_stage_bytes(const hk_scene_desc* d, int plan, uint32_t* bytes, uint
     return HK_OK;
 }
 
+int hk_scene_indirect_lds(const hk_scene_desc* d, uint32_t* stash, uint32_t* total, uint32_t* limit)
+{
+    uint32_t scene = 0;
+    const int rc = hk_scene_stage_bytes(d, PLAN_LIGHT, &scene, nullptr);
+    if (rc != HK_OK) return rc;
+    const bool staged = scene <= LDS_SCENE_MAX;
+    const uint32_t s = indirect_stash_bytes();
+    if (stash) *stash = s;
+    if (total) *total = (staged ? scene : 0u) + s;
+    if (limit) *limit = LDS_WORKGROUP_MAX;
+    return HK_OK;
+}
+
 int hk_scene_gbuffer_stack(const hk_scene_desc* d, uint32_t* need, uint32_t* lds_levels)
 {
     if (!d || !scene_desc_ok(d)) return HK_ERR_INVALID;
@@ -2665,6 +2678,33 @@ int hk_selftest_rcp(hk_ctx* c, uint32_t lo, uint32_t hi, uint64_t* mismatches)
     uint64_t total = 0;
     for (size_t k = 0; k < h.size(); k += COUNTER_STRIDE) total += h[k];
     *mismatches = total;
+    return HK_OK;
+}
+
+int hk_selftest_count(hk_ctx* c, const uint32_t* values, uint32_t n, uint64_t* sum)
+{
+    if (!c || !sum || (n && !values)) return HK_ERR_INVALID;
+    *sum = 0;
+    if (n == 0) return HK_OK;
+    (void)hipSetDevice(c->device);
+    hipStream_t st = pick(c, nullptr);
+    uint32_t* d_in = nullptr;
+    unsigned long long* d_sum = nullptr;
+    const size_t bytes = (size_t)COUNTER_SHARDS * COUNTER_STRIDE * 8;
+    HK_HIP(c, hipMalloc(&d_in, (size_t)n * 4));
+    HK_HIP(c, hipMalloc(&d_sum, bytes));
+    HK_HIP(c, hipMemcpy(d_in, values, (size_t)n * 4, hipMemcpyHostToDevice));
+    HK_HIP(c, hipMemsetAsync(d_sum, 0, bytes, st));
+    launch_count_check(d_in, n, d_sum, st);
+    HK_HIP(c, hipGetLastError());
+    std::vector<unsigned long long> h(bytes / 8);
+    HK_HIP(c, hipMemcpyAsync(h.data(), d_sum, bytes, hipMemcpyDeviceToHost, st));
+    HK_HIP(c, hipStreamSynchronize(st));
+    release(d_in);
+    release(d_sum);
+    uint64_t total = 0;
+    for (size_t k = 0; k < h.size(); k += COUNTER_STRIDE) total += h[k];
+    *sum = total;
     return HK_OK;
 }
 

@@ -54,6 +54,16 @@ def scene_stage_bytes(scene, plan: int):
     return b.value, lim.value
 
 
+def scene_indirect_lds(scene):
+    """(stash, total, limit) of hk_scene_indirect_lds: the indirect pass's stash bytes per workgroup, stash plus the
+    scene's staged bytes (none past the staging limit), and what one workgroup may allocate.  Host arithmetic only."""
+    desc = scene if isinstance(scene, _abi.hk_scene_desc) else (scene.desc if scene.desc is not None else scene.build())
+    s, t, lim = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _check(None, _abi.lib().hk_scene_indirect_lds(C.byref(desc), C.byref(s), C.byref(t), C.byref(lim)),
+           "hk_scene_indirect_lds")
+    return s.value, t.value, lim.value
+
+
 def scene_gbuffer_stack(scene):
     """(need, lds_levels) of hk_scene_gbuffer_stack: the G-buffer walk's stack bound for this scene as
     hk_scene_upload computes it, and the levels the shallow walk keeps in LDS."""
@@ -372,6 +382,13 @@ class HikariRenderer:
         """f32 bit patterns in [lo, hi) (both signs) where the kernels' rcp_exact(x) != 1 / x."""
         n = C.c_uint64()
         _check(self.ctx, self._L.hk_selftest_rcp(self.ctx, lo, hi, C.byref(n)), "hk_selftest_rcp")
+        return n.value
+
+    def selftest_count(self, values: np.ndarray) -> int:
+        """The kernels' ray-counter reduction (wave_count) over per-thread counts `values` (uint32): their total."""
+        v = np.ascontiguousarray(values, np.uint32)
+        n = C.c_uint64()
+        _check(self.ctx, self._L.hk_selftest_count(self.ctx, v.ctypes.data, len(v), C.byref(n)), "hk_selftest_count")
         return n.value
 
     def selftest_div(self, divisor: float, lo: int, hi: int) -> int:

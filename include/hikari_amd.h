@@ -261,6 +261,10 @@ int hk_update_instances(hk_ctx* ctx, const float* models, const float* local_aab
  * walk's vertices, primitives, instances and the two wide node layouts) copy into LDS, each array rounded up to
  * 16 bytes, and the limit up to which a scene is staged at all (option lds_scene).  bytes <= limit: staged. */
 int hk_scene_stage_bytes(const hk_scene_desc* scene, int plan, uint32_t* bytes, uint32_t* limit);
+/* The indirect pass's LDS per workgroup for a scene under the default staging (host arithmetic, no device): the
+ * bytes of its per-pixel stash (68 per thread), stash plus staged scene (the stash alone for a scene past the
+ * staging limit), and what one workgroup may allocate.  total <= limit for every scene. */
+int hk_scene_indirect_lds(const hk_scene_desc* scene, uint32_t* stash, uint32_t* total, uint32_t* limit);
 /* The G-buffer walk's stack bound for a scene as hk_scene_upload computes it (inner levels of the TLAS plus those
  * of the deepest instanced BLAS) and the levels the shallow walk can keep in LDS: need <= lds_levels takes the
  * shallow kernel, whose stack follows a staged scene only while bytes + need * 2048 <= limit + 16384. */
@@ -472,6 +476,9 @@ int hk_selftest_div(hk_ctx* ctx, float divisor, uint32_t lo, uint32_t hi, uint64
 /* ---- self-test of the kernels' reciprocal (rcp_exact, hk_device.h): counts the f32 bit patterns
  * x in [lo, hi) (both signs) where rcp_exact(x) != 1 / x (IEEE) */
 int hk_selftest_rcp(hk_ctx* ctx, uint32_t lo, uint32_t hi, uint64_t* mismatches);
+/* ---- self-test of the kernels' ray-counter reduction (wave_count, hk_device.h): thread i of 256-thread workgroups
+ * counts values[i] (n host words; the last workgroup's other threads count nothing); sum: the sharded counter's total */
+int hk_selftest_count(hk_ctx* ctx, const uint32_t* values, uint32_t n, uint64_t* sum);
 
 #ifdef __cplusplus
 }
