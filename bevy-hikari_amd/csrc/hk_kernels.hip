@@ -320,25 +320,34 @@ struct PixelTexels {
     uint32_t normal;
     uchar4 noise;
 };
-HKD PixelTexels load_pixel_texels(const FrameArgs& A, int32_t x, int32_t y)
+// ... at the jittered coordinates (dx, dy) of pixel (x, y): one frame test and one index for the whole batch, so the
+// loads issue back to back and are waited for once.  PD false: without the position texel, for a pass that has read
+// it already (t.pd is then zero and unused).
+template <bool PD = true>
+HKD PixelTexels load_texels_at(const FrameArgs& A, int32_t dx, int32_t dy, int32_t x, int32_t y)
 {
     const Frame& F = A.F;
     PixelTexels t;
-    int32_t dx, dy;
-    jittered_coords(F, coords_to_uv(x, y, F.s), dx, dy);
+    t.pd = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (in_frame(dx, dy, F.S)) {
         const int32_t i = band_index(F, dx, dy, F.S[0], F.S_row0, F.S_rows);
-        t.pd = A.G.position[i];
+        if constexpr (PD) t.pd = A.G.position[i];
         t.vel = A.G.velocity_uv[i];
         t.imf = A.G.instance_material[i];
         t.normal = A.G.normal[i];
     } else {
-        t.pd = t.vel = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        t.vel = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         t.imf = make_float2(0.0f, 0.0f);
         t.normal = 0u;
     }
     t.noise = noise_texel(A.noise, F.number, x, y);
     return t;
+}
+HKD PixelTexels load_pixel_texels(const FrameArgs& A, int32_t x, int32_t y)
+{
+    int32_t dx, dy;
+    jittered_coords(A.F, coords_to_uv(x, y, A.F.s), dx, dy);
+    return load_texels_at(A, dx, dy, x, y);
 }
 HKD f3 texel_normal(uint32_t n) { return mk3(hk_unpack_snorm8_fast(n, 0), hk_unpack_snorm8_fast(n, 1), hk_unpack_snorm8_fast(n, 2)); }
 HKD DirectPixel direct_pixel_of(const FrameArgs& A, int32_t x, int32_t y, const PixelTexels& t)
@@ -695,10 +704,13 @@ HKD void direct_body(const FrameArgs& A, const Scene& sc, const ChannelArgs& C, 
 // these targets (a launch without the mask, reservoir uploads, reallocation, another pass window).
 enum BgElide : uint32_t { BG_STORE = 0, BG_SKIP_OWN = 1, BG_SKIP_ALL = 2 };
 constexpr uint32_t BG_PAIR = 16u;
-HKD uint32_t bg_elide(const ChannelArgs& C, int32_t idx, bool background)
+// the pixel's mask byte (0 without a mask), for a pass that requests it with its first load, before it knows whether
+// the pixel is background; bg_elide(C, idx, background, m) then uses it where the byte was read before.  Only the
+// pixel's own thread writes the byte during a launch, so the earlier read returns the same value.
+HKD uint32_t bg_mask(const ChannelArgs& C, int32_t idx) { return C.bg ? C.bg[idx] : 0u; }
+HKD uint32_t bg_elide(const ChannelArgs& C, int32_t idx, bool background, uint32_t m)
 {
     if (!C.bg) return BG_STORE;
-    const uint32_t m = C.bg[idx];
     if (!background) {
         if (m) C.bg[idx] = 0;
         return BG_STORE;
@@ -709,6 +721,7 @@ HKD uint32_t bg_elide(const ChannelArgs& C, int32_t idx, bool background)
     if ((m & own) != own) return BG_STORE;
     return (pair && (m & BG_PAIR)) ? BG_SKIP_ALL : BG_SKIP_OWN;
 }
+HKD uint32_t bg_elide(const ChannelArgs& C, int32_t idx, bool background) { return bg_elide(C, idx, background, bg_mask(C, idx)); }
 HKD Reservoir background_reservoir()
 {
     Reservoir r = zero_reservoir();
@@ -1200,20 +1213,19 @@ HKD IndirectPixel indirect_pixel_head(const FrameArgs& A, f2 uv, const PixelTexe
 HKD void indirect_pixel_rest(const FrameArgs& A, int32_t x, int32_t y, const PixelTexels* tex, IndirectPixel& P)
 {
     const Frame& F = A.F;
-    if (tex) {
-        P.normal = normalize(texel_normal(tex->normal));
-        P.im_x = f2u32(tex->imf.x);
-        P.im_y = f2u32(tex->imf.y);
-        P.velocity_uv = mk4(tex->vel.x, tex->vel.y, tex->vel.z, tex->vel.w);
-        P.random = noise_of(tex->noise, F.number);
-    } else {
-        P.normal = normalize(load_normal(F, A.G, P.dx, P.dy));
-        const f2 imf = load_instance_material(F, A.G, P.dx, P.dy);
-        P.im_x = f2u32(imf.x);
-        P.im_y = f2u32(imf.y);
-        P.velocity_uv = load_velocity_uv(F, A.G, P.dx, P.dy);
-        P.random = noise_random(A.noise, F.number, x, y);
+    // Without preloaded texels: the normal, instance / material, velocity / uv and blue-noise texels as one batch,
+    // the texels load_normal / load_instance_material / load_velocity_uv / noise_random read.  Behind those helpers'
+    // own frame tests each load was waited for before the next was issued: four dependent round trips for one.
+    PixelTexels own;
+    if (!tex) {
+        own = load_texels_at<false>(A, P.dx, P.dy, x, y);
+        tex = &own;
     }
+    P.normal = normalize(texel_normal(tex->normal));
+    P.im_x = f2u32(tex->imf.x);
+    P.im_y = f2u32(tex->imf.y);
+    P.velocity_uv = mk4(tex->vel.x, tex->vel.y, tex->vel.z, tex->vel.w);
+    P.random = noise_of(tex->noise, F.number);
 }
 // The multiple-bounce path (light.wgsl:1300-1394 with MULTIPLE_BOUNCES) from the pixel's sample s: the whole loop,
 // both walks of every bounce included.  B.s is the path's current vertex; the first bounce's hit becomes s's sample
@@ -1294,6 +1306,9 @@ HKD bool indirect_begin(const FrameArgs& A, const Scene& sc, const ChannelArgs& 
     const Frame& F = A.F;
     const int32_t idx = s_index(F, x, y);
     const f2 uv = coords_to_uv(x, y, F.s);
+    // the mask byte is requested with the position texel (both need only the pixel's coordinates), not after it
+    uint32_t bg_m = 0u;
+    if constexpr (STAGE == IND_ALL || STAGE == IND_GEN) bg_m = bg_mask(C, idx);
     IndirectPixel P = indirect_pixel_head(A, uv, tex);
     const f4 pd = P.pd;
     f4 position = mk4(pd.x, pd.y, pd.z, 1.0f);
@@ -1302,7 +1317,7 @@ HKD bool indirect_begin(const FrameArgs& A, const Scene& sc, const ChannelArgs& 
     Reservoir r = zero_reservoir();
     const bool background = F.indirect_bounces == 0u || depth < HK_F32_EPSILON;
     uint32_t bg = BG_STORE;
-    if constexpr (STAGE == IND_ALL || STAGE == IND_GEN) bg = bg_elide(C, idx, background);
+    if constexpr (STAGE == IND_ALL || STAGE == IND_GEN) bg = bg_elide(C, idx, background, bg_m);
     if (background) {
         if constexpr (STAGE == IND_ALL || STAGE == IND_GEN) {
             if (bg != BG_SKIP_ALL) {
@@ -1401,17 +1416,15 @@ HKD void indirect_end(const FrameArgs& A, const Scene& sc, const ChannelArgs& C,
         // per SIMD.  Cornell 1080p k_indirect 0.225 -> 0.211 ms, frame 0.408 -> 0.396 ms; city 4K 0.632 -> 0.607 ms
         // (profiles/r04/c7).
         __asm__ volatile("" ::: "memory");
-        int32_t dx, dy;
-        jittered_coords(F, I.uv, dx, dy);
-        const f4 pd = load_position(F, A.G, dx, dy);
+        const PixelTexels t = load_pixel_texels(A, I.x, I.y);  // one batch (I.uv is coords_to_uv of I.x, I.y)
+        const f4 pd = mk4(t.pd.x, t.pd.y, t.pd.z, t.pd.w);
         s.visible_position = pd;
-        s.visible_normal = normalize(load_normal(F, A.G, dx, dy));
-        const f2 imf = load_instance_material(F, A.G, dx, dy);
-        s.visible_instance = f2u32(imf.x);
-        s.random = noise_random(A.noise, F.number, I.x, I.y);
+        s.visible_normal = normalize(texel_normal(t.normal));
+        s.visible_instance = f2u32(t.imf.x);
+        s.random = noise_of(t.noise, F.number);
         I.position = mk4(pd.x, pd.y, pd.z, 1.0f);
-        I.velocity_uv = load_velocity_uv(F, A.G, dx, dy);
-        I.im_y = f2u32(imf.y);
+        I.velocity_uv = mk4(t.vel.x, t.vel.y, t.vel.z, t.vel.w);
+        I.im_y = f2u32(t.imf.y);
     }
     const int32_t idx = I.idx;
     const f2 uv = I.uv;
@@ -1494,6 +1507,8 @@ __global__ __launch_bounds__(256) void k_indirect(FrameArgs A, ChannelArgs C)
     // 0.497 ms, scene 0.251 -> 0.243, profiles/r06/c13).  The staged variant (cornell) does not: the texels live
     // across the staging took it 92 -> 99 VGPRs, 5 -> 4 waves per SIMD (0.178 -> 0.192 ms), and the position + noise
     // texels alone (95 VGPRs) measured 0.181.  The multi-bounce variants (no BASELINE config) keep their own loads.
+    // Their own loads are two batches (indirect_begin: position + mask byte, then indirect_pixel_rest's); all of them
+    // in one batch after the staging barrier (94 VGPRs) measured 0.1684 against 0.1667 ms (profiles/r08).
     constexpr bool PRE = !MULTI && !LDS && !CS;
     PixelTexels tex;
     if (PRE && active) tex = load_pixel_texels(A, x, y);
