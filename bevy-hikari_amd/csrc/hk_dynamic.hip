@@ -39,6 +39,34 @@ HKD void bbox_grow(BBox& a, const float* p)
         a.mx[k] = fmaxf(a.mx[k], p[k]);
     }
 }
+// std::fmin / std::fmax as the host builder evaluates them (a NaN test, then minss / maxss): of two equal operands,
+// which zeros of either sign are, the second.  fminf / fmaxf here order -0 below +0 instead, so a box that holds
+// zeros of both signs would differ from the host's in the sign bit.  Every box that is written out (instance boxes,
+// the child boxes of a split) gets the host's fold, in the host's order; the boxes that only steer a split
+// (centroid bounds, bucket boxes, SAH areas) keep fminf / fmaxf: the sign of a zero changes no comparison there
+// (an area of either zero over a non-zero one compares equal, and 0 / 0 is NaN under both signs).
+HKD float host_fmin(float a, float b) { return (a < b || b != b) ? a : b; }
+HKD float host_fmax(float a, float b) { return (a > b || b != b) ? a : b; }
+// The box of shapes ids[first..last) as the host's fold leaves it: the value by fminf / fmaxf, and a bound of 0 with
+// the sign of the last zero in index order (host_fmin keeps the second of two equal operands).
+HKD BBox bbox_fold_host(const BBox* shapes, const uint32_t* ids, uint32_t first, uint32_t last)
+{
+    BBox a = bbox_empty();
+    for (uint32_t i = first; i < last; ++i) bbox_join(a, shapes[ids[i]]);
+    for (int k = 0; k < 3; ++k) {
+        if (a.mn[k] == 0.0f)
+            for (uint32_t i = first; i < last; ++i) {
+                const float v = shapes[ids[i]].mn[k];
+                if (v == 0.0f) a.mn[k] = v;
+            }
+        if (a.mx[k] == 0.0f)
+            for (uint32_t i = first; i < last; ++i) {
+                const float v = shapes[ids[i]].mx[k];
+                if (v == 0.0f) a.mx[k] = v;
+            }
+    }
+    return a;
+}
 HKD float bbox_center(const BBox& b, int k) { return (b.mn[k] + b.mx[k]) * 0.5f; }
 HKD float bbox_area(const BBox& b)
 {
@@ -152,9 +180,7 @@ HKD void split_segment(const BBox* shapes, const uint32_t* src, uint32_t* dst, S
         for (uint32_t i = 0; i < s.count; ++i) dst[s.start + i] = src[s.start + i];
     }
     const uint32_t nr = s.count - nl;
-    BBox la = bbox_empty(), ra = bbox_empty();
-    for (uint32_t i = 0; i < nl; ++i) bbox_join(la, shapes[dst[s.start + i]]);
-    for (uint32_t i = nl; i < s.count; ++i) bbox_join(ra, shapes[dst[s.start + i]]);
+    const BBox la = bbox_fold_host(shapes, dst + s.start, 0u, nl), ra = bbox_fold_host(shapes, dst + s.start, nl, s.count);
     const uint32_t q = s.out + 1u + flat_size(nl);  // box node of the right child
     flat[s.out] = pack_node(la, s.out + 1u, q);
     flat[q] = pack_node(ra, q + 1u, q + 1u + flat_size(nr));
@@ -342,6 +368,24 @@ HKD void coop_split(const BBox* shapes, const uint32_t* src, uint32_t* dst, Segm
             for (int k = 0; k < 3; ++k) c[o + k] = fminf(c[o + k], b.mn[k]), c[o + 3 + k] = fmaxf(c[o + 3 + k], b.mx[k]);
         }
         block_reduce<12>(c, cop, sh);
+        // A bound of 0 takes its sign from the last zero of its child in index order, as the host's fold leaves it
+        // (host_fmin).  c[] is the same in every thread, so the branch is block-uniform.
+        for (int j = 0; j < 12; ++j) {
+            if (c[j] != 0.0f) continue;
+            if (threadIdx.x == 0) sh.u[0] = 0u;
+            __syncthreads();
+            const uint32_t first = j < 6 ? 0u : nl, last = j < 6 ? nl : s.count;
+            uint32_t key = 0u;  // (index + 1) * 2 + sign bit of the thread's last zero
+            for (uint32_t i = first + threadIdx.x; i < last; i += 256u) {
+                const BBox& b = shapes[dst[s.start + i]];
+                const float v = (j % 6) < 3 ? b.mn[j % 3] : b.mx[j % 3];
+                if (v == 0.0f) key = ((i + 1u) << 1) | (__float_as_uint(v) >> 31);
+            }
+            if (key) atomicMax(&sh.u[0], key);
+            __syncthreads();
+            c[j] = (sh.u[0] & 1u) ? -0.0f : 0.0f;
+            __syncthreads();
+        }
         const uint32_t nr = s.count - nl;
         const uint32_t q = s.out + 1u + flat_size(nl);
         if (threadIdx.x == 0) {
@@ -359,7 +403,7 @@ HKD void coop_split(const BBox* shapes, const uint32_t* src, uint32_t* dst, Segm
 // seg: 2 x n scratch segments.  When the shapes and both index buffers fit BVH_LDS_SHAPES they
 // are staged in LDS.  *levels: the number of tree levels that split (max inner nodes on a path).
 constexpr uint32_t BVH_LDS_SHAPES = 1280;  // 1280 x (24 + 8) B = 40 KiB
-constexpr uint32_t BIG_MAX = 64;           // big segments per level (<= n / COOP_MIN)
+constexpr uint32_t BIG_MAX = 64;           // big segments per level; further ones are split per thread
 template <bool LDS>
 __global__ __launch_bounds__(256) void k_build_bvh(const BBox* g_shapes, uint32_t n, int buckets, hk_node* flat,
                                                    uint32_t* g_idx, Segment* seg, uint32_t* levels)
@@ -391,14 +435,18 @@ __global__ __launch_bounds__(256) void k_build_bvh(const BBox* g_shapes, uint32_
     uint32_t split_levels = 0;
     auto push = [&](int p, const Segment& l, const Segment& r) {  // children of a level-p split
         for (const Segment* c : {&l, &r}) {
-            // only thread 0 pushes big segments (from coop_split), so the bound check is race-free
-            if (coop && c->count > COOP_MIN && n_big_next < BIG_MAX) {
-                uint32_t k = atomicAdd(&n_big_next, 1u);
-                big[p ^ 1][k] = *c;
-            } else {
-                uint32_t k = atomicAdd(&n_small_next, 1u);
-                segs[p ^ 1][k] = *c;
+            // Any thread may push a big segment: thread 0 after a coop_split, and every thread whose own segment
+            // was a big one the full list turned away.  So the slot is claimed first and checked after; the
+            // counter may pass BIG_MAX and is clamped where the level ends.
+            if (coop && c->count > COOP_MIN) {
+                const uint32_t k = atomicAdd(&n_big_next, 1u);
+                if (k < BIG_MAX) {
+                    big[p ^ 1][k] = *c;
+                    continue;
+                }
             }
+            const uint32_t k = atomicAdd(&n_small_next, 1u);
+            segs[p ^ 1][k] = *c;
         }
     };
     for (int level = 0;; ++level) {
@@ -419,7 +467,7 @@ __global__ __launch_bounds__(256) void k_build_bvh(const BBox* g_shapes, uint32_
         if (n_small_next + n_big_next) split_levels = level + 1;
         __syncthreads();
         if (threadIdx.x == 0) {
-            n_big = n_big_next;
+            n_big = n_big_next < BIG_MAX ? n_big_next : BIG_MAX;
             n_small = n_small_next;
             n_big_next = n_small_next = 0;
         }
@@ -498,8 +546,8 @@ __global__ __launch_bounds__(256) void k_update_instances(hk_instance* inst, uin
         float corner[3];
         transform_vector(m, v, corner);
         for (int d = 0; d < 3; ++d) {
-            mn[d] = fminf(mn[d], corner[d]);
-            mx[d] = fmaxf(mx[d], corner[d]);
+            mn[d] = host_fmin(mn[d], corner[d]);
+            mx[d] = host_fmax(mx[d], corner[d]);
         }
     }
     BBox b;

@@ -274,3 +274,15 @@ def assert_instance_update_matches_host(r, desc, skip_empty=False):
     inst = np.frombuffer(host_scene_array(desc, 4, inst_dt).tobytes(), np.float32).reshape(-1, 44)
     leaf_ids = h["entry"][~inner] - 0x80000000
     assert np.array_equal(g["min"][~inner], inst[leaf_ids, 0:3]) and np.array_equal(g["max"][~inner], inst[leaf_ids, 4:7])
+
+
+def assert_rebuild_bitwise(r, desc):
+    """assert_instance_update_matches_host (empty host arrays not read back), and the device TLAS's leaf boxes byte for
+    byte the host instance boxes, so that a zero of the other sign counts as a difference there too."""
+    assert_instance_update_matches_host(r, desc, skip_empty=True)
+    h = host_scene_array(desc, 5, NODE_DT)
+    g = r.scene_array(5, NODE_DT, len(h))
+    leaf = h["entry"] >= 0x80000000
+    inst = np.frombuffer(host_scene_array(desc, 4, np.dtype((np.void, 176))).tobytes(), np.float32).reshape(-1, 44)
+    ids = h["entry"][leaf] - 0x80000000
+    assert g["min"][leaf].tobytes() == inst[ids, 0:3].tobytes() and g["max"][leaf].tobytes() == inst[ids, 4:7].tobytes()
