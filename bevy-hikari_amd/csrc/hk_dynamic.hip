@@ -1,4 +1,4 @@
-// hk_dynamic.hip — dynamic instances on the device.
+// hk_dynamic.hip — dynamic instances and deforming meshes on the device.
 //
 // The reference re-runs `prepare_instances` on the CPU whenever a transform changes
 // (instance.rs:284-437: instance records with world AABBs and inverse-transpose models, the
@@ -405,8 +405,8 @@ HKD void coop_split(const BBox* shapes, const uint32_t* src, uint32_t* dst, Segm
 constexpr uint32_t BVH_LDS_SHAPES = 1280;  // 1280 x (24 + 8) B = 40 KiB
 constexpr uint32_t BIG_MAX = 64;           // big segments per level; further ones are split per thread
 template <bool LDS>
-__global__ __launch_bounds__(256) void k_build_bvh(const BBox* g_shapes, uint32_t n, int buckets, hk_node* flat,
-                                                   uint32_t* g_idx, Segment* seg, uint32_t* levels)
+HKD void build_bvh(const BBox* g_shapes, uint32_t n, int buckets, hk_node* flat, uint32_t* g_idx, Segment* seg,
+                   uint32_t* levels)
 {
     __shared__ uint32_t n_small, n_small_next, n_big, n_big_next;
     __shared__ Segment big[2][BIG_MAX];
@@ -474,6 +474,77 @@ __global__ __launch_bounds__(256) void k_build_bvh(const BBox* g_shapes, uint32_
         __syncthreads();
     }
     if (threadIdx.x == 0 && levels) *levels = split_levels;
+}
+template <bool LDS>
+__global__ __launch_bounds__(256) void k_build_bvh(const BBox* g_shapes, uint32_t n, int buckets, hk_node* flat,
+                                                   uint32_t* g_idx, Segment* seg, uint32_t* levels)
+{
+    build_bvh<LDS>(g_shapes, n, buckets, flat, g_idx, seg, levels);
+}
+
+// ---- deforming meshes (mesh.rs:77-166 prepare_mesh_assets, mod.rs:379-467 GpuMesh::try_from; hk_scene.cpp
+// hks_add_mesh + hks_build "BLAS per mesh").  Topology is unchanged: the primitives keep their vertex indices.
+// One thread per vertex of the listed meshes (position and normal of the hk_vertex; u, v stay), then one per
+// triangle: its three positions from the new vertex data and its shape box, folded from empty in vertex order
+// with the host's fmin / fmax (Aabb::grow), at the mesh's slice of the shape scratch.  The triangles read the
+// uploaded positions, not the vertex array, so the two halves do not depend on each other.  Every vertex index was
+// checked against vertex_count on the host (hk_update_meshes).
+HKD uint32_t mesh_of(const MeshUpdate* tab, uint32_t n, uint32_t i, bool shapes)
+{
+    uint32_t lo = 0, hi = n;  // the last mesh whose first vertex / shape is <= i (the firsts ascend)
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if ((shapes ? tab[mid].shape0 : tab[mid].vertex0) <= i) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+__global__ __launch_bounds__(256) void k_update_mesh_geometry(const MeshUpdate* tab, uint32_t n_meshes,
+                                                              uint32_t n_vertices, uint32_t n_shapes,
+                                                              const float* positions, const float* normals,
+                                                              hk_vertex* vertices, hk_primitive* prims, BBox* shapes)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n_vertices) {
+        const MeshUpdate& m = tab[mesh_of(tab, n_meshes, i, false)];
+        const uint32_t v = i - m.vertex0;
+        if (v >= m.vertex_count) return;
+        hk_vertex& out = vertices[m.vertex + v];
+        for (int k = 0; k < 3; ++k) out.position[k] = positions[3u * (size_t)i + k];
+        if (m.has_normals)
+            for (int k = 0; k < 3; ++k) out.normal[k] = normals[3u * (size_t)i + k];
+        return;
+    }
+    const uint32_t j = i - n_vertices;
+    if (j >= n_shapes) return;
+    const MeshUpdate& m = tab[mesh_of(tab, n_meshes, j, true)];
+    const uint32_t t = j - m.shape0;
+    if (t >= m.shapes) return;
+    hk_primitive& pr = prims[m.primitive + t];
+    const float inf = __uint_as_float(0x7F800000u);
+    float mn[3] = {inf, inf, inf}, mx[3] = {-inf, -inf, -inf};
+    for (int c = 0; c < 3; ++c) {
+        const uint32_t v = pr.vertices[c].index;
+        if (v >= m.vertex_count) continue;  // (refused on the host; never taken)
+        for (int k = 0; k < 3; ++k) {
+            const float x = positions[3u * (size_t)(m.vertex0 + v) + k];
+            pr.vertices[c].position[k] = x;
+            mn[k] = host_fmin(mn[k], x);
+            mx[k] = host_fmax(mx[k], x);
+        }
+    }
+    shapes[j] = BBox{{mn[0], mn[1], mn[2]}, {mx[0], mx[1], mx[2]}};
+}
+// One workgroup per listed mesh: build_bvh over the mesh's shape boxes into its own node slice (node indices
+// relative to the mesh, as the host's per-mesh build leaves them), with the mesh's slices of the index and segment
+// scratch.  tab: the meshes of this instantiation (LDS: at most BVH_LDS_SHAPES triangles).
+template <bool LDS>
+__global__ __launch_bounds__(256) void k_build_mesh_bvh(const MeshUpdate* tab, const BBox* shapes, int buckets,
+                                                        hk_node* blas, uint32_t* idx, Segment* seg, uint32_t* levels)
+{
+    const MeshUpdate m = tab[blockIdx.x];
+    build_bvh<LDS>(shapes + m.shape0, m.shapes, buckets, blas + m.node0, idx + 2u * (size_t)m.shape0,
+                   seg + 2u * (size_t)m.shape0, levels + m.slot);
 }
 
 // ---- instance records (instance.rs:284-330; hk_scene.cpp hks_build "instances")
@@ -699,5 +770,21 @@ void launch_dynamic_update(const DynamicArgs& D, hipStream_t st)
     hipLaunchKernelGGL(k_backfill_nodes, dim3((m + 255u) / 256u), dim3(256), 0, st, D.tlas, 3u * n - 2u, D.instances,
                        D.lbvh, D.n_emissives ? 3u * D.n_emissives - 2u : 0u, D.emissives);
 }
+
+// tab: the LDS-sized meshes first (n_lds of them), then the others; levels[slot]: each mesh's split levels
+void launch_mesh_update(const MeshUpdateArgs& M, hipStream_t st)
+{
+    const uint32_t items = M.n_vertices + M.n_shapes;
+    hipLaunchKernelGGL(k_update_mesh_geometry, dim3((items + 255u) / 256u), dim3(256), 0, st, M.table, M.n_meshes,
+                       M.n_vertices, M.n_shapes, M.positions, M.normals, M.vertices, M.primitives, (BBox*)M.shapes);
+    if (M.n_lds)
+        hipLaunchKernelGGL(k_build_mesh_bvh<true>, dim3(M.n_lds), dim3(256), 0, st, M.table_by_size, (const BBox*)M.shapes,
+                           M.buckets, M.blas, M.idx, (Segment*)M.segments, M.levels);
+    if (M.n_meshes > M.n_lds)
+        hipLaunchKernelGGL(k_build_mesh_bvh<false>, dim3(M.n_meshes - M.n_lds), dim3(256), 0, st,
+                           M.table_by_size + M.n_lds, (const BBox*)M.shapes, M.buckets, M.blas, M.idx,
+                           (Segment*)M.segments, M.levels);
+}
+uint32_t mesh_lds_shapes() { return BVH_LDS_SHAPES; }
 
 }  // namespace hk

@@ -148,6 +148,38 @@ struct DynamicArgs {
 };
 void launch_dynamic_update(const DynamicArgs& D, hipStream_t st);
 
+// Deforming meshes (hk_dynamic.hip): one record per listed mesh, in a device table.
+struct MeshUpdate {
+    uint32_t vertex, vertex_count;  // the mesh's slice of the vertex array
+    uint32_t primitive, shapes;     // its slice of the primitive array (shapes = triangles)
+    uint32_t node0;                 // its first asset node (3 x shapes - 2 of them)
+    uint32_t vertex0;               // its first vertex in the uploaded positions / normals (list order)
+    uint32_t shape0;                // its first shape box in the scratch; indices and segments at 2 x shape0
+    uint32_t slot;                  // its place in the list: levels[slot]
+    uint32_t has_normals;           // 0: the vertices keep their normals
+};
+struct MeshUpdateArgs {
+    const MeshUpdate* table;          // n_meshes records in list order (vertex0 and shape0 ascend)
+    const MeshUpdate* table_by_size;  // the same records, the n_lds of at most mesh_lds_shapes() triangles first
+    uint32_t n_meshes, n_lds;
+    uint32_t n_vertices, n_shapes;    // sums over the list
+    const float* positions;           // n_vertices x 3
+    const float* normals;             // n_vertices x 3 (read where has_normals)
+    hk_vertex* vertices;
+    hk_primitive* primitives;
+    hk_node* blas;
+    int buckets;
+    // scratch
+    void* shapes;                     // n_shapes x 24 B
+    uint32_t* idx;                    // 2 x n_shapes
+    void* segments;                   // 2 x n_shapes x 12 B
+    uint32_t* levels;                 // n_meshes: split levels of each rebuilt BLAS (G-buffer stack bound)
+};
+// vertex and primitive rewrite with the shape boxes (one launch), then the BLAS builds: one workgroup per mesh, one
+// launch per instantiation of the build (LDS-staged / global)
+void launch_mesh_update(const MeshUpdateArgs& M, hipStream_t st);
+uint32_t mesh_lds_shapes();
+
 // Post-process (hk_post.hip over include/hk_post.h)
 struct PostArgs {
     hk_pp_frame frame;

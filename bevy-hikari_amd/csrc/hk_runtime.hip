@@ -15,6 +15,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -300,6 +301,17 @@ struct hk_ctx {
     uint32_t gb_blas_depth = 0;   // BLAS part of it (the TLAS part changes with hk_update_instances)
     void* dyn_scratch = nullptr;  // hk_update_instances scratch (sized at upload)
     size_t dyn_bytes = 0;
+    // hk_update_meshes: the instanced meshes as upload recorded them (slice, vertices their primitives index, BLAS
+    // depth), the per-node mesh tables of the BLAS derivatives (primitive offset, node base, node count) and scratch
+    struct MeshSlice {
+        hk_mesh_index index;
+        uint32_t vertex_need;  // largest stored vertex index + 1; U32_MAX: the slices do not fit the arrays
+        uint32_t depth;        // inner levels of its BLAS
+    };
+    std::vector<MeshSlice> meshes;
+    uint32_t* blas_aux = nullptr;
+    void* mesh_scratch = nullptr;
+    size_t mesh_bytes = 0;
     // GlobalTransformQueue[1] of every instance (transform.rs:32-44): the models as of the previous
     // k_gbuffer, read by its motion vectors; refreshed after a k_gbuffer that followed an update
     float* prev_models = nullptr;
@@ -1000,6 +1012,8 @@ void hk_destroy(hk_ctx* c)
     release(c->walk_nodes[1]);
     release(c->collapse_scratch);
     release(c->dyn_scratch);
+    release(c->blas_aux);
+    release(c->mesh_scratch);
     release(c->prev_models);
     release(c->tex_desc);
     release(c->texels);
@@ -1057,32 +1071,33 @@ static size_t staged_alloc_bytes(size_t count, size_t elem) { return ((count ? c
 // Stack bound of closest_hit_ordered for a scene (pushes along a path <= inner subtree starts on it): the inner
 // levels of the TLAS plus those of the deepest instanced BLAS.  false: an instance's node range is outside the
 // asset nodes.
+static uint32_t flat_depth(const hk_node* f, uint32_t count)
+{
+    std::vector<uint32_t> dep(count + 1, 0);
+    uint32_t best = 0;
+    for (uint32_t p = count; p-- > 0;) {
+        if (f[p].entry_index >= HK_BVH_LEAF_FLAG) continue;
+        uint32_t q = f[p].exit_index;
+        uint32_t dl = p + 1 < count ? dep[p + 1] : 0, dr = q < count && q + 1 < count ? dep[q + 1] : 0;
+        dep[p] = 1 + (dl > dr ? dl : dr);
+    }
+    for (uint32_t p = 0; p < count; ++p) best = dep[p] > best ? dep[p] : best;
+    return best;
+}
 static bool scene_stack_need(const hk_scene_desc* d, uint32_t* need, uint32_t* blas_depth_out)
 {
     const uint32_t n_blas = d->asset_nodes.count, n_tlas = d->instance_nodes.count;
     const hk_instance* inst = (const hk_instance*)d->instances.data;
     const hk_node* blas = (const hk_node*)d->asset_nodes.data;
     const hk_node* tlas = (const hk_node*)d->instance_nodes.data;
-    auto depth = [](const hk_node* f, uint32_t count) {
-        std::vector<uint32_t> dep(count + 1, 0);
-        uint32_t best = 0;
-        for (uint32_t p = count; p-- > 0;) {
-            if (f[p].entry_index >= HK_BVH_LEAF_FLAG) continue;
-            uint32_t q = f[p].exit_index;
-            uint32_t dl = p + 1 < count ? dep[p + 1] : 0, dr = q < count && q + 1 < count ? dep[q + 1] : 0;
-            dep[p] = 1 + (dl > dr ? dl : dr);
-        }
-        for (uint32_t p = 0; p < count; ++p) best = dep[p] > best ? dep[p] : best;
-        return best;
-    };
     uint32_t blas_depth = 0;
     for (uint32_t k = 0; k < d->instances.count; ++k) {
         const hk_mesh_index& m = inst[k].mesh;
         if ((size_t)m.node[0] + m.node[1] > n_blas) return false;
-        uint32_t dd = depth(blas + m.node[0], m.node[1]);
+        uint32_t dd = flat_depth(blas + m.node[0], m.node[1]);
         blas_depth = dd > blas_depth ? dd : blas_depth;
     }
-    *need = depth(tlas, n_tlas) + blas_depth;
+    *need = flat_depth(tlas, n_tlas) + blas_depth;
     if (blas_depth_out) *blas_depth_out = blas_depth;
     return true;
 }
@@ -1170,9 +1185,31 @@ int hk_scene_upload(hk_ctx* c, const hk_scene_desc* d)
         }
     }
     (void)scene_stack_need(d, &c->gb_stack_need, &c->gb_blas_depth);  // (node ranges checked above)
+    // the instanced meshes, for hk_update_meshes: each distinct slice once, with the vertices its primitives index
+    // and its BLAS depth (gb_blas_depth is the maximum of these)
+    c->meshes.clear();
+    std::set<std::array<uint32_t, 4>> seen;
+    for (uint32_t k = 0; k < d->instances.count; ++k) {
+        const hk_mesh_index& m = inst[k].mesh;
+        if (!seen.insert({m.vertex, m.primitive, m.node[0], m.node[1]}).second) continue;
+        hk_ctx::MeshSlice s{m, HK_U32_MAX, flat_depth((const hk_node*)d->asset_nodes.data + m.node[0], m.node[1])};
+        const uint32_t tris = (m.node[1] + 2u) / 3u;
+        if (m.node[1] && (m.node[1] + 2u) % 3u == 0 && (size_t)m.primitive + tris <= d->primitives.count &&
+            m.vertex < d->vertices.count) {
+            const hk_primitive* pr = (const hk_primitive*)d->primitives.data + m.primitive;
+            uint32_t top = 0;
+            for (uint32_t t = 0; t < tris; ++t)
+                for (int v = 0; v < 3; ++v) top = std::max(top, pr[t].vertices[v].index);
+            if (top < d->vertices.count - m.vertex) s.vertex_need = top + 1u;
+        }
+        c->meshes.push_back(s);
+    }
     release(c->dyn_scratch);
     c->dyn_bytes = 0;
-    uint32_t* d_aux = nullptr;
+    release(c->mesh_scratch);
+    c->mesh_bytes = 0;
+    release(c->blas_aux);
+    uint32_t*& d_aux = c->blas_aux;
     HK_HIP(c, hipMalloc(&d_aux, (size_t)(n_blas ? n_blas : 1) * 12));
     if (n_blas) {
         HK_HIP(c, hipMemcpy(d_aux, prim_offset.data(), (size_t)n_blas * 4, hipMemcpyHostToDevice));
@@ -1216,20 +1253,20 @@ int hk_scene_upload(hk_ctx* c, const hk_scene_desc* d)
                                sizeof(hk_instance), 64, d->instances.count, hipMemcpyDeviceToDevice, c->stream));
     c->models_dirty = false;
     HK_HIP(c, hipStreamSynchronize(c->stream));
-    release(d_aux);
     c->has_scene = true;
     return HK_OK;
 }
 
-int hk_update_instances(hk_ctx* c, const float* models, const float* local_aabbs, uint32_t count, void* stream)
+// The BLAS levels hk_update_meshes rebuilt, read back in the instance rebuild's one wait
+struct MeshLevels {
+    const uint32_t* device;
+    std::vector<uint32_t> slice;  // c->meshes index of each listed mesh
+};
+
+// The instance rebuild on `st` (after the mesh rebuild of hk_update_meshes, if any) and its one wait
+static int rebuild_instances(hk_ctx* c, const float* models, const float* local_aabbs, uint32_t count, hipStream_t st,
+                             const MeshLevels* ml)
 {
-    if (!c || !models || !local_aabbs) return HK_ERR_INVALID;
-    if (!c->has_scene) return fail(c, HK_ERR_STATE, "no scene uploaded (hk_scene_upload)");
-    if (count != c->count[4]) return fail(c, HK_ERR_INVALID, "hk_update_instances needs every instance, in upload order");
-    if (c->count[5] != 3u * count - 2u || (c->count[8] && c->count[7] != 3u * c->count[8] - 2u))
-        return fail(c, HK_ERR_STATE, "scene BVHs are not bvh-0.7.1 flattened (3n - 2 nodes); cannot rebuild");
-    (void)hipSetDevice(c->device);
-    hipStream_t st = pick(c, stream);
     HK_TRY(c->sch.gb_join(st));
     HK_TRY(c->sch.gb_serialize(false));
     c->gen++;
@@ -1288,12 +1325,151 @@ int hk_update_instances(hk_ctx* c, const float* models, const float* local_aabbs
     });
     HK_HIP(c, hipGetLastError());
     uint32_t flags[2] = {0, 0};
+    std::vector<uint32_t> levels(ml ? ml->slice.size() : 0);
     HK_HIP(c, hipMemcpyAsync(flags, part[8], 8, hipMemcpyDeviceToHost, st));
+    if (ml) HK_HIP(c, hipMemcpyAsync(levels.data(), ml->device, levels.size() * 4, hipMemcpyDeviceToHost, st));
     HK_HIP(c, hipStreamSynchronize(st));
+    if (ml) {  // the deepest instanced BLAS now: a mesh that became shallower lowers the bound
+        for (size_t k = 0; k < levels.size(); ++k) c->meshes[ml->slice[k]].depth = levels[k];
+        c->gb_blas_depth = 0;
+        for (const hk_ctx::MeshSlice& s : c->meshes) c->gb_blas_depth = std::max(c->gb_blas_depth, s.depth);
+        c->gb_stack_need = flags[1] + c->gb_blas_depth;
+    }
     if (flags[0]) return fail(c, HK_ERR_INVALID, "singular instance transform");
     c->gb_stack_need = flags[1] + c->gb_blas_depth;
     c->models_dirty = true;  // the next G-buffer reads the models before this update as the previous ones
     return HK_OK;
+}
+
+// the checks hk_update_instances and hk_update_meshes share; HK_OK: the scene can be rebuilt with `count` instances
+static int update_args_ok(hk_ctx* c, uint32_t count, const char* who)
+{
+    if (!c->has_scene) return fail(c, HK_ERR_STATE, "no scene uploaded (hk_scene_upload)");
+    if (count != c->count[4]) return fail(c, HK_ERR_INVALID, std::string(who) + " needs every instance, in upload order");
+    if (c->count[5] != 3u * count - 2u || (c->count[8] && c->count[7] != 3u * c->count[8] - 2u))
+        return fail(c, HK_ERR_STATE, "scene BVHs are not bvh-0.7.1 flattened (3n - 2 nodes); cannot rebuild");
+    return HK_OK;
+}
+
+int hk_update_instances(hk_ctx* c, const float* models, const float* local_aabbs, uint32_t count, void* stream)
+{
+    if (!c || !models || !local_aabbs) return HK_ERR_INVALID;
+    HK_TRY(update_args_ok(c, count, "hk_update_instances"));
+    (void)hipSetDevice(c->device);
+    return rebuild_instances(c, models, local_aabbs, count, pick(c, stream), nullptr);
+}
+
+int hk_update_meshes(hk_ctx* c, const hk_mesh_update* meshes, uint32_t mesh_count, const float* models,
+                     const float* local_aabbs, uint32_t count, void* stream)
+{
+    if (!c) return HK_ERR_INVALID;
+    if (!meshes || !models || !local_aabbs) return fail(c, HK_ERR_INVALID, "hk_update_meshes: null pointer");
+    HK_TRY(update_args_ok(c, count, "hk_update_meshes"));
+    // every listed mesh against what upload recorded (no device work before the list is accepted whole)
+    std::vector<MeshUpdate> tab(mesh_count);
+    MeshLevels ml;
+    ml.slice.resize(mesh_count);
+    uint32_t n_vertices = 0, n_shapes = 0;
+    for (uint32_t k = 0; k < mesh_count; ++k) {
+        const hk_mesh_update& u = meshes[k];
+        const std::string who = "hk_update_meshes: mesh " + std::to_string(k);
+        if (!u.positions) return fail(c, HK_ERR_INVALID, who + " has no positions");
+        size_t at = c->meshes.size();
+        for (size_t j = 0; j < c->meshes.size(); ++j)
+            if (std::memcmp(&c->meshes[j].index, &u.mesh, sizeof(u.mesh)) == 0) at = j;
+        if (at == c->meshes.size()) return fail(c, HK_ERR_INVALID, who + " is not an instanced mesh of the uploaded scene");
+        for (uint32_t j = 0; j < k; ++j)
+            if (ml.slice[j] == at) return fail(c, HK_ERR_INVALID, who + " is listed twice");
+        const hk_ctx::MeshSlice& s = c->meshes[at];
+        if (s.vertex_need == HK_U32_MAX)
+            return fail(c, HK_ERR_INVALID, who + ": its BLAS is not 3k - 2 nodes over k primitives of the scene; cannot rebuild");
+        // the vertex slice ends where the array or the next instanced mesh's vertices begin
+        uint32_t room = c->count[0] - u.mesh.vertex;
+        for (const hk_ctx::MeshSlice& o : c->meshes)
+            if (o.index.vertex > u.mesh.vertex) room = std::min(room, o.index.vertex - u.mesh.vertex);
+        if (u.vertex_count < s.vertex_need)
+            return fail(c, HK_ERR_INVALID, who + ": vertex_count does not cover the vertex indices of its primitives");
+        if (u.vertex_count > room)
+            return fail(c, HK_ERR_INVALID, who + ": vertex_count reaches past its vertex slice");
+        const uint32_t tris = (u.mesh.node[1] + 2u) / 3u;
+        if ((size_t)n_vertices + u.vertex_count > 0x40000000u || (size_t)n_shapes + tris > 0x40000000u)
+            return fail(c, HK_ERR_INVALID, "hk_update_meshes: too many vertices or primitives in one call");
+        tab[k] = MeshUpdate{u.mesh.vertex, u.vertex_count, u.mesh.primitive, tris, u.mesh.node[0],
+                            n_vertices,    n_shapes,       k,                u.normals ? 1u : 0u};
+        ml.slice[k] = (uint32_t)at;
+        n_vertices += u.vertex_count;
+        n_shapes += tris;
+    }
+    (void)hipSetDevice(c->device);
+    hipStream_t st = pick(c, stream);
+    if (mesh_count == 0) return rebuild_instances(c, models, local_aabbs, count, st, nullptr);
+    HK_TRY(c->sch.gb_join(st));
+    HK_TRY(c->sch.gb_serialize(false));
+    std::vector<MeshUpdate> by_size;
+    for (int big = 0; big < 2; ++big)
+        for (const MeshUpdate& m : tab)
+            if ((m.shapes > mesh_lds_shapes()) == (big == 1)) by_size.push_back(m);
+    uint32_t n_lds = 0;
+    for (const MeshUpdate& m : tab) n_lds += m.shapes <= mesh_lds_shapes() ? 1u : 0u;
+    auto align = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t sz[] = {align((size_t)mesh_count * sizeof(MeshUpdate)), align((size_t)mesh_count * sizeof(MeshUpdate)),
+                         align((size_t)n_vertices * 12),  align((size_t)n_vertices * 12),
+                         align((size_t)n_shapes * 24),    align((size_t)n_shapes * 8),
+                         align((size_t)n_shapes * 24),    align((size_t)mesh_count * 4)};
+    size_t total = 0;
+    for (size_t b : sz) total += b;
+    if (c->mesh_bytes < total) {
+        release(c->mesh_scratch);
+        HK_HIP(c, hipMalloc(&c->mesh_scratch, total));
+        c->mesh_bytes = total;
+    }
+    char* part[8];
+    char* p = (char*)c->mesh_scratch;
+    for (int k = 0; k < 8; ++k) {
+        part[k] = p;
+        p += sz[k];
+    }
+    HK_HIP(c, hipMemcpyAsync(part[0], tab.data(), tab.size() * sizeof(MeshUpdate), hipMemcpyHostToDevice, st));
+    HK_HIP(c, hipMemcpyAsync(part[1], by_size.data(), by_size.size() * sizeof(MeshUpdate), hipMemcpyHostToDevice, st));
+    for (uint32_t k = 0; k < mesh_count; ++k) {
+        const size_t at = (size_t)tab[k].vertex0 * 12, bytes = (size_t)tab[k].vertex_count * 12;
+        HK_HIP(c, hipMemcpyAsync(part[2] + at, meshes[k].positions, bytes, hipMemcpyHostToDevice, st));
+        if (meshes[k].normals) HK_HIP(c, hipMemcpyAsync(part[3] + at, meshes[k].normals, bytes, hipMemcpyHostToDevice, st));
+    }
+    MeshUpdateArgs M;
+    M.table = (const MeshUpdate*)part[0];
+    M.table_by_size = (const MeshUpdate*)part[1];
+    M.n_meshes = mesh_count;
+    M.n_lds = n_lds;
+    M.n_vertices = n_vertices;
+    M.n_shapes = n_shapes;
+    M.positions = (const float*)part[2];
+    M.normals = (const float*)part[3];
+    M.vertices = (hk_vertex*)c->buf[0];
+    M.primitives = (hk_primitive*)c->buf[1];
+    M.blas = (hk_node*)c->buf[2];
+    M.buckets = 6;  // bvh 0.7.1 NUM_BUCKETS (hks_build default)
+    M.shapes = part[4];
+    M.idx = (uint32_t*)part[5];
+    M.segments = part[6];
+    M.levels = (uint32_t*)part[7];
+    const uint32_t n_blas = c->count[2];
+    timed(c, "update_meshes", st, [&] {
+        launch_mesh_update(M, st);
+        // device-only derivatives of the asset nodes, over the whole array: leaf boxes, the G-buffer wide layout and
+        // the light walks' copy with its leaf collapse (as hk_scene_upload derives them)
+        launch_fill_leaves((hk_node*)c->buf[2], n_blas, c->blas_aux, (const hk_primitive*)c->buf[1], nullptr, 0, nullptr,
+                           0, st);
+        launch_build_wide((const hk_node*)c->buf[2], n_blas, c->blas_aux + n_blas, c->blas_aux + 2 * (size_t)n_blas,
+                          c->blas_wide, st);
+        (void)hipMemcpyAsync(c->walk_nodes[0], c->buf[2], (size_t)n_blas * sizeof(hk_node), hipMemcpyDeviceToDevice, st);
+        if (c->on(OPT_LEAF_COLLAPSE))
+            launch_collapse_leaves(c->walk_nodes[0], n_blas, c->blas_aux + n_blas, c->blas_aux + 2 * (size_t)n_blas,
+                                   c->collapse_scratch, st);
+    });
+    HK_HIP(c, hipGetLastError());
+    ml.device = (const uint32_t*)part[7];
+    return rebuild_instances(c, models, local_aabbs, count, st, &ml);
 }
 
 int hk_read_scene_array(hk_ctx* c, int array, void* dst, size_t bytes)

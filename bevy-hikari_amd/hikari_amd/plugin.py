@@ -228,6 +228,33 @@ class HikariRenderer:
         _check(self.ctx, self._L.hk_update_instances(self.ctx, m.ctypes.data, a.ctypes.data, len(m), _stream(stream)),
                "hk_update_instances")
 
+    def update_meshes(self, scene: Scene, mesh_ids, models=None, local_aabbs=None, stream=None) -> None:
+        """Deformed meshes of an uploaded scene (hk_update_meshes): the positions and normals of `scene.meshes[i]` for
+        each i in `mesh_ids` (same topology as uploaded) replace the uploaded ones on the GPU, which rebuilds those
+        meshes' primitives and BLAS and then everything update_instances rebuilds.  models / local_aabbs: as for
+        update_instances (default: the scene's instance_models() / instance_local_aabbs())."""
+        m = np.ascontiguousarray(scene.instance_models() if models is None else models, np.float32).reshape(-1, 16)
+        a = np.ascontiguousarray(scene.instance_local_aabbs() if local_aabbs is None else local_aabbs,
+                                 np.float32).reshape(-1, 6)
+        if len(m) != len(a):
+            raise ValueError("models and local_aabbs differ in length")
+        ups = (_abi.hk_mesh_update * max(1, len(mesh_ids)))()
+        keep = []
+        for u, i in zip(ups, mesh_ids):
+            mesh = scene.meshes[i]
+            p = np.ascontiguousarray(mesh.positions, np.float32).reshape(-1, 3)
+            n = None if mesh.normals is None else np.ascontiguousarray(mesh.normals, np.float32).reshape(-1, 3)
+            if n is not None and len(n) != len(p):
+                raise ValueError("positions and normals differ in length")
+            keep += [p, n]
+            v, pr, n0, nc = scene.mesh_index(i)
+            u.mesh = _abi.hk_mesh_index(v, pr, (C.c_uint32 * 2)(n0, nc))
+            u.vertex_count = len(p)
+            u.positions = p.ctypes.data
+            u.normals = None if n is None else n.ctypes.data
+        _check(self.ctx, self._L.hk_update_meshes(self.ctx, ups, len(mesh_ids), m.ctypes.data, a.ctypes.data, len(m),
+                                                  _stream(stream)), "hk_update_meshes")
+
     def scene_array(self, array: int, dtype, count: int) -> np.ndarray:
         """Device copy of group-2 scene array `array` (hk_scene_desc order) as `count` records."""
         out = np.empty(count, dtype)
@@ -443,6 +470,10 @@ class HikariPlugin:
             r.denoise(s, fi, stream)
         r.tone_sum(s, stream)
         self.frame_number += 1
+
+    def update_meshes(self, scene: Scene, mesh_ids, models=None, local_aabbs=None, stream=None) -> None:
+        """`prepare_mesh_assets` for modified meshes of unchanged topology (HikariRenderer.update_meshes)."""
+        self.renderer.update_meshes(scene, mesh_ids, models, local_aabbs, stream)
 
     def present(self, width: int = None, height: int = None, hdr: bool = False, viewport=None, stream=None):
         """The `Overlay` draw into a window-sized view target (overlay.rs:333-395): the plane the settings display,

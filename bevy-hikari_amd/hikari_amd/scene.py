@@ -402,6 +402,18 @@ class Scene:
         self.desc = d
         return d
 
+    def mesh_index(self, i: int) -> tuple:
+        """(vertex, primitive, node0, node_count) of mesh i: its slices of the vertex, primitive and asset-node arrays
+        as the builder concatenates the meshes (mesh.rs:140-163), from the meshes' own sizes: one primitive per three
+        indices of a list, index count - 2 of a strip, and 3k - 2 nodes over k primitives."""
+        def sizes(m):
+            n = len(m.positions) if m.indices is None else len(m.indices)
+            k = n - 2 if m.topology == 1 else n // 3
+            return len(m.positions), k, 3 * k - 2
+        before = [sizes(m) for m in self.meshes[:i]]
+        return (sum(s[0] for s in before), sum(s[1] for s in before), sum(s[2] for s in before),
+                sizes(self.meshes[i])[2])
+
     def instance_models(self) -> np.ndarray:
         """(n, 16) float32 column-major model matrices of the instances, in upload order."""
         return np.stack([col_major(m) for _, _, m in self.instances]).astype(np.float32)

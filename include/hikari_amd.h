@@ -256,6 +256,39 @@ int hk_set_noise(hk_ctx* ctx, const uint8_t* rgba8, uint32_t count, uint32_t siz
  * Bevy `Aabb`: center xyz, half_extents xyz).  count must equal the uploaded instance count
  * (same order, meshes and materials).  Waits for the stream once (singular-matrix check). */
 int hk_update_instances(hk_ctx* ctx, const float* models, const float* local_aabbs, uint32_t count, void* stream);
+
+/* Deforming meshes: what the reference does for `AssetEvent::Modified` (mesh.rs:77-166
+ * extract_mesh_assets / prepare_mesh_assets run GpuMesh::try_from again, mod.rs:379-467: vertices, primitives and a
+ * fresh bvh 0.7.1 BLAS; prepare_instances, instance.rs:284-437, then runs on the new mesh slices), ON THE GPU and in
+ * place, for meshes whose topology is unchanged: the primitives keep their stored vertex indices and the uvs stay.
+ * For each listed mesh the device rewrites hk_vertex.position and hk_vertex.normal of the slice (normals NULL: the
+ * uploaded normals stay), the three positions of each hk_primitive from the new vertices, and rebuilds the mesh's
+ * BLAS with the host builder's exact operations (hikari_scene.h hks_build: 6 buckets, node indices relative to the
+ * mesh; a subtree of k shapes is 3k - 2 nodes, so the node slice stays).  The triangles' shape boxes are folded from
+ * empty in vertex order 0, 1, 2 with the host's std::fmin / std::fmax, so a zero bound keeps the sign the host
+ * leaves.  The device-only derivatives of the asset nodes (leaf boxes, the G-buffer wide layout, the light walks'
+ * copy with its leaf collapse) are refreshed, and the G-buffer walk's stack bound becomes the TLAS depth plus the
+ * deepest instanced BLAS as rebuilt (a mesh that got shallower lowers it).  Then hk_update_instances' rebuild runs:
+ * instance records, TLAS, emissive areas, alias tables, emissive records and the light BVH; models and local_aabbs
+ * cover every instance in upload order exactly as there.  The reference reads the entity's `Aabb` component
+ * (instance.rs:193-206, 287-293), which Bevy 0.9 does not recompute when a mesh is modified: the caller supplies
+ * it, the library does not derive it.  Motion vectors keep their rule (current geometry against the previous
+ * models: prepass.wgsl has no previous-vertex input).  The result is bit-identical to hks_build + hk_scene_upload
+ * of the deformed scene.
+ * HK_ERR_INVALID with a message, the context unchanged and usable: a null pointer; count other than the instance
+ * count; a `mesh` that is not the slice of an instanced mesh of the uploaded scene; a slice whose node count is not
+ * 3k - 2 over k primitives of the scene; vertex_count not greater than every vertex index its primitives store, or
+ * reaching past the vertex array or into another instanced mesh's vertices; a mesh listed twice.  HK_ERR_STATE
+ * without a scene.  A singular model fails as in hk_update_instances (after the meshes were rebuilt).  Waits for the
+ * stream once. */
+typedef struct hk_mesh_update {
+    hk_mesh_index mesh;     /* the slice as the instances of this mesh carry it (vertex, primitive, node[2]) */
+    uint32_t vertex_count;
+    const float* positions; /* vertex_count x 3 */
+    const float* normals;   /* vertex_count x 3; NULL keeps the uploaded normals */
+} hk_mesh_update;
+int hk_update_meshes(hk_ctx* ctx, const hk_mesh_update* meshes, uint32_t mesh_count, const float* models,
+                     const float* local_aabbs, uint32_t count, void* stream);
 /* LDS staging of a scene, computed on the host with the launchers' own arithmetic (needs no device or context):
  * the bytes the traversal kernels of `plan` (0: the light passes' arrays, hk_scene_desc's nine; 1: the G-buffer
  * walk's vertices, primitives, instances and the two wide node layouts) copy into LDS, each array rounded up to
