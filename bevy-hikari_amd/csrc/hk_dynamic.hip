@@ -1,4 +1,5 @@
-// hk_dynamic.hip — dynamic instances and deforming meshes on the device.
+// hk_dynamic.hip — dynamic instances, deforming meshes and changed instance sets
+//  on the device.
 //
 // The reference re-runs `prepare_instances` on the CPU whenever a transform changes
 // (instance.rs:284-437: instance records with world AABBs and inverse-transpose models, the
@@ -631,6 +632,117 @@ __global__ __launch_bounds__(256) void k_update_instances(hk_instance* inst, uin
     boxes[i] = b;
 }
 
+// ---- a new instance set (instance.rs:123-175 InstanceEvent, 245-444 prepare_instances)
+// One thread per instance of the new set: k_update_instances' record with everything else an hk_instance holds (the
+// host memsets each record, and the buffer holds the records of the set before: material, a zeroed node_index for
+// k_backfill_nodes and the mesh slice are written too), the previous model gathered from the set before
+// (transform.rs:8-44: a surviving entity keeps the model the last G-buffer saw, a new one starts from its own), and
+// for k_compact_emitters whether the material emits (hk_scene.cpp hks_build: 255 a |rgb| > 0 in float, false for a
+// NaN) and the mesh's primitive count.  Material and previous indices were checked on the host (hk_set_instances).
+__global__ __launch_bounds__(256) void k_set_instances(hk_instance* inst, uint32_t n, const InstanceDesc* set,
+                                                       const float* models, const float* local_aabbs,
+                                                       const hk_material* mats, const float* prev_models,
+                                                       uint32_t n_prev, float* new_prev, BBox* boxes, uint2* emitter,
+                                                       uint32_t* singular)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const InstanceDesc d = set[i];
+    const float* m = models + 16u * (size_t)i;
+    const float* center = local_aabbs + 6u * (size_t)i;
+    const float* half = center + 3;
+    float c[3];
+    transform_point(m, center, c);
+    float mn[3] = {0.0f, 0.0f, 0.0f}, mx[3] = {0.0f, 0.0f, 0.0f};
+    for (int k = 0; k < 8; ++k) {
+        const float sx = (float)(2 * (k & 1) - 1), sy = (float)(2 * ((k >> 1) & 1) - 1), sz = (float)(2 * ((k >> 2) & 1) - 1);
+        const float v[3] = {half[0] * sx, half[1] * sy, half[2] * sz};
+        float corner[3];
+        transform_vector(m, v, corner);
+        for (int a = 0; a < 3; ++a) {
+            mn[a] = host_fmin(mn[a], corner[a]);
+            mx[a] = host_fmax(mx[a], corner[a]);
+        }
+    }
+    hk_instance g;
+    BBox b;
+    for (int a = 0; a < 3; ++a) {
+        g.min[a] = b.mn[a] = mn[a] + c[a];
+        g.max[a] = b.mx[a] = mx[a] + c[a];
+    }
+    g.material = d.material;
+    g.node_index = 0u;
+    for (int k = 0; k < 16; ++k) g.model[k] = m[k];
+    if (!inverse_transpose_d(m, g.inverse_transpose_model)) atomicOr(singular, 1u);
+    g.mesh = d.mesh;
+    inst[i] = g;
+    boxes[i] = b;
+    const float* pm = d.previous < n_prev ? prev_models + 16u * (size_t)d.previous : m;  // INSTANCE_NEW: its own
+    for (int k = 0; k < 16; ++k) new_prev[16u * (size_t)i + k] = pm[k];
+    const float* e = mats[d.material].emissive;
+    const float intensity = (255.0f * e[3]) * sqrtf((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+    emitter[i] = make_uint2(intensity > 0.0f ? 1u : 0u, (d.mesh.node[1] + 2u) / 3u);
+}
+
+// One workgroup walks the instances in index order, 256 per chunk: the emitters' ranks from wave ballots (as
+// coop_split and k_update_emissives rank), their alias offsets from an exclusive scan of the primitive counts over
+// the emitters (a __shfl_up scan per wave, the waves' totals through LDS, a running carry between chunks), and each
+// hk_emissive written whole: instance and alias range, everything else zero for k_update_emissives and
+// k_backfill_nodes to fill.  totals[0], [1]: emitters and alias entries, for the host to compare with its own
+// arithmetic; room: the records the host sized `em` for.  Integer arithmetic throughout.
+__global__ __launch_bounds__(256) void k_compact_emitters(const uint2* emitter, uint32_t n, hk_emissive* em,
+                                                          uint32_t room, uint32_t* totals)
+{
+    __shared__ uint32_t wave_n[4], wave_prims[4];
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    uint32_t rank_carry = 0, alias_carry = 0;
+    for (uint32_t base = 0; base < n; base += 256u) {
+        const uint32_t i = base + threadIdx.x;
+        const uint2 e = i < n ? emitter[i] : make_uint2(0u, 0u);
+        const bool emits = e.x != 0u;
+        const uint32_t prims = emits ? e.y : 0u;
+        const unsigned long long mask = __ballot(emits);
+        uint32_t incl = prims;  // inclusive scan over the wave
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t t = __shfl_up(incl, o, 64);
+            if (lane >= (uint32_t)o) incl += t;
+        }
+        if (lane == 63u) {
+            wave_n[w] = (uint32_t)__popcll(mask);
+            wave_prims[w] = incl;
+        }
+        __syncthreads();
+        uint32_t rank = rank_carry, offset = alias_carry;
+        for (uint32_t j = 0; j < w; ++j) {
+            rank += wave_n[j];
+            offset += wave_prims[j];
+        }
+        rank += (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+        offset += incl - prims;
+        if (emits && rank < room) {
+            hk_emissive r;
+            for (int k = 0; k < 4; ++k) r.emissive[k] = 0.0f;
+            for (int k = 0; k < 3; ++k) r.position[k] = 0.0f;
+            r.radius = 0.0f;
+            r.instance = i;
+            r._pad0 = 0u;
+            r.alias_table[0] = offset;
+            r.alias_table[1] = prims;
+            r.surface_area = 0.0f;
+            r.node_index = 0u;
+            r._pad1[0] = r._pad1[1] = 0u;
+            em[rank] = r;
+        }
+        rank_carry += (wave_n[0] + wave_n[1]) + (wave_n[2] + wave_n[3]);
+        alias_carry += (wave_prims[0] + wave_prims[1]) + (wave_prims[2] + wave_prims[3]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        totals[0] = rank_carry;
+        totals[1] = alias_carry;
+    }
+}
+
 // ---- emissive records + alias tables (instance.rs:377-420, mod.rs:318-376)
 struct AliasWork {
     uint32_t index;
@@ -745,11 +857,11 @@ __global__ __launch_bounds__(256) void k_backfill_nodes(const hk_node* tlas, uin
     if (i < n_lbvh && lbvh[i].entry_index >= HK_BVH_LEAF_FLAG) em[lbvh[i].entry_index - HK_BVH_LEAF_FLAG].node_index = i;
 }
 
-void launch_dynamic_update(const DynamicArgs& D, hipStream_t st)
+// what follows the instance records and their boxes: the TLAS, the emitters' areas, alias tables, records and light
+// BVH, and the leaf node indices
+static void launch_rebuild(const DynamicArgs& D, hipStream_t st)
 {
     const uint32_t n = D.n_instances;
-    hipLaunchKernelGGL(k_update_instances, dim3((n + 255u) / 256u), dim3(256), 0, st, D.instances, n, D.models,
-                       D.local_aabbs, (BBox*)D.boxes, D.flags);
     auto build = [&](uint32_t count, hk_node* out, uint32_t* levels) {
         if (count <= BVH_LDS_SHAPES)
             hipLaunchKernelGGL(k_build_bvh<true>, dim3(1), dim3(256), 0, st, (const BBox*)D.boxes, count, D.buckets, out,
@@ -769,6 +881,25 @@ void launch_dynamic_update(const DynamicArgs& D, hipStream_t st)
     const uint32_t m = 3u * n - 2u > 3u * D.n_emissives ? 3u * n - 2u : 3u * D.n_emissives;
     hipLaunchKernelGGL(k_backfill_nodes, dim3((m + 255u) / 256u), dim3(256), 0, st, D.tlas, 3u * n - 2u, D.instances,
                        D.lbvh, D.n_emissives ? 3u * D.n_emissives - 2u : 0u, D.emissives);
+}
+
+void launch_dynamic_update(const DynamicArgs& D, hipStream_t st)
+{
+    const uint32_t n = D.n_instances;
+    hipLaunchKernelGGL(k_update_instances, dim3((n + 255u) / 256u), dim3(256), 0, st, D.instances, n, D.models,
+                       D.local_aabbs, (BBox*)D.boxes, D.flags);
+    launch_rebuild(D, st);
+}
+
+void launch_set_instances(const DynamicArgs& D, const SetArgs& S, hipStream_t st)
+{
+    const uint32_t n = D.n_instances;
+    hipLaunchKernelGGL(k_set_instances, dim3((n + 255u) / 256u), dim3(256), 0, st, D.instances, n, S.set, D.models,
+                       D.local_aabbs, D.materials, S.prev_models, S.n_prev, S.new_prev, (BBox*)D.boxes, S.emitter,
+                       D.flags);
+    hipLaunchKernelGGL(k_compact_emitters, dim3(1), dim3(256), 0, st, (const uint2*)S.emitter, n, D.emissives,
+                       D.n_emissives, D.flags + 2);
+    launch_rebuild(D, st);
 }
 
 // tab: the LDS-sized meshes first (n_lds of them), then the others; levels[slot]: each mesh's split levels

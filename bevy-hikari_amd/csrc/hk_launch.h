@@ -144,9 +144,30 @@ struct DynamicArgs {
     void* boxes;               // max(n, m) x 24 B
     uint32_t* idx;             // 2 x max(n, m)
     void* segments;            // 2 x max(n, m) x 12 B
-    uint32_t* flags;           // [0] singular transform, [1] TLAS split levels (G-buffer stack bound)
+    uint32_t* flags;           // [0] singular transform, [1] TLAS split levels (G-buffer stack bound),
+                               // [2] emitters, [3] alias entries of a new instance set (launch_set_instances)
 };
 void launch_dynamic_update(const DynamicArgs& D, hipStream_t st);
+
+// A new instance set (hk_dynamic.hip): one record per instance, the layout of hk_instance_desc.
+struct InstanceDesc {
+    hk_mesh_index mesh;
+    uint32_t material;
+    uint32_t previous;  // index in the set before, or INSTANCE_NEW
+};
+constexpr uint32_t INSTANCE_NEW = 0xFFFFFFFFu;
+struct SetArgs {
+    const InstanceDesc* set;    // D.n_instances records
+    const float* prev_models;   // the previous models of the set before: n_prev x 16
+    uint32_t n_prev;
+    // scratch
+    float* new_prev;            // n x 16: the gathered previous models of the new set
+    uint2* emitter;             // n x (1 if the instance's material emits, its mesh's primitives)
+};
+// The instance records written whole from D.models / D.local_aabbs and S.set, the emissive records compacted in
+// instance order with their alias ranges (D.n_emissives and D.n_alias: the host's totals, the room in D.emissives and
+// D.alias; the device's own go to D.flags[2], [3]), then everything launch_dynamic_update rebuilds after its records.
+void launch_set_instances(const DynamicArgs& D, const SetArgs& S, hipStream_t st);
 
 // Deforming meshes (hk_dynamic.hip): one record per listed mesh, in a device table.
 struct MeshUpdate {

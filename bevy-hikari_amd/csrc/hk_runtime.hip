@@ -15,6 +15,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <map>
 #include <set>
 #include <string>
 #include <vector>
@@ -307,8 +308,15 @@ struct hk_ctx {
         hk_mesh_index index;
         uint32_t vertex_need;  // largest stored vertex index + 1; U32_MAX: the slices do not fit the arrays
         uint32_t depth;        // inner levels of its BLAS
+        uint32_t used = 0;     // instances of the current set that carry it (hk_set_instances can leave it none)
     };
     std::vector<MeshSlice> meshes;
+    // hk_set_instances: element capacities of the arrays it resizes (3, 4, 5, 7, 8; tlas_wide and walk_nodes[1]
+    // follow cap[5], prev_models follows cap[4]) and of collapse_scratch, and the materials' emissive as uploaded or
+    // last replaced (4 floats each: the host's emitter count)
+    size_t cap[9] = {};
+    size_t collapse_cap = 0;
+    std::vector<float> emissive;
     uint32_t* blas_aux = nullptr;
     void* mesh_scratch = nullptr;
     size_t mesh_bytes = 0;
@@ -1111,6 +1119,23 @@ static bool scene_desc_ok(const hk_scene_desc* d)
     return true;
 }
 
+// A mesh slice of a host-built scene as hk_update_meshes and hk_set_instances keep it: the vertices its primitives
+// index and its BLAS depth (the node range is inside the asset nodes)
+static hk_ctx::MeshSlice host_mesh_slice(const hk_scene_desc* d, const hk_mesh_index& m)
+{
+    hk_ctx::MeshSlice s{m, HK_U32_MAX, flat_depth((const hk_node*)d->asset_nodes.data + m.node[0], m.node[1])};
+    const uint32_t tris = (m.node[1] + 2u) / 3u;
+    if (m.node[1] && (m.node[1] + 2u) % 3u == 0 && (size_t)m.primitive + tris <= d->primitives.count &&
+        m.vertex < d->vertices.count) {
+        const hk_primitive* pr = (const hk_primitive*)d->primitives.data + m.primitive;
+        uint32_t top = 0;
+        for (uint32_t t = 0; t < tris; ++t)
+            for (int v = 0; v < 3; ++v) top = std::max(top, pr[t].vertices[v].index);
+        if (top < d->vertices.count - m.vertex) s.vertex_need = top + 1u;
+    }
+    return s;
+}
+
 int hk_scene_stage_bytes(const hk_scene_desc* d, int plan, uint32_t* bytes, uint32_t* limit)
 {
     if (!d || (plan != PLAN_LIGHT && plan != PLAN_GBUFFER)) return HK_ERR_INVALID;
@@ -1168,7 +1193,11 @@ int hk_scene_upload(hk_ctx* c, const hk_scene_desc* d)
         HK_HIP(c, hipMemset(c->buf[i], 0, bytes));
         if (arr[i]->count) HK_HIP(c, hipMemcpy(c->buf[i], arr[i]->data, arr[i]->count * elem[i], hipMemcpyHostToDevice));
         c->count[i] = arr[i]->count;
+        c->cap[i] = arr[i]->count ? arr[i]->count : 1;
     }
+    c->emissive.resize(4 * (size_t)d->materials.count);
+    for (uint32_t k = 0; k < d->materials.count; ++k)
+        std::memcpy(&c->emissive[4 * (size_t)k], ((const hk_material*)d->materials.data)[k].emissive, 16);
     // leaf boxes of the device node copies (see k_fill_blas_leaves) and the wide layout of the
     // G-buffer traversal: BLAS node -> primitive offset / node range of the mesh that owns it,
     // from the instances' mesh indices
@@ -1188,21 +1217,12 @@ int hk_scene_upload(hk_ctx* c, const hk_scene_desc* d)
     // the instanced meshes, for hk_update_meshes: each distinct slice once, with the vertices its primitives index
     // and its BLAS depth (gb_blas_depth is the maximum of these)
     c->meshes.clear();
-    std::set<std::array<uint32_t, 4>> seen;
+    std::map<std::array<uint32_t, 4>, size_t> seen;
     for (uint32_t k = 0; k < d->instances.count; ++k) {
         const hk_mesh_index& m = inst[k].mesh;
-        if (!seen.insert({m.vertex, m.primitive, m.node[0], m.node[1]}).second) continue;
-        hk_ctx::MeshSlice s{m, HK_U32_MAX, flat_depth((const hk_node*)d->asset_nodes.data + m.node[0], m.node[1])};
-        const uint32_t tris = (m.node[1] + 2u) / 3u;
-        if (m.node[1] && (m.node[1] + 2u) % 3u == 0 && (size_t)m.primitive + tris <= d->primitives.count &&
-            m.vertex < d->vertices.count) {
-            const hk_primitive* pr = (const hk_primitive*)d->primitives.data + m.primitive;
-            uint32_t top = 0;
-            for (uint32_t t = 0; t < tris; ++t)
-                for (int v = 0; v < 3; ++v) top = std::max(top, pr[t].vertices[v].index);
-            if (top < d->vertices.count - m.vertex) s.vertex_need = top + 1u;
-        }
-        c->meshes.push_back(s);
+        const auto at = seen.emplace(std::array<uint32_t, 4>{m.vertex, m.primitive, m.node[0], m.node[1]}, c->meshes.size());
+        if (at.second) c->meshes.push_back(host_mesh_slice(d, m));
+        c->meshes[at.first->second].used++;
     }
     release(c->dyn_scratch);
     c->dyn_bytes = 0;
@@ -1235,7 +1255,8 @@ int hk_scene_upload(hk_ctx* c, const hk_scene_desc* d)
     // uploaded (hk_read_scene_array, the wide layout and hk_update_instances read them)
     HK_HIP(c, hipMalloc(&c->walk_nodes[0], (size_t)(n_blas ? n_blas : 1) * sizeof(hk_node)));
     HK_HIP(c, hipMalloc(&c->walk_nodes[1], (size_t)(n_tlas ? n_tlas : 1) * sizeof(hk_node)));
-    HK_HIP(c, hipMalloc(&c->collapse_scratch, (size_t)std::max<uint32_t>(1u, std::max(n_blas, n_tlas)) * 4));
+    c->collapse_cap = std::max<uint32_t>(1u, std::max(n_blas, n_tlas));
+    HK_HIP(c, hipMalloc(&c->collapse_scratch, c->collapse_cap * 4));
     HK_HIP(c, hipMemcpyAsync(c->walk_nodes[0], c->buf[2], (size_t)n_blas * sizeof(hk_node), hipMemcpyDeviceToDevice,
                              c->stream));
     HK_HIP(c, hipMemcpyAsync(c->walk_nodes[1], c->buf[5], (size_t)n_tlas * sizeof(hk_node), hipMemcpyDeviceToDevice,
@@ -1263,35 +1284,274 @@ struct MeshLevels {
     std::vector<uint32_t> slice;  // c->meshes index of each listed mesh
 };
 
-// The instance rebuild on `st` (after the mesh rebuild of hk_update_meshes, if any) and its one wait
+// What hk_set_instances decided on the host before the rebuild (plan_instance_set): the new set, the nine counts
+// after it, and the mesh slice each instance carries
+struct SetChange {
+    const hk_instance_desc* set = nullptr;
+    const hk_material* materials = nullptr;  // all count[6] records, or null: the materials stay
+    uint32_t counts[9] = {};
+    std::vector<uint32_t> slice;             // per instance: its index in the known slices followed by `fresh`
+    std::vector<hk_ctx::MeshSlice> fresh;    // the slices to register, in the order of their first use
+};
+
+// Where the host arithmetic reads a slice's primitives and nodes: a host-built scene, or a context's device arrays
+struct SliceReader {
+    const hk_scene_desc* desc;
+    const hk_ctx* ctx;
+    bool read(int array, uint32_t first, uint32_t n, void* dst) const
+    {
+        const size_t elem = SCENE_ELEM[array], at = (size_t)first * elem, bytes = (size_t)n * elem;
+        if (desc) {
+            std::memcpy(dst, (const char*)(array == 1 ? desc->primitives.data : desc->asset_nodes.data) + at, bytes);
+            return true;
+        }
+        return hipMemcpy(dst, (const char*)ctx->buf[array] + at, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+};
+
+static bool ranges_meet(size_t a, size_t na, size_t b, size_t nb) { return a < b + nb && b < a + na; }
+
+// A slice no instance has carried so far (hikari_amd.h hk_set_instances "mesh"): its shape against the array counts,
+// against every slice known so far, and what upload records for an instanced mesh.  `why` says what failed.
+static int check_new_slice(const hk_mesh_index& x, const uint32_t* count, const std::vector<hk_ctx::MeshSlice>& known,
+                           const std::vector<hk_ctx::MeshSlice>& fresh, const SliceReader& rd, hk_ctx::MeshSlice* out,
+                           std::string* why)
+{
+    const uint32_t nc = x.node[1], k = (nc + 2u) / 3u;
+    auto no = [&](const char* text) {
+        *why = text;
+        return HK_ERR_INVALID;
+    };
+    if (nc == 0 || (nc + 2u) % 3u != 0) return no("its BLAS is not 3k - 2 nodes over k primitives");
+    if ((size_t)x.primitive + k > count[1]) return no("its primitives reach past the primitive array");
+    if ((size_t)x.node[0] + nc > count[2]) return no("its nodes reach past the asset nodes");
+    if (x.vertex >= count[0]) return no("its vertices begin past the vertex array");
+    for (const std::vector<hk_ctx::MeshSlice>* list : {&known, &fresh})
+        for (const hk_ctx::MeshSlice& o : *list)
+            if (ranges_meet(x.primitive, k, o.index.primitive, (o.index.node[1] + 2u) / 3u) ||
+                ranges_meet(x.node[0], nc, o.index.node[0], o.index.node[1]))
+                return no("it partly overlaps another mesh slice");
+    std::vector<hk_primitive> prims(k);
+    std::vector<hk_node> nodes(nc);
+    if (!rd.read(1, x.primitive, k, prims.data()) || !rd.read(2, x.node[0], nc, nodes.data())) {
+        *why = "its primitives and nodes could not be read back";
+        return HK_ERR_HIP;
+    }
+    uint32_t top = 0;
+    for (const hk_primitive& p : prims)
+        for (int v = 0; v < 3; ++v) top = std::max(top, p.vertices[v].index);
+    if (top >= count[0] - x.vertex) return no("its vertex indices reach past the vertex array");
+    for (const std::vector<hk_ctx::MeshSlice>* list : {&known, &fresh})
+        for (const hk_ctx::MeshSlice& o : *list)
+            if (o.vertex_need != HK_U32_MAX && ranges_meet(x.vertex, top + 1u, o.index.vertex, o.vertex_need))
+                return no("its vertices overlap another mesh slice's");
+    *out = hk_ctx::MeshSlice{x, top + 1u, flat_depth(nodes.data(), nc)};
+    return HK_OK;
+}
+
+// hks_build's emitter test (hk_scene.cpp: 255 a |rgb| > 0 in float; false for a NaN), as k_set_instances evaluates it
+static bool material_emits(const float* e)
+{
+    const float intensity = (255.0f * e[3]) * std::sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+    return intensity > 0.0f;
+}
+
+// The host arithmetic of a new instance set: every refusal that needs no device, the slices to register and the nine
+// counts after the set (count: the counts before; emissive: 4 floats per material)
+static int plan_instance_set(const uint32_t* count, const std::vector<hk_ctx::MeshSlice>& known, const float* emissive,
+                             const hk_instance_desc* set, uint32_t n, const SliceReader& rd, SetChange* out,
+                             std::string* why)
+{
+    if (n == 0) {
+        *why = "an empty instance set (hk_scene_upload refuses an empty scene too)";
+        return HK_ERR_INVALID;
+    }
+    if (n > 0x20000000u) {
+        *why = "too many instances";
+        return HK_ERR_INVALID;
+    }
+    std::map<std::array<uint32_t, 4>, uint32_t> at;
+    for (size_t k = 0; k < known.size(); ++k) {
+        const hk_mesh_index& m = known[k].index;
+        at.emplace(std::array<uint32_t, 4>{m.vertex, m.primitive, m.node[0], m.node[1]}, (uint32_t)k);
+    }
+    out->set = set;
+    out->slice.resize(n);
+    out->fresh.clear();
+    uint64_t n_em = 0, n_alias = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const hk_instance_desc& d = set[i];
+        const std::string who = "instance " + std::to_string(i) + ": ";
+        if (d.material >= count[6]) {
+            *why = who + "material index out of range";
+            return HK_ERR_INVALID;
+        }
+        const std::array<uint32_t, 4> key{d.mesh.vertex, d.mesh.primitive, d.mesh.node[0], d.mesh.node[1]};
+        auto it = at.find(key);
+        if (it == at.end()) {
+            hk_ctx::MeshSlice f;
+            std::string text;
+            const int rc = check_new_slice(d.mesh, count, known, out->fresh, rd, &f, &text);
+            if (rc != HK_OK) {
+                *why = who + "mesh slice refused: " + text;
+                return rc;
+            }
+            it = at.emplace(key, (uint32_t)(known.size() + out->fresh.size())).first;
+            out->fresh.push_back(f);
+        }
+        out->slice[i] = it->second;
+        if (material_emits(emissive + 4 * (size_t)d.material)) {
+            n_em++;
+            n_alias += (d.mesh.node[1] + 2u) / 3u;
+        }
+    }
+    if (n_alias > 0x40000000u) {
+        *why = "too many alias entries";
+        return HK_ERR_INVALID;
+    }
+    std::memcpy(out->counts, count, sizeof(out->counts));
+    out->counts[3] = (uint32_t)n_alias;
+    out->counts[4] = n;
+    out->counts[5] = 3u * n - 2u;
+    out->counts[7] = n_em ? 3u * (uint32_t)n_em - 2u : 0u;
+    out->counts[8] = (uint32_t)n_em;
+    return HK_OK;
+}
+
+// device-only derivatives of the asset nodes, over the whole array: leaf boxes, the G-buffer wide layout and the light
+// walks' copy with its leaf collapse (as hk_scene_upload derives them)
+static void refresh_blas_derivatives(hk_ctx* c, hipStream_t st)
+{
+    const uint32_t n_blas = c->count[2];
+    launch_fill_leaves((hk_node*)c->buf[2], n_blas, c->blas_aux, (const hk_primitive*)c->buf[1], nullptr, 0, nullptr, 0,
+                       st);
+    launch_build_wide((const hk_node*)c->buf[2], n_blas, c->blas_aux + n_blas, c->blas_aux + 2 * (size_t)n_blas,
+                      c->blas_wide, st);
+    (void)hipMemcpyAsync(c->walk_nodes[0], c->buf[2], (size_t)n_blas * sizeof(hk_node), hipMemcpyDeviceToDevice, st);
+    if (c->on(OPT_LEAF_COLLAPSE))
+        launch_collapse_leaves(c->walk_nodes[0], n_blas, c->blas_aux + n_blas, c->blas_aux + 2 * (size_t)n_blas,
+                               c->collapse_scratch, st);
+}
+
+// Room for the counts of a new set (hikari_amd.h hk_set_instances "Capacity"): an array whose count passes its
+// capacity is allocated anew, zeroed, at max(count, 1.5 x capacity); its records are all rewritten by the rebuild.
+// *old_prev: the previous models of the set before, where they moved (the gather reads them; the caller frees).
+static int reserve_set(hk_ctx* c, const uint32_t* counts, float** old_prev)
+{
+    auto grown = [](size_t need, size_t cap) { return std::max(need, cap + cap / 2); };
+    auto fresh = [&](void** p, size_t bytes) {
+        void* nb = nullptr;
+        if (hipMalloc(&nb, bytes) != hipSuccess) return false;
+        if (hipMemset(nb, 0, bytes) != hipSuccess) {
+            (void)hipFree(nb);
+            return false;
+        }
+        if (*p) (void)hipFree(*p);
+        *p = nb;
+        return true;
+    };
+    for (int i : {3, 4, 5, 7, 8}) {
+        if (counts[i] <= c->cap[i]) continue;
+        const size_t cap = grown(counts[i], c->cap[i]);
+        bool ok = true;
+        if (i == 5)
+            ok = fresh((void**)&c->tlas_wide, cap * WIDE_NODE_BYTES) && fresh((void**)&c->walk_nodes[1], cap * sizeof(hk_node));
+        if (i == 4) {
+            void* np = nullptr;
+            ok = fresh(&np, cap * 64);
+            if (ok) {
+                *old_prev = c->prev_models;
+                c->prev_models = (float*)np;
+            }
+        }
+        if (!ok || !fresh(&c->buf[i], staged_alloc_bytes(cap, SCENE_ELEM[i])))
+            return fail(c, HK_ERR_HIP, "hk_set_instances: out of device memory");
+        c->cap[i] = cap;
+    }
+    const size_t need = std::max<size_t>(1, std::max(c->count[2], counts[5]));
+    if (need > c->collapse_cap) {
+        const size_t cap = grown(need, c->collapse_cap);
+        if (!fresh((void**)&c->collapse_scratch, cap * 4)) return fail(c, HK_ERR_HIP, "hk_set_instances: out of device memory");
+        c->collapse_cap = cap;
+    }
+    return HK_OK;
+}
+
+// The instance rebuild on `st` (after the mesh rebuild of hk_update_meshes, if any) and its one wait: the one body of
+// hk_update_instances, hk_update_meshes and hk_set_instances.  set: the new instance set that replaces the current one
+// (null: the current set with new models).
 static int rebuild_instances(hk_ctx* c, const float* models, const float* local_aabbs, uint32_t count, hipStream_t st,
-                             const MeshLevels* ml)
+                             const MeshLevels* ml, const SetChange* set = nullptr)
 {
     HK_TRY(c->sch.gb_join(st));
     HK_TRY(c->sch.gb_serialize(false));
     c->gen++;
+    struct Moved {  // the previous models of the set before, where reserve_set moved them: freed on every way out
+        float* p = nullptr;
+        ~Moved() { release(p); }
+    } old_prev;
+    const uint32_t n_before = c->count[4];
+    if (set) {
+        HK_TRY(reserve_set(c, set->counts, &old_prev.p));
+        if (!set->fresh.empty()) {  // register the new slices: their rows of the per-node mesh tables, then the derivatives
+            const uint32_t n_blas = c->count[2];
+            for (const hk_ctx::MeshSlice& f : set->fresh) {
+                const hk_mesh_index& x = f.index;
+                const uint32_t value[3] = {x.primitive, x.node[0], x.node[1]};
+                std::vector<uint32_t> row(x.node[1]);
+                for (int k = 0; k < 3; ++k) {
+                    std::fill(row.begin(), row.end(), value[k]);
+                    HK_HIP(c, hipMemcpy(c->blas_aux + k * (size_t)n_blas + x.node[0], row.data(), row.size() * 4,
+                                        hipMemcpyHostToDevice));
+                }
+                c->meshes.push_back(f);
+            }
+            refresh_blas_derivatives(c, st);
+        }
+        for (hk_ctx::MeshSlice& s : c->meshes) s.used = 0;
+        for (uint32_t k : set->slice) c->meshes[k].used++;
+        c->gb_blas_depth = 0;
+        for (const hk_ctx::MeshSlice& s : c->meshes)
+            if (s.used) c->gb_blas_depth = std::max(c->gb_blas_depth, s.depth);
+        for (int i : {3, 4, 5, 7, 8}) {
+            c->count[i] = set->counts[i];
+            // staged_alloc_bytes' zeroed tail behind the new count (an empty array keeps one zeroed element)
+            const size_t at = (size_t)c->count[i] * SCENE_ELEM[i], end = staged_alloc_bytes(c->count[i], SCENE_ELEM[i]);
+            if (end > at) HK_HIP(c, hipMemsetAsync((char*)c->buf[i] + at, 0, end - at, st));
+        }
+        if (set->materials) {
+            for (uint32_t k = 0; k < c->count[6]; ++k) std::memcpy(&c->emissive[4 * (size_t)k], set->materials[k].emissive, 16);
+            HK_HIP(c, hipMemcpyAsync(c->buf[6], set->materials, (size_t)c->count[6] * sizeof(hk_material),
+                                     hipMemcpyHostToDevice, st));
+        }
+    }
     const uint32_t n = count, m = c->count[8], n_alias = c->count[3];
     const uint32_t nm = n > m ? n : m;
+    const size_t ns = set ? n : 0;  // (scratch of a set change only)
     auto align = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t sz[] = {align((size_t)n * 64), align((size_t)n * 24), align((size_t)(n_alias ? n_alias : 1) * 4),
                          align((size_t)(n_alias ? n_alias : 1) * 16), align((size_t)nm * 24), align((size_t)nm * 8),
-                         align((size_t)nm * 24), align((size_t)3 * n * 4), align(16)};
+                         align((size_t)nm * 24), align((size_t)3 * n * 4), align(16),
+                         align(ns * sizeof(InstanceDesc)), align(ns * 64), align(ns * 8)};
+    constexpr int PARTS = sizeof(sz) / sizeof(sz[0]);
     size_t total = 0;
     for (size_t b : sz) total += b;
     if (c->dyn_bytes < total) {
         release(c->dyn_scratch);
+        c->dyn_bytes = 0;
         HK_HIP(c, hipMalloc(&c->dyn_scratch, total));
         c->dyn_bytes = total;
     }
     char* p = (char*)c->dyn_scratch;
-    char* part[9];
-    for (int k = 0; k < 9; ++k) {
+    char* part[PARTS];
+    for (int k = 0; k < PARTS; ++k) {
         part[k] = p;
         p += sz[k];
     }
     HK_HIP(c, hipMemcpyAsync(part[0], models, (size_t)n * 64, hipMemcpyHostToDevice, st));
     HK_HIP(c, hipMemcpyAsync(part[1], local_aabbs, (size_t)n * 24, hipMemcpyHostToDevice, st));
     HK_HIP(c, hipMemsetAsync(part[8], 0, 16, st));
+    if (set) HK_HIP(c, hipMemcpyAsync(part[9], set->set, (size_t)n * sizeof(InstanceDesc), hipMemcpyHostToDevice, st));
     DynamicArgs D;
     D.instances = (hk_instance*)c->buf[4];
     D.n_instances = n;
@@ -1312,8 +1572,19 @@ static int rebuild_instances(hk_ctx* c, const float* models, const float* local_
     D.idx = (uint32_t*)part[5];
     D.segments = part[6];
     D.flags = (uint32_t*)part[8];
-    timed(c, "update_instances", st, [&] {
-        launch_dynamic_update(D, st);
+    SetArgs S;
+    S.set = (const InstanceDesc*)part[9];
+    S.prev_models = old_prev.p ? old_prev.p : c->prev_models;
+    S.n_prev = n_before;
+    S.new_prev = (float*)part[10];
+    S.emitter = (uint2*)part[11];
+    timed(c, set ? "set_instances" : "update_instances", st, [&] {
+        if (set) {
+            launch_set_instances(D, S, st);
+            (void)hipMemcpyAsync(c->prev_models, S.new_prev, (size_t)n * 64, hipMemcpyDeviceToDevice, st);
+        } else {
+            launch_dynamic_update(D, st);
+        }
         // device-only derivatives of the TLAS: leaf boxes and the G-buffer wide layout
         launch_fill_leaves(nullptr, 0, nullptr, nullptr, (hk_node*)c->buf[5], c->count[5], (const hk_instance*)c->buf[4],
                            n, st);
@@ -1324,17 +1595,22 @@ static int rebuild_instances(hk_ctx* c, const float* models, const float* local_
             launch_collapse_leaves(c->walk_nodes[1], c->count[5], nullptr, nullptr, c->collapse_scratch, st);
     });
     HK_HIP(c, hipGetLastError());
-    uint32_t flags[2] = {0, 0};
+    uint32_t flags[4] = {0, 0, 0, 0};
     std::vector<uint32_t> levels(ml ? ml->slice.size() : 0);
-    HK_HIP(c, hipMemcpyAsync(flags, part[8], 8, hipMemcpyDeviceToHost, st));
+    HK_HIP(c, hipMemcpyAsync(flags, part[8], 16, hipMemcpyDeviceToHost, st));
     if (ml) HK_HIP(c, hipMemcpyAsync(levels.data(), ml->device, levels.size() * 4, hipMemcpyDeviceToHost, st));
     HK_HIP(c, hipStreamSynchronize(st));
     if (ml) {  // the deepest instanced BLAS now: a mesh that became shallower lowers the bound
         for (size_t k = 0; k < levels.size(); ++k) c->meshes[ml->slice[k]].depth = levels[k];
         c->gb_blas_depth = 0;
-        for (const hk_ctx::MeshSlice& s : c->meshes) c->gb_blas_depth = std::max(c->gb_blas_depth, s.depth);
-        c->gb_stack_need = flags[1] + c->gb_blas_depth;
+        for (const hk_ctx::MeshSlice& s : c->meshes)
+            if (s.used) c->gb_blas_depth = std::max(c->gb_blas_depth, s.depth);
     }
+    if (ml || set) c->gb_stack_need = flags[1] + c->gb_blas_depth;
+    if (set && (flags[2] != m || flags[3] != n_alias))
+        return fail(c, HK_ERR_HIP, "hk_set_instances: the device counted " + std::to_string(flags[2]) + " emitters and " +
+                                       std::to_string(flags[3]) + " alias entries, the host " + std::to_string(m) +
+                                       " and " + std::to_string(n_alias));
     if (flags[0]) return fail(c, HK_ERR_INVALID, "singular instance transform");
     c->gb_stack_need = flags[1] + c->gb_blas_depth;
     c->models_dirty = true;  // the next G-buffer reads the models before this update as the previous ones
@@ -1453,23 +1729,81 @@ int hk_update_meshes(hk_ctx* c, const hk_mesh_update* meshes, uint32_t mesh_coun
     M.idx = (uint32_t*)part[5];
     M.segments = part[6];
     M.levels = (uint32_t*)part[7];
-    const uint32_t n_blas = c->count[2];
     timed(c, "update_meshes", st, [&] {
         launch_mesh_update(M, st);
-        // device-only derivatives of the asset nodes, over the whole array: leaf boxes, the G-buffer wide layout and
-        // the light walks' copy with its leaf collapse (as hk_scene_upload derives them)
-        launch_fill_leaves((hk_node*)c->buf[2], n_blas, c->blas_aux, (const hk_primitive*)c->buf[1], nullptr, 0, nullptr,
-                           0, st);
-        launch_build_wide((const hk_node*)c->buf[2], n_blas, c->blas_aux + n_blas, c->blas_aux + 2 * (size_t)n_blas,
-                          c->blas_wide, st);
-        (void)hipMemcpyAsync(c->walk_nodes[0], c->buf[2], (size_t)n_blas * sizeof(hk_node), hipMemcpyDeviceToDevice, st);
-        if (c->on(OPT_LEAF_COLLAPSE))
-            launch_collapse_leaves(c->walk_nodes[0], n_blas, c->blas_aux + n_blas, c->blas_aux + 2 * (size_t)n_blas,
-                                   c->collapse_scratch, st);
+        refresh_blas_derivatives(c, st);
     });
     HK_HIP(c, hipGetLastError());
     ml.device = (const uint32_t*)part[7];
     return rebuild_instances(c, models, local_aabbs, count, st, &ml);
+}
+
+int hk_set_instances(hk_ctx* c, const hk_instance_desc* set, const float* models, const float* local_aabbs,
+                     uint32_t count, const hk_material* materials, void* stream)
+{
+    if (!c) return HK_ERR_INVALID;
+    if (!set || !models || !local_aabbs) return fail(c, HK_ERR_INVALID, "hk_set_instances: null pointer");
+    if (!c->has_scene) return fail(c, HK_ERR_STATE, "no scene uploaded (hk_scene_upload)");
+    if (c->count[5] != 3u * c->count[4] - 2u || (c->count[8] && c->count[7] != 3u * c->count[8] - 2u))
+        return fail(c, HK_ERR_STATE, "scene BVHs are not bvh-0.7.1 flattened (3n - 2 nodes); cannot rebuild");
+    // the previous indices against the set before
+    std::vector<bool> taken(c->count[4], false);
+    for (uint32_t i = 0; i < count; ++i) {
+        const uint32_t p = set[i].previous;
+        if (p == HK_INSTANCE_NEW) continue;
+        if (p >= c->count[4])
+            return fail(c, HK_ERR_INVALID, "hk_set_instances: instance " + std::to_string(i) + ": previous is not an index of the set before");
+        if (taken[p])
+            return fail(c, HK_ERR_INVALID, "hk_set_instances: instance " + std::to_string(i) + ": previous is used twice");
+        taken[p] = true;
+    }
+    (void)hipSetDevice(c->device);
+    std::vector<float> emissive;
+    if (materials) {
+        emissive.resize(4 * (size_t)c->count[6]);
+        for (uint32_t k = 0; k < c->count[6]; ++k) std::memcpy(&emissive[4 * (size_t)k], materials[k].emissive, 16);
+    }
+    SetChange change;
+    std::string why;
+    const int rc = plan_instance_set(c->count, c->meshes, materials ? emissive.data() : c->emissive.data(), set, count,
+                                     SliceReader{nullptr, c}, &change, &why);
+    if (rc != HK_OK) return fail(c, rc, "hk_set_instances: " + why);
+    change.materials = materials;
+    return rebuild_instances(c, models, local_aabbs, count, pick(c, stream), nullptr, &change);
+}
+
+int hk_scene_counts(const hk_ctx* c, uint32_t counts[9])
+{
+    if (!c || !counts) return HK_ERR_INVALID;
+    if (!c->has_scene) return HK_ERR_STATE;
+    std::memcpy(counts, c->count, sizeof(c->count));
+    return HK_OK;
+}
+
+int hk_instance_set_counts(const hk_scene_desc* d, const hk_instance_desc* set, uint32_t count,
+                           const hk_material* materials, uint32_t counts[9])
+{
+    if (!d || !set || !counts || !scene_desc_ok(d)) return HK_ERR_INVALID;
+    const uint32_t before[9] = {d->vertices.count,  d->primitives.count,     d->asset_nodes.count,
+                                d->alias_table.count, d->instances.count,    d->instance_nodes.count,
+                                d->materials.count, d->emissive_nodes.count, d->emissives.count};
+    std::vector<hk_ctx::MeshSlice> known;
+    std::set<std::array<uint32_t, 4>> seen;
+    const hk_instance* inst = (const hk_instance*)d->instances.data;
+    for (uint32_t k = 0; k < d->instances.count; ++k) {
+        const hk_mesh_index& m = inst[k].mesh;
+        if ((size_t)m.node[0] + m.node[1] > d->asset_nodes.count) return HK_ERR_INVALID;
+        if (seen.insert({m.vertex, m.primitive, m.node[0], m.node[1]}).second) known.push_back(host_mesh_slice(d, m));
+    }
+    std::vector<float> emissive(4 * (size_t)d->materials.count);
+    const hk_material* mats = materials ? materials : (const hk_material*)d->materials.data;
+    for (uint32_t k = 0; k < d->materials.count; ++k) std::memcpy(&emissive[4 * (size_t)k], mats[k].emissive, 16);
+    SetChange change;
+    std::string why;
+    const int rc = plan_instance_set(before, known, emissive.data(), set, count, SliceReader{d, nullptr}, &change, &why);
+    if (rc != HK_OK) return rc;
+    std::memcpy(counts, change.counts, sizeof(change.counts));
+    return HK_OK;
 }
 
 int hk_read_scene_array(hk_ctx* c, int array, void* dst, size_t bytes)

@@ -61,6 +61,14 @@ class hk_mesh_update(C.Structure):
                 ("normals", C.c_void_p)]
 
 
+HK_INSTANCE_NEW = 0xFFFFFFFF
+
+
+class hk_instance_desc(C.Structure):
+    """include/hikari_amd.h hk_instance_desc (one instance of hk_set_instances' new set)."""
+    _fields_ = [("mesh", hk_mesh_index), ("material", C.c_uint32), ("previous", C.c_uint32)]
+
+
 class hk_texture(C.Structure):
     """include/hikari_amd.h hk_texture (one GpuImage level 0 + its sampler)."""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("format", C.c_uint32), ("address_u", C.c_uint32),
@@ -196,6 +204,9 @@ def lib() -> C.CDLL:
         "hk_get_present": (i32, [vp, vp, C.c_size_t, i32, vp]),
         "hk_update_instances": (i32, [vp, vp, vp, u32, vp]),
         "hk_update_meshes": (i32, [vp, C.POINTER(hk_mesh_update), u32, vp, vp, u32, vp]),
+        "hk_set_instances": (i32, [vp, C.POINTER(hk_instance_desc), vp, vp, u32, vp, vp]),
+        "hk_scene_counts": (i32, [vp, C.POINTER(u32)]),
+        "hk_instance_set_counts": (i32, [C.POINTER(hk_scene_desc), C.POINTER(hk_instance_desc), u32, vp, C.POINTER(u32)]),
         "hk_read_scene_array": (i32, [vp, i32, vp, C.c_size_t]),
         "hk_resolve_accumulation": (i32, [vp, vp]),
         "hk_output_info": (i32, [vp, i32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]),
@@ -239,7 +250,7 @@ EXPORTED_SYMBOLS = [
     "hk_get_option", "hk_option_name", "hk_scene_upload", "hk_scene_stage_bytes", "hk_scene_indirect_lds",
     "hk_scene_gbuffer_stack",
     "hk_set_noise", "hk_texture_upload", "hk_resize", "hk_resize_striped", "hk_set_band_halo", "hk_band_info", "hk_band_window_grow", "hk_reservoir_rows", "hk_resize_tile", "hk_tile_info", "hk_copy_output_rect", "hk_copy_output_rows", "hk_render_gbuffer", "hk_set_gbuffer_plane", "hk_render_frame",
-    "hk_denoise", "hk_tone_sum", "hk_update_instances", "hk_update_meshes", "hk_read_scene_array", "hk_post_process", "hk_set_fsr1_sharpness", "hk_present", "hk_present_info", "hk_get_present", "hk_accumulate", "hk_resolve_accumulation", "hk_output_info", "hk_get_output", "hk_output_device_ptr", "hk_sync", "hk_set_wavefront", "hk_lane_stats", "hk_dump_reservoirs",
+    "hk_denoise", "hk_tone_sum", "hk_update_instances", "hk_update_meshes", "hk_set_instances", "hk_scene_counts", "hk_instance_set_counts", "hk_read_scene_array", "hk_post_process", "hk_set_fsr1_sharpness", "hk_present", "hk_present_info", "hk_get_present", "hk_accumulate", "hk_resolve_accumulation", "hk_output_info", "hk_get_output", "hk_output_device_ptr", "hk_sync", "hk_set_wavefront", "hk_lane_stats", "hk_dump_reservoirs",
     "hk_load_reservoirs", "hk_reset_counters", "hk_read_counters", "hk_enable_kernel_timing", "hk_kernel_timing", "hk_set_kernel_timing_interval",
     "hk_trace", "hk_selftest_f16", "hk_selftest_div", "hk_selftest_rcp", "hk_selftest_count", "hks_create", "hks_destroy", "hks_last_error", "hks_add_mesh", "hks_add_material",
     "hks_add_instance", "hks_build", "hks_get_desc",

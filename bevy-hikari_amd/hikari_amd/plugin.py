@@ -73,6 +73,42 @@ def scene_gbuffer_stack(scene):
     return n.value, lv.value
 
 
+def instance_descs(scene: Scene, previous=None):
+    """ctypes array of hk_instance_desc for the instance list of `scene`: each instance's mesh slice
+    (Scene.mesh_index), its material and its index in the set before (`previous`: one entry per instance, None or
+    HK_INSTANCE_NEW for a new entity; previous=None: every entity is new)."""
+    n = len(scene.instances)
+    if previous is not None and len(previous) != n:
+        raise ValueError("previous needs one entry per instance")
+    out = (_abi.hk_instance_desc * max(1, n))()
+    slices = {}
+    for k, (mesh, mat, _) in enumerate(scene.instances):
+        if mesh not in slices:
+            v, pr, n0, nc = scene.mesh_index(mesh)
+            slices[mesh] = _abi.hk_mesh_index(v, pr, (C.c_uint32 * 2)(n0, nc))
+        p = None if previous is None else previous[k]
+        out[k] = _abi.hk_instance_desc(slices[mesh], int(mat), _abi.HK_INSTANCE_NEW if p is None else int(p))
+    return out
+
+
+def material_records(scene: Scene):
+    """The scene's GpuStandardMaterial records as one ctypes buffer (hk_material x len(scene.materials))."""
+    return C.create_string_buffer(b"".join(m.record() for m in scene.materials), 80 * max(1, len(scene.materials)))
+
+
+def instance_set_counts(uploaded, scene: Scene, materials: bool = False):
+    """The nine element counts (hk_scene_desc order) hk_instance_set_counts gives for the instance list of `scene`
+    set on the host-built `uploaded` scene (a Scene or its hk_scene_desc); materials=True: with the scene's material
+    records instead of the uploaded ones.  Host arithmetic only: needs no device."""
+    desc = uploaded if isinstance(uploaded, _abi.hk_scene_desc) else (
+        uploaded.desc if uploaded.desc is not None else uploaded.build())
+    out = (C.c_uint32 * 9)()
+    mats = material_records(scene) if materials else None
+    _check(None, _abi.lib().hk_instance_set_counts(C.byref(desc), instance_descs(scene), len(scene.instances), mats, out),
+           "hk_instance_set_counts")
+    return list(out)
+
+
 class HikariRenderer:
     """A camera's integrator context (hk_ctx)."""
 
@@ -254,6 +290,29 @@ class HikariRenderer:
             u.normals = None if n is None else n.ctypes.data
         _check(self.ctx, self._L.hk_update_meshes(self.ctx, ups, len(mesh_ids), m.ctypes.data, a.ctypes.data, len(m),
                                                   _stream(stream)), "hk_update_meshes")
+
+    def set_instances(self, scene: Scene, previous=None, materials: bool = False, stream=None, models=None,
+                      local_aabbs=None) -> None:
+        """A new instance set for the uploaded scene (hk_set_instances): entities spawned, despawned, hidden or given
+        another material.  `scene` has the uploaded scene's meshes and materials in the same order and any instance
+        list; the GPU rebuilds instances, TLAS, emissives, alias tables and the light BVH for it.  previous: per
+        instance its index in the set before this call (None for a new entity; previous=None: all new), for the motion
+        vectors.  materials=True also sends the scene's material records.  models / local_aabbs: default
+        the scene's instance_models() / instance_local_aabbs()."""
+        m = np.ascontiguousarray(scene.instance_models() if models is None else models, np.float32).reshape(-1, 16)
+        a = np.ascontiguousarray(scene.instance_local_aabbs() if local_aabbs is None else local_aabbs,
+                                 np.float32).reshape(-1, 6)
+        if len(m) != len(a) or len(m) != len(scene.instances):
+            raise ValueError("models and local_aabbs need one record per instance")
+        mats = material_records(scene) if materials else None
+        _check(self.ctx, self._L.hk_set_instances(self.ctx, instance_descs(scene, previous), m.ctypes.data, a.ctypes.data,
+                                                  len(m), mats, _stream(stream)), "hk_set_instances")
+
+    def scene_counts(self) -> list:
+        """The current element counts of the nine scene arrays, hk_scene_desc order (hk_scene_counts)."""
+        out = (C.c_uint32 * 9)()
+        _check(self.ctx, self._L.hk_scene_counts(self.ctx, out), "hk_scene_counts")
+        return list(out)
 
     def scene_array(self, array: int, dtype, count: int) -> np.ndarray:
         """Device copy of group-2 scene array `array` (hk_scene_desc order) as `count` records."""
@@ -474,6 +533,10 @@ class HikariPlugin:
     def update_meshes(self, scene: Scene, mesh_ids, models=None, local_aabbs=None, stream=None) -> None:
         """`prepare_mesh_assets` for modified meshes of unchanged topology (HikariRenderer.update_meshes)."""
         self.renderer.update_meshes(scene, mesh_ids, models, local_aabbs, stream)
+
+    def set_instances(self, scene: Scene, previous=None, materials: bool = False, stream=None) -> None:
+        """`prepare_instances` for spawned, despawned, hidden or re-materialed entities (HikariRenderer.set_instances)."""
+        self.renderer.set_instances(scene, previous, materials, stream)
 
     def present(self, width: int = None, height: int = None, hdr: bool = False, viewport=None, stream=None):
         """The `Overlay` draw into a window-sized view target (overlay.rs:333-395): the plane the settings display,

@@ -289,6 +289,56 @@ typedef struct hk_mesh_update {
 } hk_mesh_update;
 int hk_update_meshes(hk_ctx* ctx, const hk_mesh_update* meshes, uint32_t mesh_count, const float* models,
                      const float* local_aabbs, uint32_t count, void* stream);
+
+/* A new instance set: what the reference's prepare_instances (instance.rs:245-444) does with
+ * InstanceEvent::Created / Modified / Removed (instance.rs:123-175), with the visibility filter and with changed
+ * materials (material.rs AssetEvent::Modified), ON THE GPU and in place: entities spawned, despawned or hidden, an
+ * instance given another material, an emissive colour going to or from zero.  After hk_set_instances the scene is what
+ * hks_build + hk_scene_upload give for the same meshes and materials in the same order and THIS instance list in this
+ * order (the reference's order is its BTreeMap's entity order; the caller supplies it, as at upload): the alias
+ * table, the instances, the TLAS, the light BVH and the emissives (arrays 3, 4, 5, 7, 8) are bit-identical to that
+ * host build, the emissive list re-derived from `intensity > 0` in instance order; arrays 0-2 are untouched; the
+ * materials (array 6) are replaced only when `materials` is given: all of the uploaded material count.  models and
+ * local_aabbs: `count` records as in hk_update_instances.  The G-buffer walk's stack bound becomes the rebuilt
+ * TLAS's levels plus the deepest BLAS among the slices the new set instances (it can fall).  Waits for the stream
+ * once.  hk_update_instances and hk_update_meshes afterwards take the current set: its count and order, and any
+ * slice instanced or registered so far.
+ *   previous: the motion vectors' previous model (transform.rs:8-44 GlobalTransformQueue) of instance i is the one
+ * the last G-buffer saw for entity set[i].previous of the set before this call, or the instance's own current model
+ * for HK_INSTANCE_NEW.
+ *   mesh: a slice instanced at upload is taken as it is.  Any other slice of the uploaded vertex / primitive /
+ * asset-node arrays (hks_build concatenates every added mesh, instanced or not) is registered on first use: it
+ * must be node[1] == 3k - 2 nodes over k primitives inside the primitive array, its node range inside the asset
+ * nodes, its stored vertex indices inside the vertex array, and identical to or disjoint from every slice known so
+ * far.
+ *   Capacity: the five arrays, the TLAS derivatives, the previous models and the scratch keep a capacity beside
+ * their count; a call allocates only for a count above its capacity, and then max(count, 1.5 x capacity); nothing
+ * shrinks before hk_scene_upload or hk_destroy.  A set without an emitter is legal (empty alias table, light BVH and
+ * emissives).  An EMPTY set is not: hk_scene_upload refuses an empty scene too.
+ *   HK_ERR_INVALID with a message, decided before any device work, the context unchanged and usable: a null set,
+ * models or local_aabbs; count == 0; a material index >= the material count; a slice that fails the checks above; a
+ * previous that is neither HK_INSTANCE_NEW nor below the count before, or used twice.  HK_ERR_STATE without a scene
+ * or on a scene whose BVHs are not 3n - 2 flattened.  A singular model fails after the rebuild as in
+ * hk_update_instances; the set is then the new one and a following valid call repairs it.  HK_ERR_HIP if the
+ * device's emitter or alias totals differ from the host's (hk_instance_set_counts). */
+#define HK_INSTANCE_NEW 0xFFFFFFFFu
+typedef struct hk_instance_desc {
+    hk_mesh_index mesh;   /* a mesh slice of the uploaded vertex / primitive / asset-node arrays */
+    uint32_t material;    /* < uploaded material count */
+    uint32_t previous;    /* this entity's index in the set before the call, or HK_INSTANCE_NEW */
+} hk_instance_desc;
+int hk_set_instances(hk_ctx* ctx, const hk_instance_desc* set, const float* models, const float* local_aabbs,
+                     uint32_t count, const hk_material* materials, void* stream);
+/* the current element counts of the nine scene arrays, hk_scene_desc order */
+int hk_scene_counts(const hk_ctx* ctx, uint32_t counts[9]);
+/* The host arithmetic hk_set_instances sizes its allocations and launches with (needs no device or context): the
+ * nine counts after `set` replaces the instances of the host-built `uploaded` scene: the instances, 3n - 2 TLAS
+ * nodes, the emitters (255 * emissive[3] * |emissive.rgb| > 0 in float, so a NaN does not emit; `materials`, if
+ * given, instead of the uploaded ones), the alias entries (the emitters' primitives) and 3m - 2 light-BVH nodes.
+ * `previous` is not read.  HK_ERR_INVALID: count == 0, a material index out of range, a slice that fails
+ * hk_set_instances' checks. */
+int hk_instance_set_counts(const hk_scene_desc* uploaded, const hk_instance_desc* set, uint32_t count,
+                           const hk_material* materials, uint32_t counts[9]);
 /* LDS staging of a scene, computed on the host with the launchers' own arithmetic (needs no device or context):
  * the bytes the traversal kernels of `plan` (0: the light passes' arrays, hk_scene_desc's nine; 1: the G-buffer
  * walk's vertices, primitives, instances and the two wide node layouts) copy into LDS, each array rounded up to
