@@ -145,6 +145,10 @@ struct Scene {
     const uint32_t* texels;
     const float* texture_lut;
     uint32_t n_textures;
+    // every instance record carries the same inverse_transpose_model (hk_scene_shared_transform) and option
+    // shared_xform is on: a light walk computes its instance-local ray once, from instances[0] (traverse_top; the
+    // G-buffer's closest_hit_ordered gained nothing from it).  Uniform per launch.
+    uint32_t shared_xform;
 };
 
 // ------------------------------------------------------------------ LDS scene staging
@@ -918,7 +922,9 @@ HKD f3 local_to_world_normal(const hk_instance& in, f3 n)
 // Slot 0: the traverse_top walks; slots 1-4: the stages of spatial reuse's neighbour loop (k_spatial: a neighbour
 // tested, a depth-march tap, the record tests, the shade / jacobian / merge), each tick at a stage's entry, so
 // active / (64 x iterations) of a slot is the fraction of the wave's lanes that do that stage's work when it runs.
-constexpr int LANE_SLOTS = 5;
+// Slot 5: the instance-entry branch of traverse_top (a lane's walk enters a non-empty instance): its iterations over
+// slot 0's are the share of a wave's walk iterations that run the branch.
+constexpr int LANE_SLOTS = 6;
 #ifdef HK_LANE_STATS
 extern __device__ unsigned long long hk_lane_stats_dev[2 * LANE_SLOTS];
 template <int SLOT = 0>
@@ -940,13 +946,15 @@ struct LaneStats {
         }
     }
 };
-#define HK_LANE_STATS_DECL LaneStats<0> lane_stats_
+#define HK_LANE_STATS_DECL LaneStats<0> lane_stats_; LaneStats<5> entry_stats_
 #define HK_LANE_STATS_TICK lane_stats_.tick()
+#define HK_ENTRY_STATS_TICK entry_stats_.tick()
 #define HK_STAGE_STATS_DECL LaneStats<1> stage1_; LaneStats<2> stage2_; LaneStats<3> stage3_; LaneStats<4> stage4_
 #define HK_STAGE_TICK(k) stage##k##_.tick()
 #else
 #define HK_LANE_STATS_DECL
 #define HK_LANE_STATS_TICK
+#define HK_ENTRY_STATS_TICK
 #define HK_STAGE_STATS_DECL
 #define HK_STAGE_TICK(k)
 #endif
@@ -961,8 +969,8 @@ struct LaneStats {
 // walks): intersects_triangle returns a distance > F32_EPSILON or F32_MAX, so no hit is nearer than an early
 // distance of 0 and neither early exit can be taken, and no instance index equals DONT_EXCLUDE; the loop then
 // carries no stop flag, no early-distance compares and no exclude compare.  Same visits and results.
-template <bool ANY_HIT = true>
-HKD Hit traverse_top(const Scene& sc, const Ray& ray, float max_distance, float early_distance, uint32_t exclude)
+template <bool ANY_HIT>
+HKD Hit traverse_top_general(const Scene& sc, const Ray& ray, float max_distance, float early_distance, uint32_t exclude)
 {
     Hit hit;
     hit.uv = mk2(0.0f, 0.0f);
@@ -1030,6 +1038,7 @@ HKD Hit traverse_top(const Scene& sc, const Ray& ray, float max_distance, float 
                     nodes = sc.asset_nodes + in.mesh.node[0];
                     count = bot_count;
                     index = 0u;
+                    HK_ENTRY_STATS_TICK;
                     tr.origin = world_to_local_point(in, ray.origin);
                     tr.direction = world_to_local_dir(in, ray.direction);
                     tr.inv_direction = inv(tr.direction);
@@ -1038,6 +1047,101 @@ HKD Hit traverse_top(const Scene& sc, const Ray& ray, float max_distance, float 
         }
     }
     return hit;
+}
+// One local ray per walk (Scene::shared_xform): every instance record holds the same inverse_transpose_model, so
+// each instance entry of the walk above would compute the same local origin, direction and reciprocal from the same
+// inputs.  They are computed once before the loop, by the same three functions from instances[0] (a wave-uniform
+// address), and an entry keeps the empty-mesh test, the mesh slice and the level switch.  There is no switched ray:
+// the slab test's origin and reciprocal are selected per iteration between the world and the local ray (a third,
+// switched ray measured slower: 95 / 120 VGPRs instead of 93 / 111 in the indirect / fused direct kernel),
+// and the triangle test, which only runs inside a BLAS, reads the local ray.  Same visits, tests, hit and early exits
+// as the general walk.
+template <bool ANY_HIT>
+HKD Hit traverse_top_shared(const Scene& sc, const Ray& ray, float max_distance, float early_distance, uint32_t exclude)
+{
+    Hit hit;
+    hit.uv = mk2(0.0f, 0.0f);
+    hit.distance = max_distance;
+    hit.instance_index = HK_U32_MAX;
+    hit.primitive_index = HK_U32_MAX;
+    const hk_node* nodes = sc.instance_nodes;
+    uint32_t count = sc.n_instance_nodes, index = 0u;
+    Ray local;
+    {
+        const hk_instance& in0 = sc.instances[0];
+        local.origin = world_to_local_point(in0, ray.origin);
+        local.direction = world_to_local_dir(in0, ray.direction);
+        local.inv_direction = inv(local.direction);
+    }
+    uint32_t top = 0u;
+    uint32_t prim_offset = 0u, cur_instance = 0u;
+    bool in_bottom = false, intersected = false;
+    HK_LANE_STATS_DECL;
+    while (index < count) {
+        HK_LANE_STATS_TICK;
+        Ray tr;  // (walk_step reads the origin and the reciprocal only)
+        tr.origin = in_bottom ? local.origin : ray.origin;
+        tr.direction = local.direction;
+        tr.inv_direction = in_bottom ? local.inv_direction : ray.inv_direction;
+        bool leaf_pass;
+        uint32_t leaf_entry;
+        index = walk_step<WALK_STEPS>(nodes, index, count, tr, hit.distance, leaf_pass, leaf_entry);
+        if (in_bottom) {
+            bool stop = false;
+            if (leaf_pass) {
+                const uint32_t primitive_index = prim_offset + leaf_entry - HK_BVH_LEAF_FLAG;
+                f3 a, b, c;
+                load_triangle(sc.primitives, primitive_index, a, b, c);
+                f2 uv;
+                const float d = intersects_triangle(local, a, b, c, uv);
+                if (d < hit.distance) {
+                    hit.distance = d;
+                    hit.uv = uv;
+                    hit.primitive_index = primitive_index;
+                    intersected = true;
+                    if constexpr (ANY_HIT) stop = d < early_distance;
+                }
+            }
+            if (stop || index >= count) {
+                in_bottom = false;
+                nodes = sc.instance_nodes;
+                count = sc.n_instance_nodes;
+                index = top;
+                if (intersected) {
+                    hit.instance_index = cur_instance;
+                    if constexpr (ANY_HIT) {
+                        if (hit.distance < early_distance) return hit;
+                    }
+                }
+            }
+        } else {
+            const uint32_t instance_index = leaf_entry - HK_BVH_LEAF_FLAG;
+            if (leaf_pass && (!ANY_HIT || instance_index != exclude)) {
+                const hk_instance& in = sc.instances[instance_index];
+                const uint32_t bot_count = in.mesh.node[1];
+                prim_offset = in.mesh.primitive;
+                cur_instance = instance_index;
+                intersected = false;
+                if (bot_count > 0u) {
+                    in_bottom = true;
+                    top = index;
+                    nodes = sc.asset_nodes + in.mesh.node[0];
+                    count = bot_count;
+                    index = 0u;
+                    HK_ENTRY_STATS_TICK;
+                }
+            }
+        }
+    }
+    return hit;
+}
+// The walk of a launch: one scalar branch on the scene's uniform flag, so a scene with several transforms runs the
+// general walk as before.
+template <bool ANY_HIT = true>
+HKD Hit traverse_top(const Scene& sc, const Ray& ray, float max_distance, float early_distance, uint32_t exclude)
+{
+    if (sc.shared_xform) return traverse_top_shared<ANY_HIT>(sc, ray, max_distance, early_distance, exclude);
+    return traverse_top_general<ANY_HIT>(sc, ray, max_distance, early_distance, exclude);
 }
 // the closest hit along a ray (light.wgsl's traverse_top(ray, F32_MAX, 0.0)): the bounce walks
 HKD Hit traverse_top_closest(const Scene& sc, const Ray& ray)

@@ -9,10 +9,11 @@
 //   k_direct_lit_w4<LDS,VAL>    direct_kernel<false,true>, 4 waves per SIMD  launch_direct: direct_lit from direct_w4_min_px up
 //   k_direct_fused<LDS,VD,VE>   direct_fused_kernel (both direct passes)     launch_direct_fused: fused_w4 off, or a staged
 //                                                                            emissive-validation frame
-//   k_direct_fused_w4<LDS,VD,VE> direct_fused_kernel, 4 waves per SIMD       launch_direct_fused: fused_w4 (default) otherwise
+//   k_direct_fused_w4<LDS,VD,VE,SX> direct_fused_kernel, 4 waves per SIMD    launch_direct_fused: fused_w4 (default) otherwise;
+//                                                                            SX: the scene's shared_xform (fix_shared_xform)
 //   k_direct_fused_cw<VD,CS>    own: direct_begin / _candidate / _finish     launch_direct_fused: compact_emitter or compact_shadow,
 //                               around compact_walks                         unstaged, not an emissive-validation frame
-//   k_indirect<MULTI,LDS,CS>    indirect_body (light.wgsl:1263); CS:         launch_indirect: default; CS: compact_shadow
+//   k_indirect<MULTI,LDS,CS,SX> indirect_body (light.wgsl:1263); CS:         launch_indirect: default (SX as above); CS: compact_shadow
 //                               indirect_begin / compact_walks / indirect_end
 //   k_indirect_persist<MULTI,LDS> persist_tiles over indirect_body           launch_indirect: persistent_indirect
 //   k_light_merged<VD,VE,LDS_I> fused_direct_pixel | indirect_body by role   launch_light_merged: the runtime's merged frames
@@ -820,7 +821,18 @@ HKD void fused_direct_pixel(const FrameArgs& A, const Scene& sc, const ChannelAr
 // 1: the G-buffer of k_gbuffer), so per-thread program order is the reference's pass order for
 // every stored word; the runtime uses it only then.  One launch and one tail instead of two.
 // The body of k_direct_fused and k_direct_fused_w4 (argument blocks by value: direct_kernel).
-template <bool LDS, bool VD, bool VE>
+// SX: Scene::shared_xform as a compile-time constant (0 / 1, chosen at launch from the scene's flag), so that the kernel
+// holds one of traverse_top's two walks and the general instantiation is the code it was before the shared walk; -1:
+// the flag is read at run time (one scalar branch per walk, both walks in the kernel).  The two kernels of the
+// default frame take it (k_direct_fused_w4 and the one-bounce k_indirect): with both walks inlined the fused kernel
+// needs 113 VGPRs instead of 110, one allocation granule more, which costs the overlapped frame 0.004 ms whichever
+// walk runs.
+template <int SX>
+HKD void fix_shared_xform(Scene& sc)
+{
+    if constexpr (SX >= 0) sc.shared_xform = (uint32_t)SX;
+}
+template <bool LDS, bool VD, bool VE, int SX = -1>
 HKD void direct_fused_kernel(FrameArgs A, ChannelArgs C0, ChannelArgs C1)
 {
     int32_t x, y;
@@ -830,6 +842,7 @@ HKD void direct_fused_kernel(FrameArgs A, ChannelArgs C0, ChannelArgs C1)
     Scene sc;
     if constexpr (LDS) sc = stage_scene<PLAN_LIGHT>(A.sc, hk_lds_scene);
     else sc = A.sc;
+    fix_shared_xform<SX>(sc);
     uint32_t n_top = 0, n_emitter = 0;
     if (active) fused_direct_pixel<VD, VE, !LDS>(A, sc, C0, C1, direct_pixel_of(A, x, y, tex), n_top, n_emitter);
     finish_counts(A, x, y, n_top, n_emitter);
@@ -844,11 +857,11 @@ __global__ __launch_bounds__(256) void k_direct_fused(FrameArgs A, ChannelArgs C
 // validation block on every third frame), a few of which then spill.
 // With the validation blocks parked in LDS (non-LDS-scene variants) the emissive
 // validation frames take this 4-wave kernel too (VE).
-template <bool LDS, bool VD, bool VE = false>
+template <bool LDS, bool VD, bool VE = false, bool SX = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_direct_fused_w4(FrameArgs A, ChannelArgs C0,
                                                                                                    ChannelArgs C1)
 {
-    direct_fused_kernel<LDS, VD, VE>(A, C0, C1);
+    direct_fused_kernel<LDS, VD, VE, SX ? 1 : 0>(A, C0, C1);
 }
 
 // Emitter walks of a workgroup as one compacted batch (the CW variant of the fused launch).  In city the
@@ -1497,7 +1510,8 @@ HKD bool indirect_body(const FrameArgs& A, const Scene& sc, const ChannelArgs& C
 }
 
 // CS: the one-bounce path's shadow walks compacted per workgroup (compact_top_walks; option compact_shadow)
-template <bool MULTI, bool LDS, bool CS = false>
+// SX: fix_shared_xform's constant for the one-bounce kernel (-1: the flag at run time)
+template <bool MULTI, bool LDS, bool CS = false, int SX = -1>
 __global__ __launch_bounds__(256) void k_indirect(FrameArgs A, ChannelArgs C)
 {
     int32_t x, y;
@@ -1516,6 +1530,7 @@ __global__ __launch_bounds__(256) void k_indirect(FrameArgs A, ChannelArgs C)
     if constexpr (LDS) {
         sc = stage_scene<PLAN_LIGHT>(A.sc, hk_lds_scene);
     }
+    fix_shared_xform<SX>(sc);
     uint32_t n_top = 0, n_emitter = 0;
     if constexpr (CS && !MULTI) {
         IndirectState I;
@@ -2656,8 +2671,8 @@ static void launch_fused_v(const FrameArgs& A, const ChannelArgs& C0, const Chan
         dispatch([&](auto VD, auto CS) { hipLaunchKernelGGL((k_direct_fused_cw<VD, CS>), g, dim3(256), lds, st, A, C0, C1); },
                  vd, A.opt.compact_shadow != 0);
     } else if (w4 && (!LDS || !ve)) {
-        dispatch([&](auto VD, auto VE) { hipLaunchKernelGGL((k_direct_fused_w4<LDS, VD, VE>), g, dim3(256), lds, st, A, C0, C1); },
-                 vd, ve);
+        dispatch([&](auto VD, auto VE, auto SX) { hipLaunchKernelGGL((k_direct_fused_w4<LDS, VD, VE, SX>), g, dim3(256), lds, st, A, C0, C1); },
+                 vd, ve, A.sc.shared_xform != 0u);
     } else {
         dispatch([&](auto VD, auto VE) { hipLaunchKernelGGL((k_direct_fused<LDS, VD, VE>), g, dim3(256), lds, st, A, C0, C1); },
                  vd, ve);
@@ -2726,12 +2741,12 @@ void launch_indirect(const FrameArgs& A, const ChannelArgs& C, bool multi, hipSt
     }
     // (only the staging flag goes through dispatch: there is no compacted multi-bounce kernel)
     dispatch(
-        [&](auto L) {
+        [&](auto L, auto SX) {
             if (multi) hipLaunchKernelGGL((k_indirect<true, L>), g, dim3(256), lds, st, A, C);
             else if (A.opt.compact_shadow) hipLaunchKernelGGL((k_indirect<false, L, true>), g, dim3(256), lds, st, A, C);
-            else hipLaunchKernelGGL((k_indirect<false, L>), g, dim3(256), lds, st, A, C);
+            else hipLaunchKernelGGL((k_indirect<false, L, false, SX ? 1 : 0>), g, dim3(256), lds, st, A, C);
         },
-        lds != 0u);
+        lds != 0u, A.sc.shared_xform != 0u);
 }
 uint32_t indirect_stash_bytes() { return (uint32_t)sizeof(IndStash); }
 // the largest staged scene with the stash behind it is within a workgroup's LDS (k_indirect, k_light_merged)

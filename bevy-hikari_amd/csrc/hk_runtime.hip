@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/hikari_amd.h"
+#include "../../include/hikari_scene.h"
 #include "hk_launch.h"
 
 using namespace hk;
@@ -65,6 +66,7 @@ enum Opt {
     OPT_COMPACT_SHADOW,
     OPT_FSR_TILED,           // EASU with its input footprint staged in LDS (hk_fsr.hip)
     OPT_PRESENT_RUN,         // hk_present stores 16-byte row runs where the viewport's runs are aligned (hk_overlay.hip)
+    OPT_SHARED_XFORM,        // one local ray per walk where every instance carries the same transform (Scene::shared_xform)
     OPT_COUNT
 };
 struct OptDef {
@@ -81,7 +83,7 @@ constexpr OptDef OPTS[OPT_COUNT] = {
     {"gbuffer_lds_max_px", 6e5, 0.0, 1e12},
     {"direct_w4_min_px", 4e5, 0.0, 1e12},  {"fused_w4", 1, 0, 1},          {"persistent_indirect", 0, 0, 1},
     {"compact_emitter", 0, 0, 1},          {"compact_shadow", 0, 0, 1},    {"fsr_tiled", 1, 0, 1},
-    {"present_run", 1, 0, 1},
+    {"present_run", 1, 0, 1},              {"shared_xform", 1, 0, 1},
 };
 
 // One slot of the planes k_gbuffer double-buffers (hk_ctx::g / g_prev: swapped on each hk_render_gbuffer) so a
@@ -326,6 +328,9 @@ struct hk_ctx {
     bool models_dirty = false;   // hk_update_instances ran since the last k_gbuffer
     bool velocity_zero = true;   // the current G-buffer's velocity plane is all zero (k_gbuffer, no motion)
     bool has_scene = false;
+    // every instance record holds the same inverse_transpose_model bits (hks_shared_transform): set where the
+    // records change, at hk_scene_upload from the records and in rebuild_instances from the models they derive from
+    bool shared_transform = false;
     uchar4* noise = nullptr;
     bool has_noise = false;
     // material textures (hk_texture_upload)
@@ -601,7 +606,8 @@ void lane_stats_account(hk_ctx* c, const char* name, hipStream_t st)
 {
     unsigned long long v[2 * LANE_SLOTS];
     if (!lane_stats_take(v, st)) return;
-    static const char* const stage[LANE_SLOTS] = {"", "/neighbour", "/march_tap", "/record_tests", "/merge"};
+    static const char* const stage[LANE_SLOTS] = {"", "/neighbour", "/march_tap", "/record_tests", "/merge",
+                                                    "/instance_entry"};
     for (int slot = 0; slot < LANE_SLOTS; ++slot) {
         if (!v[2 * slot + 1]) continue;
         const std::string key = std::string(name) + stage[slot];
@@ -699,6 +705,7 @@ FrameArgs frame_args(hk_ctx* c, const hk_settings* st, const hk_frame_inputs* in
     A.sc.texels = c->texels;
     A.sc.texture_lut = c->tex_lut;
     A.sc.n_textures = c->n_textures;
+    A.sc.shared_xform = c->shared_transform && c->on(OPT_SHARED_XFORM);
     scene_array_bytes(c->count, A.sc.bytes);
     Frame& F = A.F;
     hk_settings def;
@@ -1183,6 +1190,7 @@ int hk_scene_upload(hk_ctx* c, const hk_scene_desc* d)
     if (d->instances.count == 0 || d->materials.count == 0)
         return fail(c, HK_ERR_INVALID, "scene needs at least one instance and one material");
     c->gen++;
+    c->shared_transform = false;
     for (int i = 0; i < 9; ++i)
         if (arr[i]->count && !arr[i]->data) return fail(c, HK_ERR_INVALID, "scene array with count but no data");
     HK_HIP(c, hipStreamSynchronize(c->stream));
@@ -1274,6 +1282,11 @@ int hk_scene_upload(hk_ctx* c, const hk_scene_desc* d)
                                sizeof(hk_instance), 64, d->instances.count, hipMemcpyDeviceToDevice, c->stream));
     c->models_dirty = false;
     HK_HIP(c, hipStreamSynchronize(c->stream));
+    {   // what the walks read: the records' inverse_transpose_model
+        std::vector<float> itm(16 * (size_t)d->instances.count);
+        for (uint32_t k = 0; k < d->instances.count; ++k) std::memcpy(&itm[16 * (size_t)k], inst[k].inverse_transpose_model, 64);
+        c->shared_transform = hks_shared_transform(itm.data(), d->instances.count) != 0;
+    }
     c->has_scene = true;
     return HK_OK;
 }
@@ -1486,6 +1499,7 @@ static int rebuild_instances(hk_ctx* c, const float* models, const float* local_
     HK_TRY(c->sch.gb_join(st));
     HK_TRY(c->sch.gb_serialize(false));
     c->gen++;
+    c->shared_transform = false;  // (the general walks, should this call fail half-way)
     struct Moved {  // the previous models of the set before, where reserve_set moved them: freed on every way out
         float* p = nullptr;
         ~Moved() { release(p); }
@@ -1614,6 +1628,9 @@ static int rebuild_instances(hk_ctx* c, const float* models, const float* local_
     if (flags[0]) return fail(c, HK_ERR_INVALID, "singular instance transform");
     c->gb_stack_need = flags[1] + c->gb_blas_depth;
     c->models_dirty = true;  // the next G-buffer reads the models before this update as the previous ones
+    // one kernel derives every record's inverse_transpose_model from its model with the same code: equal model bits
+    // give equal record bits
+    c->shared_transform = hks_shared_transform(models, n) != 0;
     return HK_OK;
 }
 
@@ -1777,6 +1794,14 @@ int hk_scene_counts(const hk_ctx* c, uint32_t counts[9])
     if (!c || !counts) return HK_ERR_INVALID;
     if (!c->has_scene) return HK_ERR_STATE;
     std::memcpy(counts, c->count, sizeof(c->count));
+    return HK_OK;
+}
+
+int hk_scene_shared_transform(const hk_ctx* c, int32_t* shared)
+{
+    if (!c || !shared) return HK_ERR_INVALID;
+    if (!c->has_scene) return HK_ERR_STATE;
+    *shared = c->shared_transform ? 1 : 0;
     return HK_OK;
 }
 

@@ -537,4 +537,14 @@ int hks_get_desc(const hks_scene* s, hk_scene_desc* out)
     return HK_OK;
 }
 
+// Bitwise, not by value: the walks reuse one instance's local ray for every instance only where the records hold
+// the same bits, so -0.0 differs from 0.0 and a NaN payload counts.
+int hks_shared_transform(const float* matrices, uint32_t n)
+{
+    if (!matrices || n == 0) return 0;
+    for (uint32_t k = 1; k < n; ++k)
+        if (std::memcmp(matrices, matrices + 16 * (size_t)k, 64) != 0) return 0;
+    return 1;
+}
+
 }  // extern "C"

@@ -206,6 +206,7 @@ def lib() -> C.CDLL:
         "hk_update_meshes": (i32, [vp, C.POINTER(hk_mesh_update), u32, vp, vp, u32, vp]),
         "hk_set_instances": (i32, [vp, C.POINTER(hk_instance_desc), vp, vp, u32, vp, vp]),
         "hk_scene_counts": (i32, [vp, C.POINTER(u32)]),
+        "hk_scene_shared_transform": (i32, [vp, C.POINTER(i32)]),
         "hk_instance_set_counts": (i32, [C.POINTER(hk_scene_desc), C.POINTER(hk_instance_desc), u32, vp, C.POINTER(u32)]),
         "hk_read_scene_array": (i32, [vp, i32, vp, C.c_size_t]),
         "hk_resolve_accumulation": (i32, [vp, vp]),
@@ -235,6 +236,7 @@ def lib() -> C.CDLL:
         "hks_add_instance": (i32, [vp, u32, u32, vp]),
         "hks_build": (i32, [vp, i32]),
         "hks_get_desc": (i32, [vp, C.POINTER(hk_scene_desc)]),
+        "hks_shared_transform": (i32, [vp, u32]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -253,7 +255,7 @@ EXPORTED_SYMBOLS = [
     "hk_denoise", "hk_tone_sum", "hk_update_instances", "hk_update_meshes", "hk_set_instances", "hk_scene_counts", "hk_instance_set_counts", "hk_read_scene_array", "hk_post_process", "hk_set_fsr1_sharpness", "hk_present", "hk_present_info", "hk_get_present", "hk_accumulate", "hk_resolve_accumulation", "hk_output_info", "hk_get_output", "hk_output_device_ptr", "hk_sync", "hk_set_wavefront", "hk_lane_stats", "hk_dump_reservoirs",
     "hk_load_reservoirs", "hk_reset_counters", "hk_read_counters", "hk_enable_kernel_timing", "hk_kernel_timing", "hk_set_kernel_timing_interval",
     "hk_trace", "hk_selftest_f16", "hk_selftest_div", "hk_selftest_rcp", "hk_selftest_count", "hks_create", "hks_destroy", "hks_last_error", "hks_add_mesh", "hks_add_material",
-    "hks_add_instance", "hks_build", "hks_get_desc",
+    "hks_add_instance", "hks_build", "hks_get_desc", "hk_scene_shared_transform", "hks_shared_transform",
 ]
 
 

@@ -73,6 +73,13 @@ def scene_gbuffer_stack(scene):
     return n.value, lv.value
 
 
+def shared_transform(models) -> bool:
+    """hks_shared_transform: True when there is at least one matrix and all the column-major 4x4 float32 matrices
+    of `models` (n x 16) hold the same bits (-0.0 differs from 0.0).  Host only: needs no device."""
+    m = np.ascontiguousarray(models, np.float32).reshape(-1, 16)
+    return bool(_abi.lib().hks_shared_transform(m.ctypes.data if len(m) else None, len(m)))
+
+
 def instance_descs(scene: Scene, previous=None):
     """ctypes array of hk_instance_desc for the instance list of `scene`: each instance's mesh slice
     (Scene.mesh_index), its material and its index in the set before (`previous`: one entry per instance, None or
@@ -313,6 +320,13 @@ class HikariRenderer:
         out = (C.c_uint32 * 9)()
         _check(self.ctx, self._L.hk_scene_counts(self.ctx, out), "hk_scene_counts")
         return list(out)
+
+    def scene_shared_transform(self) -> bool:
+        """Every instance of the current scene carries one bit-identical transform (hk_scene_shared_transform): the
+        walks then compute one local ray per walk while option shared_xform is on."""
+        out = C.c_int32()
+        _check(self.ctx, self._L.hk_scene_shared_transform(self.ctx, C.byref(out)), "hk_scene_shared_transform")
+        return bool(out.value)
 
     def scene_array(self, array: int, dtype, count: int) -> np.ndarray:
         """Device copy of group-2 scene array `array` (hk_scene_desc order) as `count` records."""

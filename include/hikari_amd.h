@@ -236,6 +236,9 @@ void hk_settings_default(hk_settings* out);
  *   present_run (1)        hk_present stores 16-byte row runs (4 texels, RGBA16F 2) where the viewport's first texel
  *                            and the pitch are 16-byte aligned, each row's tail per texel (0: every texel on its own);
  *                            tests force both variants with it
+ *   shared_xform (1)         in a scene whose instances all carry one bit-identical transform
+ *                            (hk_scene_shared_transform) a walk computes its instance-local ray once instead of at
+ *                            every instance it enters; 0: always the general walk
  * hk_set_option returns HK_ERR_INVALID for an unknown key, a value outside the key's range, or a fractional value
  * for any key but the pixel-count thresholds (*_px). */
 int hk_set_option(hk_ctx* ctx, const char* key, double value);
@@ -331,6 +334,11 @@ int hk_set_instances(hk_ctx* ctx, const hk_instance_desc* set, const float* mode
                      uint32_t count, const hk_material* materials, void* stream);
 /* the current element counts of the nine scene arrays, hk_scene_desc order */
 int hk_scene_counts(const hk_ctx* ctx, uint32_t counts[9]);
+/* *shared = 1 when every instance of the current scene carries the same transform, bit for bit (hikari_scene.h
+ * hks_shared_transform over the records' inverse_transpose_model at hk_scene_upload, over the models given to
+ * hk_update_instances / hk_update_meshes / hk_set_instances after them), 0 otherwise.  It does not depend on option
+ * shared_xform, which decides whether the walks use it.  HK_ERR_STATE without a scene. */
+int hk_scene_shared_transform(const hk_ctx* ctx, int32_t* shared);
 /* The host arithmetic hk_set_instances sizes its allocations and launches with (needs no device or context): the
  * nine counts after `set` replaces the instances of the host-built `uploaded` scene: the instances, 3n - 2 TLAS
  * nodes, the emitters (255 * emissive[3] * |emissive.rgb| > 0 in float, so a NaN does not emit; `materials`, if

@@ -45,6 +45,10 @@ int hks_build(hks_scene* scene, int buckets);
 /* Pointers stay valid until the next hks_build / hks_destroy. */
 int hks_get_desc(const hks_scene* scene, hk_scene_desc* out);
 
+/* 1 when n >= 1 and the n column-major 4x4 matrices (n blocks of 64 bytes) are bitwise equal, 0 otherwise: the
+ * property behind hk_scene_shared_transform, for callers that want it without a device. */
+int hks_shared_transform(const float* matrices, uint32_t n);
+
 #ifdef __cplusplus
 }
 #endif

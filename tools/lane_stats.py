@@ -6,7 +6,8 @@ EXTRA=-DHK_LANE_STATS), once with the megakernel indirect pass and once with the
 and writes {config: {layout: {kernel: {active, iterations, efficiency}}}} where efficiency =
 active lanes / (64 x walk iterations) — the fraction of a wave's lanes doing walk work per
 iteration (lanes whose walk ended or that trace no ray count as idle).  bench.py reports it next
-to the roofline.  usage: HK_LIB=exp_lanestats/lanestats.so python tools/lane_stats.py out.json
+to the roofline.  Keys ending in /instance_entry count the iterations in which a wave runs traverse_top's
+instance-entry branch and the lanes in it: their iterations over the kernel's are the branch's share.  usage: HK_LIB=exp_lanestats/lanestats.so python tools/lane_stats.py out.json
 """
 import json
 import os
