@@ -3036,6 +3036,22 @@ void launch_f16(const float* in, uint32_t n, uint16_t* out, hipStream_t st)
     hipLaunchKernelGGL(k_f16, dim3((n + 255u) / 256u), dim3(256), 0, st, in, n, out);
 }
 
+// the kernels' own sample_material_texture (hk_device.h) of texture `id` at n uv pairs; the caller checked id < n_textures
+__global__ __launch_bounds__(256) void k_texture_check(Scene sc, uint32_t id, const float* uv, uint32_t n, float* out)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const f4 t = sample_material_texture(sc, id, mk2(uv[2 * i], uv[2 * i + 1]));
+    out[4 * i] = t.x;
+    out[4 * i + 1] = t.y;
+    out[4 * i + 2] = t.z;
+    out[4 * i + 3] = t.w;
+}
+void launch_texture_check(const Scene& sc, uint32_t id, const float* uv, uint32_t n, float* out, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_texture_check, dim3((n + 255u) / 256u), dim3(256), 0, st, sc, id, uv, n, out);
+}
+
 void launch_trace(const Scene& sc, const float* rays, const float* max_d, const float* early_d, const uint32_t* excl,
                   uint32_t n, uint32_t* hits, unsigned long long* top, hipStream_t st)
 {

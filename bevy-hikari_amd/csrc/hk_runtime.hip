@@ -3243,4 +3243,26 @@ int hk_selftest_count(hk_ctx* c, const uint32_t* values, uint32_t n, uint64_t* s
     return HK_OK;
 }
 
+int hk_selftest_texture(hk_ctx* c, uint32_t texture, const float* uv, uint32_t n, float* out)
+{
+    if (!c) return HK_ERR_INVALID;
+    if (texture >= c->n_textures) return fail(c, HK_ERR_INVALID, "texture id past the uploaded textures");
+    if (n && (!uv || !out)) return HK_ERR_INVALID;
+    if (n == 0) return HK_OK;
+    (void)hipSetDevice(c->device);
+    hipStream_t st = pick(c, nullptr);
+    FrameArgs A = frame_args(c, nullptr, nullptr);
+    float *d_uv = nullptr, *d_out = nullptr;
+    HK_HIP(c, hipMalloc(&d_uv, (size_t)n * 8));
+    HK_HIP(c, hipMalloc(&d_out, (size_t)n * 16));
+    HK_HIP(c, hipMemcpy(d_uv, uv, (size_t)n * 8, hipMemcpyHostToDevice));
+    launch_texture_check(A.sc, texture, d_uv, n, d_out, st);
+    HK_HIP(c, hipGetLastError());
+    HK_HIP(c, hipMemcpyAsync(out, d_out, (size_t)n * 16, hipMemcpyDeviceToHost, st));
+    HK_HIP(c, hipStreamSynchronize(st));
+    release(d_uv);
+    release(d_out);
+    return HK_OK;
+}
+
 }  // extern "C"

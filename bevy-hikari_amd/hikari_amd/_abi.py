@@ -228,6 +228,7 @@ def lib() -> C.CDLL:
         "hk_selftest_div": (i32, [vp, C.c_float, u32, u32, C.POINTER(C.c_uint64)]),
         "hk_selftest_rcp": (i32, [vp, u32, u32, C.POINTER(C.c_uint64)]),
         "hk_selftest_count": (i32, [vp, vp, u32, C.POINTER(C.c_uint64)]),
+        "hk_selftest_texture": (i32, [vp, u32, vp, u32, vp]),
         "hks_create": (vp, []),
         "hks_destroy": (None, [vp]),
         "hks_last_error": (C.c_char_p, [vp]),
@@ -254,7 +255,7 @@ EXPORTED_SYMBOLS = [
     "hk_set_noise", "hk_texture_upload", "hk_resize", "hk_resize_striped", "hk_set_band_halo", "hk_band_info", "hk_band_window_grow", "hk_reservoir_rows", "hk_resize_tile", "hk_tile_info", "hk_copy_output_rect", "hk_copy_output_rows", "hk_render_gbuffer", "hk_set_gbuffer_plane", "hk_render_frame",
     "hk_denoise", "hk_tone_sum", "hk_update_instances", "hk_update_meshes", "hk_set_instances", "hk_scene_counts", "hk_instance_set_counts", "hk_read_scene_array", "hk_post_process", "hk_set_fsr1_sharpness", "hk_present", "hk_present_info", "hk_get_present", "hk_accumulate", "hk_resolve_accumulation", "hk_output_info", "hk_get_output", "hk_output_device_ptr", "hk_sync", "hk_set_wavefront", "hk_lane_stats", "hk_dump_reservoirs",
     "hk_load_reservoirs", "hk_reset_counters", "hk_read_counters", "hk_enable_kernel_timing", "hk_kernel_timing", "hk_set_kernel_timing_interval",
-    "hk_trace", "hk_selftest_f16", "hk_selftest_div", "hk_selftest_rcp", "hk_selftest_count", "hks_create", "hks_destroy", "hks_last_error", "hks_add_mesh", "hks_add_material",
+    "hk_trace", "hk_selftest_f16", "hk_selftest_div", "hk_selftest_rcp", "hk_selftest_count", "hk_selftest_texture", "hks_create", "hks_destroy", "hks_last_error", "hks_add_mesh", "hks_add_material",
     "hks_add_instance", "hks_build", "hks_get_desc", "hk_scene_shared_transform", "hks_shared_transform",
 ]
 

@@ -176,6 +176,12 @@ class HikariRenderer:
         tex = texture_array(scene.textures)
         _check(self.ctx, self._L.hk_texture_upload(self.ctx, tex, len(scene.textures)), "hk_texture_upload")
 
+    def upload_textures(self, textures) -> None:
+        """Replace the material textures alone (hk_texture_upload; an empty list: the NO_TEXTURE pipeline)."""
+        textures = list(textures)
+        tex = texture_array(textures)
+        _check(self.ctx, self._L.hk_texture_upload(self.ctx, tex, len(textures)), "hk_texture_upload")
+
     def set_noise(self, noise: Optional[np.ndarray] = None) -> None:
         n = np.ascontiguousarray(load_noise() if noise is None else noise, np.uint8)
         _check(self.ctx, self._L.hk_set_noise(self.ctx, n.ctypes.data, 16, 64), "hk_set_noise")
@@ -496,6 +502,14 @@ class HikariRenderer:
         n = C.c_uint64()
         _check(self.ctx, self._L.hk_selftest_div(self.ctx, divisor, lo, hi, C.byref(n)), "hk_selftest_div")
         return n.value
+
+    def selftest_texture(self, texture: int, uv: np.ndarray) -> np.ndarray:
+        """The kernels' own texture sampler on uploaded texture `texture` at (n, 2) uv -> (n, 4) float32."""
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        out = np.empty((len(uv), 4), np.float32)
+        _check(self.ctx, self._L.hk_selftest_texture(self.ctx, texture, uv.ctypes.data, len(uv), out.ctypes.data),
+               "hk_selftest_texture")
+        return out
 
     def selftest_f16(self, values: np.ndarray) -> np.ndarray:
         """The kernels' own f32 -> f16 conversion applied to `values` (uint16 bit patterns)."""

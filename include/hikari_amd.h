@@ -570,6 +570,11 @@ int hk_selftest_rcp(hk_ctx* ctx, uint32_t lo, uint32_t hi, uint64_t* mismatches)
 /* ---- self-test of the kernels' ray-counter reduction (wave_count, hk_device.h): thread i of 256-thread workgroups
  * counts values[i] (n host words; the last workgroup's other threads count nothing); sum: the sharded counter's total */
 int hk_selftest_count(hk_ctx* ctx, const uint32_t* values, uint32_t n, uint64_t* sum);
+/* ---- self-test of the kernels' texture sampler (sample_material_texture, hk_device.h; include/hk_texture.h):
+ * samples uploaded texture `texture` at n host uv pairs (2 floats each); out: n x 4 host floats.
+ * HK_ERR_INVALID, before any launch: texture >= the uploaded count (none uploaded included), or uv / out NULL with
+ * n > 0.  n == 0 does nothing. */
+int hk_selftest_texture(hk_ctx* ctx, uint32_t texture, const float* uv, uint32_t n, float* out);
 
 #ifdef __cplusplus
 }

@@ -56,7 +56,7 @@ HK_HD void hk_texture_build_lut(float* lut)
 HK_HD int32_t hk_tex_f2i(float x)
 {
     if (x != x) return 0;
-    if (x >= 2147483520.0f) return 2147483647;
+    if (x >= 2147483648.0f) return 2147483647;
     if (x <= -2147483648.0f) return (int32_t)0x80000000u;
     return (int32_t)x;
 }

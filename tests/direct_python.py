@@ -124,9 +124,21 @@ class Scene:
         self.inst_u = self.inst_f.view(np.uint32)
         self.tlas = np.frombuffer(a["instance_nodes"].tobytes(), NODE)
         self.mat_f = np.frombuffer(a["materials"].tobytes(), F).reshape(-1, 20)
+        self.mat_u = self.mat_f.view(np.uint32)
+        self.textures = []  # set_textures
+        self.misread = None  # tests: a deliberate misreading of the textured retreive_surface
         self.lbvh = np.frombuffer(a["emissive_nodes"].tobytes(), NODE)
         self.emis_f = np.frombuffer(a["emissives"].tobytes(), F).reshape(-1, 16)
         self.emis_u = self.emis_f.view(np.uint32)
+
+    def set_textures(self, textures, lut):
+        """The bound material textures (hikari_amd.Texture: (H, W, 4) uint8 texels, srgb, address modes, filter) and
+        the (2, 256) texel decode table [sRGB, unorm] — the sRGB curve is the build's own pow, so like sin / cos / exp2
+        the table is taken from the oracle library (read through a 256x1 ramp) and checked separately against the
+        float64 formula by tests/test_texture_independent.py."""
+        self.textures = [(np.ascontiguousarray(t.rgba8, np.uint8), bool(t.srgb), int(t.address_u), int(t.address_v),
+                          int(t.filter)) for t in textures]
+        self.lut = np.asarray(lut, F).reshape(2, 256)
 
     def sin(self, x):
         return F(self.lib.hko_sin(float(x)))
@@ -350,11 +362,94 @@ def select_light_candidate(sc, fr, rand, position, normal, instance):
     return cand, info
 
 
+# ------------------------------------------------------------------ textures (light.wgsl:748-794)
+# textureSampleLevel(textures[id], samplers[id], uv, 0.0) on an RGBA8 image, scalar float32.  WGSL leaves the filter's
+# precision to the implementation; the build fixes it: nearest takes texel floor(u W); linear blends the
+# four texels around u W - 0.5 with weights a = frac and 1 - a, horizontally first, every operation in f32; texel
+# coordinates are converted to i32 saturating (NaN -> 0) and then wrapped by the sampler's GPUAddressMode; sRGB images
+# decode rgb through the sRGB table and alpha as unorm.
+def _texel_coord(x):
+    if x != x:
+        return 0
+    if x >= F(2147483648.0):
+        return 2 ** 31 - 1
+    if x <= F(-2147483648.0):
+        return -2 ** 31
+    return int(x)
+
+
+def _wrap(i, n, mode):
+    if mode == 1:  # repeat
+        return i % n
+    if mode == 2:  # mirror-repeat: 0 .. n-1, n-1 .. 0
+        r = i % (2 * n)
+        return r if r < n else 2 * n - 1 - r
+    return min(max(i, 0), n - 1)  # clamp-to-edge
+
+
+def _texel(sc, tex, i, j):
+    texels, srgb = tex[0], tex[1]
+    b = texels[j, i]
+    colour = sc.lut[0 if srgb else 1]
+    return (colour[b[0]], colour[b[1]], colour[b[2]], sc.lut[1][b[3]])
+
+
+def texture_sample_level(sc, tid, uv):
+    tex = sc.textures[tid]
+    h, w = tex[0].shape[:2]
+    au, av, filt = tex[2], tex[3], tex[4]
+    with np.errstate(all="ignore"):
+        if filt == 0:
+            i = _wrap(_texel_coord(np.floor(uv[0] * F(w))), w, au)
+            j = _wrap(_texel_coord(np.floor(uv[1] * F(h))), h, av)
+            return _texel(sc, tex, i, j)
+        x, y = uv[0] * F(w) - F(0.5), uv[1] * F(h) - F(0.5)
+        x0, y0 = np.floor(x), np.floor(y)
+        a, b = x - x0, y - y0
+        i0, j0 = _texel_coord(x0), _texel_coord(y0)
+        i1 = i0 if i0 == 2 ** 31 - 1 else i0 + 1  # i32: the neighbour of the last texel coordinate does not wrap
+        j1 = j0 if j0 == 2 ** 31 - 1 else j0 + 1
+        ia, ib, ja, jb = _wrap(i0, w, au), _wrap(i1, w, au), _wrap(j0, h, av), _wrap(j1, h, av)
+        t00, t10, t01, t11 = _texel(sc, tex, ia, ja), _texel(sc, tex, ib, ja), _texel(sc, tex, ia, jb), _texel(sc, tex, ib, jb)
+        ca, cb = F(1.0) - a, F(1.0) - b
+        return tuple((t00[k] * ca + t10[k] * a) * cb + (t01[k] * ca + t11[k] * a) * b for k in range(4))
+
+
+def texture_bound(sc, tid):
+    """`id != U32_MAX`, and an id past the bound textures counts as unbound (the build's choice: WGSL would index out
+    of the binding array).  With no texture bound at all this is the NO_TEXTURE pipeline."""
+    return tid != U32_MAX and tid < len(sc.textures)
+
+
+# material record words: 4 base_color_texture, 12 emissive_texture, 15 metallic_roughness_texture, 18 occlusion_texture
+def retreive_emissive(sc, m, uv):
+    e = tuple(sc.mat_f[m][8:12])
+    tid = int(sc.mat_u[m][12])
+    if texture_bound(sc, tid):
+        t = texture_sample_level(sc, tid, uv)
+        e = tuple(e[k] * t[k] for k in range(4))
+    return e
+
+
 # ------------------------------------------------------------------ shading (light.wgsl:714-908, Bevy 0.9.1)
-def retreive_surface(sc, m):
-    f = sc.mat_f[m]
+def retreive_surface(sc, m, uv):
+    f, u = sc.mat_f[m], sc.mat_u[m]
+    base = tuple(f[0:4])
+    if texture_bound(sc, int(u[4])):
+        t = texture_sample_level(sc, int(u[4]), uv)
+        base = tuple(base[k] * t[k] for k in range(4))
+    emissive = retreive_emissive(sc, m, uv)
+    metallic = f[14]
+    if texture_bound(sc, int(u[15])):
+        metallic = metallic * texture_sample_level(sc, int(u[15]), uv)[2 if sc.misread == "metallic_b" else 0]
+    occlusion = F(1.0)
+    if texture_bound(sc, int(u[18])):
+        t = texture_sample_level(sc, int(u[18]), uv)[0]
+        # the misreading: `*=` on the zero-initialised `var surface` in place of the assignment of 1.0 and of the
+        # sample (with the 1.0 kept, multiplying and assigning give the same bits)
+        occlusion = F(0.0) * t if sc.misread == "occlusion_multiplied" else t
     pr = clamp(f[13], 0.089, 1.0)
-    return {"base": tuple(f[0:3]), "emissive": tuple(f[8:12]), "metallic": f[14], "occlusion": F(1.0),
+    return {"base": base[:3], "emissive": emissive, "metallic": metallic, "occlusion": occlusion,
             "roughness": pr * pr, "reflectance": f[16]}
 
 
@@ -418,7 +513,7 @@ def input_radiance(sc, fr, direction, info, sample_directional, sample_emissive,
             radiance = fr["ambient"] if sample_ambient else v3(0, 0, 0)
             ambient = F(1.0)
     elif sample_emissive == info["inst"]:
-        e = sc.mat_f[info["mat"]][8:12]
+        e = retreive_emissive(sc, info["mat"], info["uv"])
         radiance = scale(tuple(e[:3]), F(255.0) * e[3])
     return (radiance[0], radiance[1], radiance[2], F(1.0) - ambient)
 
@@ -639,7 +734,7 @@ def direct_lit(sc, fr, gb, noise, bufs, x, y, emissive_lit, counts):
     bufs["variance"][y, x] = fmin(variance, MAX_VARIANCE)
     if fr["temporal_reuse"]:
         bufs["cur"][idx] = pack_reservoir(r)
-    surface = retreive_surface(sc, im_y)
+    surface = retreive_surface(sc, im_y, (velocity_uv[2], velocity_uv[3]))
     wp = position[:3]
     if fr.get("orthographic_view") is not None:  # calculate_view(position, view.projection[3].w == 1.0)
         V = normalize(fr["orthographic_view"])

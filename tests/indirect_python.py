@@ -247,7 +247,7 @@ def indirect_lit_ambient(sc, fm: Frame, bufs, x, y, counts):
                 s["sample_position"], s["sample_normal"], pdf = info["position"], info["normal"], rs_pdf
             bounce["sample_position"], bounce["sample_normal"] = info["position"], info["normal"]
             if hit["inst"] != U32_MAX:
-                surface = dp.retreive_surface(sc, info["mat"])
+                surface = dp.retreive_surface(sc, info["mat"], info["uv"])
                 surface["roughness"] = F(1.0)
                 sp3 = bounce["sample_position"][:3]
                 view_dir = dp.normalize(dp.sub(bounce["visible_position"][:3], sp3))
@@ -278,7 +278,7 @@ def indirect_lit_ambient(sc, fm: Frame, bufs, x, y, counts):
         hit, info = _trace_bounce(sc, fm, counts, origin, direction)
         s["sample_position"], s["sample_normal"] = info["position"], info["normal"]
         if hit["inst"] != U32_MAX:
-            surface = dp.retreive_surface(sc, info["mat"])
+            surface = dp.retreive_surface(sc, info["mat"], info["uv"])
             surface["roughness"] = F(1.0)
             sp3 = s["sample_position"][:3]
             view_dir = dp.normalize(dp.sub(s["visible_position"][:3], sp3))
@@ -298,7 +298,7 @@ def indirect_lit_ambient(sc, fm: Frame, bufs, x, y, counts):
             abs(previous_uv[0] - F(0.5)) <= F(0.5) and abs(previous_uv[1] - F(0.5)) <= F(0.5):
         pc = (dp.f2i(previous_uv[0] * F(W)), dp.f2i(previous_uv[1] * F(H)))
         bufs["prev_spatial"][pc[0] + W * pc[1]] = dp.pack_reservoir(r)
-    surface = dp.retreive_surface(sc, im_y)
+    surface = dp.retreive_surface(sc, im_y, (velocity_uv[2], velocity_uv[3]))
     V = fm.view_direction(position)
     with np.errstate(all="ignore"):
         L = dp.normalize(dp.sub(s["sample_position"][:3], s["visible_position"][:3]))
@@ -342,7 +342,7 @@ def spatial_reuse(sc, fm: Frame, bufs, x, y, emissive_lit):
         return
     im = fm.load("instance_material", dc)
     velocity_uv = fm.load("velocity_uv", dc)
-    surface = dp.retreive_surface(sc, dp.f2u(im[1]))
+    surface = dp.retreive_surface(sc, dp.f2u(im[1]), (velocity_uv[2], velocity_uv[3]))
     use_spatial_variance = r["count"] <= F(SPATIAL_VARIANCE_SAMPLE_THRESHOLD)
     juv = fm.jittered_uv(uv)
     previous_uv = (juv[0] - velocity_uv[0], juv[1] - velocity_uv[1])

@@ -21,7 +21,7 @@ def test_headers_declare_expected_entry_points():
     names = declared_symbols()
     for required in ("hk_create", "hk_destroy", "hk_scene_upload", "hk_resize", "hk_render_frame", "hk_denoise",
                      "hk_tone_sum", "hk_get_output", "hk_trace", "hk_last_error", "hks_build", "hk_scene_stage_bytes",
-                     "hk_scene_gbuffer_stack"):
+                     "hk_scene_gbuffer_stack", "hk_texture_upload", "hk_selftest_texture"):
         assert required in names
 
 
@@ -126,3 +126,10 @@ def test_runtime_options_documented():
         assert re.search(r"\b" + k + r"\b", doc), f"option {k} not documented"
     for src in (root / "bevy-hikari_amd" / "csrc").glob("*"):
         assert "getenv" not in src.read_text(), f"{src.name} reads the environment"
+
+
+def test_selftest_texture_refuses_a_null_context():
+    """hk_selftest_texture validates before it touches the device: no context, nothing to sample."""
+    import hikari_amd
+    L = hikari_amd._abi.lib()
+    assert L.hk_selftest_texture(None, 0, None, 0, None) == hikari_amd._abi.HK_ERR_INVALID

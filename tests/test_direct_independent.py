@@ -18,6 +18,7 @@ import pytest
 
 import direct_python as dp
 import scene_ladder as sl
+import texture_cases as tc
 
 
 def _gbuffer(o, w, h):
@@ -30,22 +31,46 @@ def _gbuffer(o, w, h):
     return {"position": pos, "normal": nrm, "instance_material": im, "velocity_uv": vel}
 
 
-@pytest.mark.parametrize("scene_fn", ["cornell", "scene", "city", "emitters_3", "no_emitters", "one_triangle"])
+TEXTURED = ["wrap_all", "emitters_textured"]  # tests/texture_cases.py: uvs in [-2.5, 3.5] over 18 samplers; textured emitters
+
+
+@pytest.mark.parametrize("scene_fn", ["cornell", "scene", "city", "emitters_3", "no_emitters", "one_triangle"] + TEXTURED)
 def test_direct_passes_match_python_restatement(scene_fn):
+    _direct_passes(scene_fn)
+
+
+def test_metallic_from_the_blue_channel_is_caught():
+    """Metallic taken from the image's blue channel (glTF's packing) instead of light.wgsl's `.r`: the comparison on
+    wrap_all fails."""
+    with pytest.raises(AssertionError):
+        _direct_passes("wrap_all", misread="metallic_b", frames=1)
+
+
+def test_occlusion_is_out_of_the_direct_passes_reach():
+    """Occlusion `*=` on the zero-initialised surface instead of assigned (occlusion 0 wherever an image is bound) is
+    caught by test_indirect_independent.py, and cannot be caught here: occlusion weighs only the ambient term, whose
+    weight 1 - radiance.a is non-zero only for a ray that left the scene, and the direct and emissive passes take no
+    ambient radiance (sample_ambient = false), so such a sample has luminance 0 and its reservoir weight w = 0.  This
+    pins that reading: the direct passes of wrap_all are the same words under the misreading."""
+    _direct_passes("wrap_all", misread="occlusion_multiplied", frames=3)
+
+
+def _direct_passes(scene_fn, misread=None, frames=6):
     import oracle as orc
     from hikari_amd import HikariSettings, Taa, Upscale, examples, frame_inputs, load_noise
     from oracle import Oracle
     w = h = 12 if scene_fn in sl.RUNGS else 16
-    scene, cam, lights = sl.example_or_rung(scene_fn)
+    scene, cam, lights = tc.CASES[scene_fn]() if scene_fn in tc.CASES else sl.example_or_rung(scene_fn)
     desc = scene.build()
-    sc = dp.Scene(scene.arrays(), orc.lib())
+    sc = tc.python_scene(scene, orc.lib())
+    sc.misread = misread
     noise = load_noise().reshape(16, 64, 64, 4)
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, taa=Taa.None_, indirect_spatial_reuse=False, denoise=False)
     s = st.to_c()
-    o = Oracle(desc, load_noise(), w, h, 1.0, threads=1)
+    o = Oracle(desc, load_noise(), w, h, 1.0, threads=1, textures=scene.textures)
     L = orc.lib()
     emitted = 0
-    for f in range(6):
+    for f in range(frames):
         before = [o.reservoirs(k).view(np.uint32).reshape(-1, 16)[: w * h].copy() for k in range(10)]
         fi = frame_inputs(f, cam, lights, w, h)
         o.render_gbuffer(fi)

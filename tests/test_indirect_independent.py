@@ -27,6 +27,7 @@ import denoise_python as dnp
 import direct_python as dp
 import indirect_python as ip
 import scene_ladder as sl
+import texture_cases as tc
 
 W, H = 24, 20
 # the ladder rungs (tests/scene_ladder.py) at a smaller frame: the three of them together cost about one example scene
@@ -79,29 +80,45 @@ def _check_channel(o, ch, bufs, spatial_pair_ids, tag):
         assert len(bad) == 0, (tag, name, k, bad[:5].tolist(), got[bad[0]].tolist(), bufs[name][bad[0]].tolist())
 
 
+# tests/texture_cases.py: the bounce hit's surface and the emitter hit's radiance are sampled at the hit's barycentric uv,
+# the primary surface at the G-buffer's
+TEXTURED = ["wrap_all", "emitters_textured"]
+
+
 @pytest.mark.parametrize("variant", ["default", "multi"])
-@pytest.mark.parametrize("scene_fn", ["cornell", "scene", "city", "emitters_3", "no_emitters", "one_triangle"])
+@pytest.mark.parametrize("scene_fn", ["cornell", "scene", "city", "emitters_3", "no_emitters", "one_triangle"] + TEXTURED)
 def test_indirect_spatial_denoise_match_python_restatement(scene_fn, variant):
+    _indirect_passes(scene_fn, variant)
+
+
+@pytest.mark.parametrize("misread", ["metallic_b", "occlusion_multiplied"])
+def test_surface_misreadings_are_caught(misread):
+    with pytest.raises(AssertionError):
+        _indirect_passes("wrap_all", "default", misread=misread, frames=1, size=LADDER_SIZE)
+
+
+def _indirect_passes(scene_fn, variant, misread=None, frames=6, size=None):
     import oracle as orc
     from hikari_amd import HikariSettings, Taa, Upscale, examples, frame_inputs, load_noise
     from oracle import Oracle
     global W, H
-    W, H = LADDER_SIZE if scene_fn in sl.RUNGS else (24, 20)
-    scene, cam, lights = sl.example_or_rung(scene_fn)
+    W, H = size or (LADDER_SIZE if scene_fn in sl.RUNGS else (24, 20))
+    scene, cam, lights = tc.CASES[scene_fn]() if scene_fn in tc.CASES else sl.example_or_rung(scene_fn)
     desc = scene.build()
-    sc = dp.Scene(scene.arrays(), orc.lib())
+    sc = tc.python_scene(scene, orc.lib())
+    sc.misread = misread
     noise = load_noise().reshape(16, 64, 64, 4)
     multi = variant == "multi"
     st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, taa=Taa.None_, indirect_spatial_reuse=True, denoise=True,
                         indirect_bounces=3 if multi else 1, emissive_spatial_reuse=multi,
                         max_reservoir_lifetime=3.0 if multi else 100.0)
     s = st.to_c()
-    o = Oracle(desc, load_noise(), W, H, 1.0, threads=1)
+    o = Oracle(desc, load_noise(), W, H, 1.0, threads=1, textures=scene.textures)
     L = orc.lib()
     counts = {"top": 0, "emitter": 0}
     reused = lifetime_kept = 0
     stats = {}
-    for f in range(6):
+    for f in range(frames):
         before = [o.reservoirs(k).view(np.uint32).reshape(-1, 16)[: W * H].copy() for k in range(10)]
         fi = frame_inputs(f, cam, lights, W, H)
         o.render_gbuffer(fi)
