@@ -3036,6 +3036,113 @@ void launch_f16(const float* in, uint32_t n, uint16_t* out, hipStream_t st)
     hipLaunchKernelGGL(k_f16, dim3((n + 255u) / 256u), dim3(256), 0, st, in, n, out);
 }
 
+// hk_selftest_math: scalar function FN (hk_math_fn, include/hikari_amd.h) of element i by thread i, each called as the
+// frame kernels call it; one instantiation per id, so nothing of another id's code shapes how a function compiles.
+// a, b, out0, out1: n words each; b, out1 and rb (RN(1 / b[i]) from the host, HK_MATH_DIV_BY only) are NULL where the
+// id does not use them (the caller checked the required ones).
+template <int FN>
+__global__ __launch_bounds__(256) void k_math(const uint32_t* a, const uint32_t* b, const float* rb, uint32_t n,
+                                              uint32_t* out0, uint32_t* out1)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t ua = a[i];
+    const float x = __uint_as_float(ua);
+    uint32_t ub = 0u;
+    if constexpr (FN == HK_MATH_POW || FN == HK_MATH_UNPACK_SNORM8_FAST || FN == HK_MATH_MINF || FN == HK_MATH_MAXF ||
+                  FN == HK_MATH_DIV || FN == HK_MATH_DIV_BY)
+        ub = b[i];
+    const float y = __uint_as_float(ub);
+    uint32_t r0 = 0u;
+    if constexpr (FN == HK_MATH_EXP2) r0 = __float_as_uint(hk_exp2(x));
+    else if constexpr (FN == HK_MATH_EXP) r0 = __float_as_uint(hk_exp(x));
+    else if constexpr (FN == HK_MATH_EXP_WEIGHT) r0 = __float_as_uint(hk_exp_weight(x));
+    else if constexpr (FN == HK_MATH_LOG2) r0 = __float_as_uint(hk_log2(x));
+    else if constexpr (FN == HK_MATH_POW) r0 = __float_as_uint(hk_pow(x, y));
+    else if constexpr (FN == HK_MATH_POW2) r0 = __float_as_uint(hk_pow2(x));
+    else if constexpr (FN == HK_MATH_POW5) r0 = __float_as_uint(hk_pow5(x));
+    else if constexpr (FN == HK_MATH_POW16) r0 = __float_as_uint(hk_pow16(x));
+    else if constexpr (FN == HK_MATH_SINCOS) {
+        float s, c;
+        hk_sincos(x, &s, &c);
+        r0 = __float_as_uint(s);
+        out1[i] = __float_as_uint(c);
+    } else if constexpr (FN == HK_MATH_UNORM16) r0 = hk_unorm16(x);
+    else if constexpr (FN == HK_MATH_SNORM8) r0 = hk_snorm8(x);
+    else if constexpr (FN == HK_MATH_UNPACK_UNORM16_FAST) r0 = __float_as_uint(hk_unpack_unorm16_fast(ua));
+    else if constexpr (FN == HK_MATH_UNPACK_SNORM8_FAST) {
+        // (the kernels pass the lane as a literal)
+        const uint32_t lane = ub & 3u;
+        const float v = lane == 0u   ? hk_unpack_snorm8_fast(ua, 0)
+                        : lane == 1u ? hk_unpack_snorm8_fast(ua, 1)
+                        : lane == 2u ? hk_unpack_snorm8_fast(ua, 2)
+                                     : hk_unpack_snorm8_fast(ua, 3);
+        r0 = __float_as_uint(v);
+    } else if constexpr (FN == HK_MATH_UNORM8_FAST) r0 = __float_as_uint(hk_unorm8_fast(ua));
+    else if constexpr (FN == HK_MATH_RANDOM_FLOAT) r0 = __float_as_uint(hk_random_float(ua));
+    else if constexpr (FN == HK_MATH_FRACT) r0 = __float_as_uint(hk_fract(x));
+    else if constexpr (FN == HK_MATH_MINF) r0 = __float_as_uint(hk_minf(x, y));
+    else if constexpr (FN == HK_MATH_MAXF) r0 = __float_as_uint(hk_maxf(x, y));
+    else if constexpr (FN == HK_MATH_SATURATE) r0 = __float_as_uint(hk_saturate(x));
+    else if constexpr (FN == HK_MATH_SIGNF) r0 = __float_as_uint(hk_signf(x));
+    else if constexpr (FN == HK_MATH_DIV) r0 = __float_as_uint((mk3(x, x, x) / y).x);
+    else if constexpr (FN == HK_MATH_SQRT) r0 = __float_as_uint(sqrtf(x));  // length()'s sqrtf, of the argument itself
+    else if constexpr (FN == HK_MATH_RCP_EXACT) r0 = __float_as_uint(rcp_exact(x));
+    else if constexpr (FN == HK_MATH_RCP_FAST) r0 = __float_as_uint(rcp_fast_ok(x) ? rcp_fast(x) : 1.0f / x);
+    else if constexpr (FN == HK_MATH_DIV_BY) r0 = __float_as_uint(div_by(x, y, rb[i]));
+    else if constexpr (FN == HK_MATH_F2U32) r0 = f2u32(x);
+    else if constexpr (FN == HK_MATH_F2I32) r0 = (uint32_t)f2i32(x);
+    else if constexpr (FN == HK_MATH_UNPACK_F16) {
+        r0 = __float_as_uint(unpack_lo16float(ua));
+        if (out1) out1[i] = __float_as_uint(unpack_hi16float(ua));
+    }
+    out0[i] = r0;
+}
+template <int FN>
+static void launch_math_fn(const uint32_t* a, const uint32_t* b, const float* rb, uint32_t n, uint32_t* out0,
+                           uint32_t* out1, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_math<FN>, dim3((n + 255u) / 256u), dim3(256), 0, st, a, b, rb, n, out0, out1);
+}
+bool launch_math(int fn, const uint32_t* a, const uint32_t* b, const float* rb, uint32_t n, uint32_t* out0,
+                 uint32_t* out1, hipStream_t st)
+{
+    switch (fn) {
+#define HK_MATH_CASE(id) \
+    case id: launch_math_fn<id>(a, b, rb, n, out0, out1, st); return true
+        HK_MATH_CASE(HK_MATH_EXP2);
+        HK_MATH_CASE(HK_MATH_EXP);
+        HK_MATH_CASE(HK_MATH_EXP_WEIGHT);
+        HK_MATH_CASE(HK_MATH_LOG2);
+        HK_MATH_CASE(HK_MATH_POW);
+        HK_MATH_CASE(HK_MATH_POW2);
+        HK_MATH_CASE(HK_MATH_POW5);
+        HK_MATH_CASE(HK_MATH_POW16);
+        HK_MATH_CASE(HK_MATH_SINCOS);
+        HK_MATH_CASE(HK_MATH_UNORM16);
+        HK_MATH_CASE(HK_MATH_SNORM8);
+        HK_MATH_CASE(HK_MATH_UNPACK_UNORM16_FAST);
+        HK_MATH_CASE(HK_MATH_UNPACK_SNORM8_FAST);
+        HK_MATH_CASE(HK_MATH_UNORM8_FAST);
+        HK_MATH_CASE(HK_MATH_RANDOM_FLOAT);
+        HK_MATH_CASE(HK_MATH_FRACT);
+        HK_MATH_CASE(HK_MATH_MINF);
+        HK_MATH_CASE(HK_MATH_MAXF);
+        HK_MATH_CASE(HK_MATH_SATURATE);
+        HK_MATH_CASE(HK_MATH_SIGNF);
+        HK_MATH_CASE(HK_MATH_DIV);
+        HK_MATH_CASE(HK_MATH_SQRT);
+        HK_MATH_CASE(HK_MATH_RCP_EXACT);
+        HK_MATH_CASE(HK_MATH_RCP_FAST);
+        HK_MATH_CASE(HK_MATH_DIV_BY);
+        HK_MATH_CASE(HK_MATH_F2U32);
+        HK_MATH_CASE(HK_MATH_F2I32);
+        HK_MATH_CASE(HK_MATH_UNPACK_F16);
+#undef HK_MATH_CASE
+    }
+    return false;
+}
+
 // the kernels' own sample_material_texture (hk_device.h) of texture `id` at n uv pairs; the caller checked id < n_textures
 __global__ __launch_bounds__(256) void k_texture_check(Scene sc, uint32_t id, const float* uv, uint32_t n, float* out)
 {

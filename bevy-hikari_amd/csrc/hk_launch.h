@@ -265,6 +265,9 @@ void launch_div_check(float d, float r, uint32_t lo, uint32_t hi, unsigned long 
 void launch_rcp_check(uint32_t lo, uint32_t hi, unsigned long long* bad, hipStream_t st);
 void launch_count_check(const uint32_t* values, uint32_t n, unsigned long long* sum, hipStream_t st);
 void launch_f16(const float* in, uint32_t n, uint16_t* out, hipStream_t st);
+// false: fn is no hk_math_fn (nothing launched)
+bool launch_math(int fn, const uint32_t* a, const uint32_t* b, const float* rb, uint32_t n, uint32_t* out0,
+                 uint32_t* out1, hipStream_t st);
 void launch_texture_check(const Scene& sc, uint32_t id, const float* uv, uint32_t n, float* out, hipStream_t st);
 void launch_trace(const Scene& sc, const float* rays, const float* max_d, const float* early_d, const uint32_t* excl,
                   uint32_t n, uint32_t* hits, unsigned long long* top, hipStream_t st);

@@ -3265,4 +3265,51 @@ int hk_selftest_texture(hk_ctx* c, uint32_t texture, const float* uv, uint32_t n
     return HK_OK;
 }
 
+int hk_selftest_math(hk_ctx* c, int fn, const uint32_t* a, const uint32_t* b, uint32_t n, uint32_t* out0,
+                     uint32_t* out1)
+{
+    if (!c || fn < 0 || fn >= HK_MATH_COUNT) return HK_ERR_INVALID;
+    const bool two = fn == HK_MATH_POW || fn == HK_MATH_UNPACK_SNORM8_FAST || fn == HK_MATH_MINF ||
+                     fn == HK_MATH_MAXF || fn == HK_MATH_DIV || fn == HK_MATH_DIV_BY;
+    if (fn == HK_MATH_SINCOS && !out1) return HK_ERR_INVALID;
+    if (n && (!a || !out0 || (two && !b))) return HK_ERR_INVALID;
+    if (n == 0) return HK_OK;
+    (void)hipSetDevice(c->device);
+    hipStream_t st = pick(c, nullptr);
+    const bool pair = out1 && (fn == HK_MATH_SINCOS || fn == HK_MATH_UNPACK_F16);
+    const size_t bytes = (size_t)n * 4;
+    uint32_t *d_a = nullptr, *d_b = nullptr, *d_out0 = nullptr, *d_out1 = nullptr;
+    float* d_rb = nullptr;
+    HK_HIP(c, hipMalloc(&d_a, bytes));
+    HK_HIP(c, hipMalloc(&d_out0, bytes));
+    HK_HIP(c, hipMemcpy(d_a, a, bytes, hipMemcpyHostToDevice));
+    if (two) {
+        HK_HIP(c, hipMalloc(&d_b, bytes));
+        HK_HIP(c, hipMemcpy(d_b, b, bytes, hipMemcpyHostToDevice));
+    }
+    if (fn == HK_MATH_DIV_BY) {
+        // the reciprocal as frame_args evaluates inv_s: the host's IEEE divide
+        std::vector<float> rb(n);
+        for (uint32_t i = 0; i < n; ++i) {
+            float d;
+            memcpy(&d, &b[i], 4);
+            rb[i] = 1.0f / d;
+        }
+        HK_HIP(c, hipMalloc(&d_rb, bytes));
+        HK_HIP(c, hipMemcpy(d_rb, rb.data(), bytes, hipMemcpyHostToDevice));
+    }
+    if (pair) HK_HIP(c, hipMalloc(&d_out1, bytes));
+    if (!launch_math(fn, d_a, d_b, d_rb, n, d_out0, d_out1, st)) return HK_ERR_INVALID;
+    HK_HIP(c, hipGetLastError());
+    HK_HIP(c, hipMemcpyAsync(out0, d_out0, bytes, hipMemcpyDeviceToHost, st));
+    if (pair) HK_HIP(c, hipMemcpyAsync(out1, d_out1, bytes, hipMemcpyDeviceToHost, st));
+    HK_HIP(c, hipStreamSynchronize(st));
+    release(d_a);
+    release(d_b);
+    release(d_rb);
+    release(d_out0);
+    release(d_out1);
+    return HK_OK;
+}
+
 }  // extern "C"

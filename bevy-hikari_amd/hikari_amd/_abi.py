@@ -20,6 +20,17 @@ HK_ERR_NO_DEVICE = -4
 
 RESERVOIR_BUFFERS = 10  # HK_RESERVOIR_BUFFERS
 
+# enum hk_math_fn in its order (HK_MATH_<NAME>; tests/test_math_cases.py compares this list with the header)
+MATH_FN_NAMES = (
+    "exp2", "exp", "exp_weight", "log2", "pow", "pow2", "pow5", "pow16", "sincos",
+    "unorm16", "snorm8", "unpack_unorm16_fast", "unpack_snorm8_fast", "unorm8_fast", "random_float",
+    "fract", "minf", "maxf", "saturate", "signf",
+    "div", "sqrt", "rcp_exact", "rcp_fast", "div_by", "f2u32", "f2i32", "unpack_f16",
+)
+MATH_FN = {name: i for i, name in enumerate(MATH_FN_NAMES)}
+MATH_FN_TWO_OPERANDS = ("pow", "unpack_snorm8_fast", "minf", "maxf", "div", "div_by")
+MATH_FN_TWO_RESULTS = ("sincos", "unpack_f16")
+
 # hk_output_id
 OUT_ALBEDO = 0
 OUT_VARIANCE = (1, 2, 3)
@@ -229,6 +240,7 @@ def lib() -> C.CDLL:
         "hk_selftest_rcp": (i32, [vp, u32, u32, C.POINTER(C.c_uint64)]),
         "hk_selftest_count": (i32, [vp, vp, u32, C.POINTER(C.c_uint64)]),
         "hk_selftest_texture": (i32, [vp, u32, vp, u32, vp]),
+        "hk_selftest_math": (i32, [vp, i32, vp, vp, u32, vp, vp]),
         "hks_create": (vp, []),
         "hks_destroy": (None, [vp]),
         "hks_last_error": (C.c_char_p, [vp]),
@@ -255,7 +267,7 @@ EXPORTED_SYMBOLS = [
     "hk_set_noise", "hk_texture_upload", "hk_resize", "hk_resize_striped", "hk_set_band_halo", "hk_band_info", "hk_band_window_grow", "hk_reservoir_rows", "hk_resize_tile", "hk_tile_info", "hk_copy_output_rect", "hk_copy_output_rows", "hk_render_gbuffer", "hk_set_gbuffer_plane", "hk_render_frame",
     "hk_denoise", "hk_tone_sum", "hk_update_instances", "hk_update_meshes", "hk_set_instances", "hk_scene_counts", "hk_instance_set_counts", "hk_read_scene_array", "hk_post_process", "hk_set_fsr1_sharpness", "hk_present", "hk_present_info", "hk_get_present", "hk_accumulate", "hk_resolve_accumulation", "hk_output_info", "hk_get_output", "hk_output_device_ptr", "hk_sync", "hk_set_wavefront", "hk_lane_stats", "hk_dump_reservoirs",
     "hk_load_reservoirs", "hk_reset_counters", "hk_read_counters", "hk_enable_kernel_timing", "hk_kernel_timing", "hk_set_kernel_timing_interval",
-    "hk_trace", "hk_selftest_f16", "hk_selftest_div", "hk_selftest_rcp", "hk_selftest_count", "hk_selftest_texture", "hks_create", "hks_destroy", "hks_last_error", "hks_add_mesh", "hks_add_material",
+    "hk_trace", "hk_selftest_f16", "hk_selftest_div", "hk_selftest_rcp", "hk_selftest_count", "hk_selftest_texture", "hk_selftest_math", "hks_create", "hks_destroy", "hks_last_error", "hks_add_mesh", "hks_add_material",
     "hks_add_instance", "hks_build", "hks_get_desc", "hk_scene_shared_transform", "hks_shared_transform",
 ]
 

@@ -511,6 +511,23 @@ class HikariRenderer:
                "hk_selftest_texture")
         return out
 
+    def selftest_math(self, fn, a: np.ndarray, b: np.ndarray = None):
+        """The kernels' own scalar function `fn` (an hk_math_fn id or its name in _abi.MATH_FN) on the uint32 words
+        `a` (and `b` for the two-operand ids): the result words, a pair (out0, out1) for sincos and unpack_f16."""
+        from . import _abi
+        name = fn if isinstance(fn, str) else _abi.MATH_FN_NAMES[fn]
+        a = np.ascontiguousarray(a, np.uint32).ravel()
+        if b is not None:
+            b = np.ascontiguousarray(b, np.uint32).ravel()
+            if len(b) != len(a):
+                raise ValueError("a and b differ in length")
+        out0 = np.empty(len(a), np.uint32)
+        out1 = np.empty(len(a), np.uint32) if name in _abi.MATH_FN_TWO_RESULTS else None
+        _check(self.ctx, self._L.hk_selftest_math(self.ctx, _abi.MATH_FN[name], a.ctypes.data,
+                                                  None if b is None else b.ctypes.data, len(a), out0.ctypes.data,
+                                                  None if out1 is None else out1.ctypes.data), "hk_selftest_math")
+        return out0 if out1 is None else (out0, out1)
+
     def selftest_f16(self, values: np.ndarray) -> np.ndarray:
         """The kernels' own f32 -> f16 conversion applied to `values` (uint16 bit patterns)."""
         v = np.ascontiguousarray(values, np.float32)

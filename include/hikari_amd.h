@@ -575,6 +575,52 @@ int hk_selftest_count(hk_ctx* ctx, const uint32_t* values, uint32_t n, uint64_t*
  * HK_ERR_INVALID, before any launch: texture >= the uploaded count (none uploaded included), or uv / out NULL with
  * n > 0.  n == 0 does nothing. */
 int hk_selftest_texture(hk_ctx* ctx, uint32_t texture, const float* uv, uint32_t n, float* out);
+/* ---- self-test of the kernels' scalar functions (include/hk_math.h as hipcc compiles it for the device, and the
+ * arithmetic helpers of hk_device.h), so that the device's bits can be compared with the host's on given inputs
+ * (oracle hko_math_array, tests/test_gpu_math.py).  One function id per call; element i is computed by thread i of
+ * 256-thread workgroups, each id calling its function as the frame kernels do.  Operands and results are 32-bit
+ * words: f32 bit patterns, or u32 codes where the function takes or returns one. */
+enum hk_math_fn {
+    /* hk_math.h transcendentals */
+    HK_MATH_EXP2 = 0,            /* hk_exp2(a) */
+    HK_MATH_EXP,                 /* hk_exp(a) */
+    HK_MATH_EXP_WEIGHT,          /* hk_exp_weight(a) */
+    HK_MATH_LOG2,                /* hk_log2(a) */
+    HK_MATH_POW,                 /* hk_pow(a, b) */
+    HK_MATH_POW2,                /* hk_pow2(a) */
+    HK_MATH_POW5,                /* hk_pow5(a) */
+    HK_MATH_POW16,               /* hk_pow16(a) */
+    HK_MATH_SINCOS,              /* hk_sincos(a): out0 = sin, out1 = cos */
+    /* hk_math.h packing */
+    HK_MATH_UNORM16,             /* hk_unorm16(a): f32 -> code */
+    HK_MATH_SNORM8,              /* hk_snorm8(a): f32 -> code */
+    HK_MATH_UNPACK_UNORM16_FAST, /* hk_unpack_unorm16_fast(a): code -> f32 */
+    HK_MATH_UNPACK_SNORM8_FAST,  /* hk_unpack_snorm8_fast(a, b & 3): byte lane b of word a -> f32 */
+    HK_MATH_UNORM8_FAST,         /* hk_unorm8_fast(a): code -> f32 */
+    HK_MATH_RANDOM_FLOAT,        /* hk_random_float(a): u32 -> f32 */
+    /* hk_math.h small operations */
+    HK_MATH_FRACT,               /* hk_fract(a) */
+    HK_MATH_MINF,                /* hk_minf(a, b) */
+    HK_MATH_MAXF,                /* hk_maxf(a, b) */
+    HK_MATH_SATURATE,            /* hk_saturate(a) */
+    HK_MATH_SIGNF,               /* hk_signf(a) */
+    /* hk_device.h arithmetic (host reference: the IEEE operation) */
+    HK_MATH_DIV,                 /* a / b, the divide behind operator/ */
+    HK_MATH_SQRT,                /* sqrtf(a), the one in length() */
+    HK_MATH_RCP_EXACT,           /* rcp_exact(a); reference 1 / a */
+    HK_MATH_RCP_FAST,            /* one component of inv(): rcp_fast(a) where rcp_fast_ok(a), else 1.0f / a */
+    HK_MATH_DIV_BY,              /* div_by(a, b, RN(1 / b)), the reciprocal evaluated on the host; reference a / b */
+    HK_MATH_F2U32,               /* f2u32(a): saturating f32 -> u32 */
+    HK_MATH_F2I32,               /* f2i32(a): saturating f32 -> i32 */
+    /* hk_device.h f16 decode */
+    HK_MATH_UNPACK_F16,          /* out0 = unpack_lo16float(a), out1 = unpack_hi16float(a) (out1 may be NULL) */
+    HK_MATH_COUNT
+};
+/* a, b: n host words each (b may be NULL for the one-operand ids); out0, out1: n host words each (out1 may be NULL
+ * except for HK_MATH_SINCOS).  HK_ERR_INVALID, before any launch: an unknown fn, a required pointer NULL with n > 0,
+ * out1 NULL for HK_MATH_SINCOS.  n == 0 does nothing. */
+int hk_selftest_math(hk_ctx* ctx, int fn, const uint32_t* a, const uint32_t* b, uint32_t n, uint32_t* out0,
+                     uint32_t* out1);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,9 @@
  * operations that both targets round identically: +, -, *, correctly-rounded / and
  * sqrt, rint/floor, integer bit manipulation.  Both sides compile with
  * -ffp-contract=off, so no mul+add is ever fused.  Accuracy vs libm is checked by
- * tests/test_math.py (<= 4 ulp on the ranges the integrator uses).
+ * tests/test_oracle_kat.py::test_transcendentals_accuracy (<= 4 ulp on the ranges the integrator uses), and that the
+ * device build of this header gives the host build's bits by tests/test_gpu_math.py (hk_selftest_math against
+ * hko_math_array on the inputs of tests/math_cases.py; all 2^32 patterns once, tools/math_sweep.py).
  *
  * Plain C99 + HIP: HK_HD marks functions callable from host and device.
  */
@@ -42,8 +44,31 @@ typedef union { float f; uint32_t u; int32_t i; } hk_fbits;
 HK_HD uint32_t hk_f2u(float f) { hk_fbits b; b.f = f; return b.u; }
 HK_HD float hk_u2f(uint32_t u) { hk_fbits b; b.u = u; return b.f; }
 
-HK_HD float hk_minf(float a, float b) { return fminf(a, b); } /* IEEE minNum */
-HK_HD float hk_maxf(float a, float b) { return fmaxf(a, b); } /* IEEE maxNum */
+/* IEEE minNum / maxNum with every NaN taken as missing data, a signalling one included: the other operand, and a NaN
+ * only when both are.  The device's fminf / fmaxf are that (the compiler quiets a signalling operand before
+ * v_min_f32 / v_max_f32); glibc's return a quiet NaN for a signalling operand (IEEE 754-2008), after which
+ * hk_saturate(sNaN) was 1 on the host and 0 on the device (tests/test_gpu_math.py found it).  So the host states the
+ * whole rule itself, without libm — also -0 < +0, as the device orders the zeros, which minNum leaves open and
+ * which gcc's inline fminf / fmaxf decide by operand order.  For numbers and quiet NaNs the value is fminf's. */
+#if defined(__HIP_DEVICE_COMPILE__)
+HK_HD float hk_minf(float a, float b) { return fminf(a, b); }
+HK_HD float hk_maxf(float a, float b) { return fmaxf(a, b); }
+#else
+HK_HD float hk_minf(float a, float b)
+{
+    if (b != b) return a;
+    if (a != a) return b;
+    if (a == b) return hk_u2f(hk_f2u(a) | hk_f2u(b)); /* equal, or the two zeros: -0 if either is */
+    return a < b ? a : b;
+}
+HK_HD float hk_maxf(float a, float b)
+{
+    if (b != b) return a;
+    if (a != a) return b;
+    if (a == b) return hk_u2f(hk_f2u(a) & hk_f2u(b)); /* +0 if either is */
+    return a > b ? a : b;
+}
+#endif
 HK_HD float hk_clampf(float x, float lo, float hi) { return hk_minf(hk_maxf(x, lo), hi); }
 HK_HD float hk_saturate(float x) { return hk_clampf(x, 0.0f, 1.0f); }
 HK_HD float hk_fract(float x) { return x - floorf(x); }

@@ -2670,3 +2670,67 @@ void hko_f32_to_f16_array(const float* in, size_t n, uint16_t* out)
     for (long i = 0; i < (long)n; ++i) out[i] = (uint16_t)hk_f32_to_f16(in[i]);
 }
 uint32_t hko_hash(uint32_t x) { return hk_hash(x); }
+
+/* The host's bits for hk_selftest_math's function ids (enum hk_math_fn, include/hikari_amd.h): hk_math.h's function
+ * where the id names one; for the device-only helpers the plain restatement — the IEEE operation (rcp_exact, rcp_fast
+ * and div_by are not mirrored: their reference is the quotient), the divisions for the _fast decodes, the saturating
+ * conversions above, hk_f16_to_f32 on each half.  0: done; -1: unknown fn or a required pointer NULL. */
+static inline void math_one(int fn, uint32_t ua, uint32_t ub, uint32_t* r0, uint32_t* r1)
+{
+    const float x = hk_u2f(ua), y = hk_u2f(ub);
+    float s, c;
+    switch (fn) {
+    case HK_MATH_EXP2: *r0 = hk_f2u(hk_exp2(x)); break;
+    case HK_MATH_EXP: *r0 = hk_f2u(hk_exp(x)); break;
+    case HK_MATH_EXP_WEIGHT: *r0 = hk_f2u(hk_exp_weight(x)); break;
+    case HK_MATH_LOG2: *r0 = hk_f2u(hk_log2(x)); break;
+    case HK_MATH_POW: *r0 = hk_f2u(hk_pow(x, y)); break;
+    case HK_MATH_POW2: *r0 = hk_f2u(hk_pow2(x)); break;
+    case HK_MATH_POW5: *r0 = hk_f2u(hk_pow5(x)); break;
+    case HK_MATH_POW16: *r0 = hk_f2u(hk_pow16(x)); break;
+    case HK_MATH_SINCOS:
+        hk_sincos(x, &s, &c);
+        *r0 = hk_f2u(s);
+        *r1 = hk_f2u(c);
+        break;
+    case HK_MATH_UNORM16: *r0 = hk_unorm16(x); break;
+    case HK_MATH_SNORM8: *r0 = hk_snorm8(x); break;
+    case HK_MATH_UNPACK_UNORM16_FAST: *r0 = hk_f2u(hk_unpack_unorm16(ua)); break;
+    case HK_MATH_UNPACK_SNORM8_FAST: *r0 = hk_f2u(hk_unpack_snorm8(ua, (int)(ub & 3u))); break;
+    case HK_MATH_UNORM8_FAST: *r0 = hk_f2u((float)(ua & 0xFFu) / 255.0f); break;
+    case HK_MATH_RANDOM_FLOAT: *r0 = hk_f2u(hk_random_float(ua)); break;
+    case HK_MATH_FRACT: *r0 = hk_f2u(hk_fract(x)); break;
+    case HK_MATH_MINF: *r0 = hk_f2u(hk_minf(x, y)); break;
+    case HK_MATH_MAXF: *r0 = hk_f2u(hk_maxf(x, y)); break;
+    case HK_MATH_SATURATE: *r0 = hk_f2u(hk_saturate(x)); break;
+    case HK_MATH_SIGNF: *r0 = hk_f2u(hk_signf(x)); break;
+    case HK_MATH_DIV:
+    case HK_MATH_DIV_BY: *r0 = hk_f2u(x / y); break;
+    case HK_MATH_SQRT: *r0 = hk_f2u(sqrtf(x)); break;
+    case HK_MATH_RCP_EXACT:
+    case HK_MATH_RCP_FAST: *r0 = hk_f2u(1.0f / x); break;
+    case HK_MATH_F2U32: *r0 = f2u32(x); break;
+    case HK_MATH_F2I32: *r0 = (uint32_t)f2i32(x); break;
+    case HK_MATH_UNPACK_F16:
+        *r0 = hk_f2u(hk_f16_to_f32(ua & 0xFFFFu));
+        *r1 = hk_f2u(hk_f16_to_f32(ua >> 16));
+        break;
+    default: break;
+    }
+}
+int hko_math_array(int fn, const uint32_t* a, const uint32_t* b, size_t n, uint32_t* out0, uint32_t* out1)
+{
+    if (fn < 0 || fn >= HK_MATH_COUNT) return -1;
+    const int two = fn == HK_MATH_POW || fn == HK_MATH_UNPACK_SNORM8_FAST || fn == HK_MATH_MINF ||
+                    fn == HK_MATH_MAXF || fn == HK_MATH_DIV || fn == HK_MATH_DIV_BY;
+    if (fn == HK_MATH_SINCOS && !out1) return -1;
+    if (n && (!a || !out0 || (two && !b))) return -1;
+#pragma omp parallel for schedule(static)
+    for (long long i = 0; i < (long long)n; ++i) {
+        uint32_t r0 = 0u, r1 = 0u;
+        math_one(fn, a[i], two ? b[i] : 0u, &r0, &r1);
+        out0[i] = r0;
+        if (out1) out1[i] = r1;
+    }
+    return 0;
+}

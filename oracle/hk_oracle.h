@@ -88,6 +88,9 @@ float hko_cos(float x);
 uint32_t hko_f32_to_f16(float x);
 void hko_f32_to_f16_array(const float* in, size_t n, uint16_t* out);
 uint32_t hko_hash(uint32_t x);
+/* the host's bits for hk_selftest_math's ids (enum hk_math_fn): words as there, out1 only for the two-result ids
+ * (NULL allowed except for HK_MATH_SINCOS); 0, or -1 for an unknown fn or a required pointer NULL */
+int hko_math_array(int fn, const uint32_t* a, const uint32_t* b, size_t n, uint32_t* out0, uint32_t* out1);
 
 #ifdef __cplusplus
 }

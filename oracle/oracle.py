@@ -68,6 +68,7 @@ def lib() -> C.CDLL:
         "hko_sample_texture": (None, [vp, u32, vp, u32, vp]),
         "hko_hash": (u32, [u32]),
         "hko_unpack_fast_mismatches": (u32, []),
+        "hko_math_array": (C.c_int, [C.c_int, vp, vp, C.c_size_t, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -75,6 +76,25 @@ def lib() -> C.CDLL:
         fn.argtypes = args
     _L = L
     return L
+
+
+def math_array(fn, a, b=None):
+    """The host's bits for hk_selftest_math's function `fn` (an hk_math_fn id or its name in hikari_amd._abi.MATH_FN)
+    on the uint32 words `a` (and `b`): the result words, a pair (out0, out1) for sincos and unpack_f16."""
+    from hikari_amd import _abi
+    name = fn if isinstance(fn, str) else _abi.MATH_FN_NAMES[fn]
+    a = np.ascontiguousarray(a, np.uint32).ravel()
+    if b is not None:
+        b = np.ascontiguousarray(b, np.uint32).ravel()
+        if len(b) != len(a):
+            raise ValueError("a and b differ in length")
+    out0 = np.empty(len(a), np.uint32)
+    out1 = np.empty(len(a), np.uint32) if name in _abi.MATH_FN_TWO_RESULTS else None
+    rc = lib().hko_math_array(_abi.MATH_FN[name], a.ctypes.data, None if b is None else b.ctypes.data, len(a),
+                              out0.ctypes.data, None if out1 is None else out1.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"hko_math_array({name}) refused its arguments")
+    return out0 if out1 is None else (out0, out1)
 
 
 def default_threads() -> int:

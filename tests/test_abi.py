@@ -21,7 +21,7 @@ def test_headers_declare_expected_entry_points():
     names = declared_symbols()
     for required in ("hk_create", "hk_destroy", "hk_scene_upload", "hk_resize", "hk_render_frame", "hk_denoise",
                      "hk_tone_sum", "hk_get_output", "hk_trace", "hk_last_error", "hks_build", "hk_scene_stage_bytes",
-                     "hk_scene_gbuffer_stack", "hk_texture_upload", "hk_selftest_texture"):
+                     "hk_scene_gbuffer_stack", "hk_texture_upload", "hk_selftest_texture", "hk_selftest_math"):
         assert required in names
 
 
@@ -133,3 +133,11 @@ def test_selftest_texture_refuses_a_null_context():
     import hikari_amd
     L = hikari_amd._abi.lib()
     assert L.hk_selftest_texture(None, 0, None, 0, None) == hikari_amd._abi.HK_ERR_INVALID
+
+
+def test_selftest_math_refuses_a_null_context_and_unknown_ids():
+    """hk_selftest_math validates before it touches the device: no context, or no such function."""
+    import hikari_amd
+    L = hikari_amd._abi.lib()
+    assert L.hk_selftest_math(None, 0, None, None, 0, None, None) == hikari_amd._abi.HK_ERR_INVALID
+    assert len(hikari_amd._abi.MATH_FN) == len(hikari_amd._abi.MATH_FN_NAMES) == 28
