@@ -129,6 +129,11 @@ HKD void tile_origin(const Frame& F, int32_t row0, int32_t& x0, int32_t& y0)
 constexpr int SPATIAL_ORDER = XCD_STRIPS;  // spatial reuse: neighbour reservoirs +/- 20 px in one XCD's L2
 constexpr int TRACE_ORDER = RASTER;        // G-buffer and light-pass kernels
 constexpr int DENOISE_ORDER = XCD_STRIPS;  // the a-trous levels (taps up to 8 px away): city 4K 0.529 -> 0.436 ms per level
+// Background tile skip (TileKeep): tile (tx, ty) of the launch's grid is outside the tiles to run.  Workgroup-uniform
+// and on scalars (the raster order's tile is the workgroup's index), so a kernel tests it before anything else.
+static_assert(TRACE_ORDER == RASTER, "tile_skipped takes the workgroup's index as its tile");
+HKD bool tile_skipped(const TileKeep& K, uint32_t tx, uint32_t ty) { return tx < K.x0 || tx >= K.x1 || ty < K.y0 || ty >= K.y1; }
+HKD bool tile_skipped(const TileKeep& K) { return tile_skipped(K, blockIdx.x, blockIdx.y); }
 
 // ------------------------------------------------------------------ G-buffer
 // The primary ray through (px, py) (oracle/hk_oracle.c primary_ray, step for step).  ORTHO (view.projection[3].w
@@ -204,6 +209,11 @@ __global__ __launch_bounds__(256) void k_gbuffer(FrameArgs A, ViewArgs V, uint2*
     // workgroups then take less LDS and more of them fit a CU), the first LVL otherwise.  The
     // scene-staged variant (LDS) puts a shallow scene's stack after the staged arrays (small frames:
     // launch_gbuffer) and a deep one in scratch.
+    // the skipped tiles' primary rays (their pixels trace nothing, the reference counts them): once per launch, by
+    // the workgroup of tile (0, 0), skipped or not
+    if (V.skipped_primary && blockIdx.x == 0u && blockIdx.y == 0u && threadIdx.x == 0u)
+        atomicAdd(A.cnt.primary, (unsigned long long)V.skipped_primary);
+    if (tile_skipped(V.keep)) return;
     uint2* gb_lds_stack = reinterpret_cast<uint2*>(hk_lds_scene);
     if constexpr (LDS) gb_lds_stack = SHALLOW ? reinterpret_cast<uint2*>(hk_lds_scene + stage_bytes(A.sc.bytes, PLAN_GBUFFER) / 4u) : nullptr;
     Scene sc;
@@ -771,8 +781,9 @@ HKD void direct_pass(const FrameArgs& A, const Scene& sc, const ChannelArgs& C, 
 // One direct-light pass per launch: the body of k_direct and k_direct_lit_w4.  (The argument blocks by value, as a
 // kernel has them: by reference the unstaged variants compile to other code.)
 template <bool EMISSIVE_LIT, bool RENDER_EMISSIVE, bool LDS, bool VALIDATE>
-HKD void direct_kernel(FrameArgs A, ChannelArgs C)
+HKD void direct_kernel(FrameArgs A, ChannelArgs C, TileKeep K)
 {
+    if (tile_skipped(K)) return;  // before the texel loads, the staging and its barrier (workgroup-uniform)
     int32_t x, y;
     const bool active = tile_pixel<TRACE_ORDER>(A.F, A.F.s[0], A.F.s_row0, A.F.s_rows, x, y);
     PixelTexels tex;
@@ -785,9 +796,9 @@ HKD void direct_kernel(FrameArgs A, ChannelArgs C)
     finish_counts(A, x, y, n_top, n_emitter);
 }
 template <bool EMISSIVE_LIT, bool RENDER_EMISSIVE, bool LDS, bool VALIDATE>
-__global__ __launch_bounds__(256) void k_direct(FrameArgs A, ChannelArgs C)
+__global__ __launch_bounds__(256) void k_direct(FrameArgs A, ChannelArgs C, TileKeep K)
 {
-    direct_kernel<EMISSIVE_LIT, RENDER_EMISSIVE, LDS, VALIDATE>(A, C);
+    direct_kernel<EMISSIVE_LIT, RENDER_EMISSIVE, LDS, VALIDATE>(A, C, K);
 }
 // direct_lit alone (no emissive sampling) fits 128 VGPRs with at most a few scratch words: the
 // same body with 4 waves per SIMD for the separate-launch path (bands / stripes) when the grid
@@ -795,9 +806,10 @@ __global__ __launch_bounds__(256) void k_direct(FrameArgs A, ChannelArgs C)
 // 4-way 0.192 -> 0.187; an 8-way stripe (259 K pixels, about one wave per slot) 0.1455 -> 0.1474
 // (the threshold is LaunchOpts::direct_w4_min_px)
 template <bool LDS, bool VALIDATE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_direct_lit_w4(FrameArgs A, ChannelArgs C)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_direct_lit_w4(FrameArgs A, ChannelArgs C,
+                                                                                                 TileKeep K)
 {
-    direct_kernel<false, true, LDS, VALIDATE>(A, C);
+    direct_kernel<false, true, LDS, VALIDATE>(A, C, K);
 }
 
 // direct_lit then the emissive pass of one pixel (the fused kernels, k_light_merged's direct role): the pair's
@@ -833,8 +845,9 @@ HKD void fix_shared_xform(Scene& sc)
     if constexpr (SX >= 0) sc.shared_xform = (uint32_t)SX;
 }
 template <bool LDS, bool VD, bool VE, int SX = -1>
-HKD void direct_fused_kernel(FrameArgs A, ChannelArgs C0, ChannelArgs C1)
+HKD void direct_fused_kernel(FrameArgs A, ChannelArgs C0, ChannelArgs C1, TileKeep K)
 {
+    if (tile_skipped(K)) return;  // (as direct_kernel)
     int32_t x, y;
     const bool active = tile_pixel<TRACE_ORDER>(A.F, A.F.s[0], A.F.s_row0, A.F.s_rows, x, y);
     PixelTexels tex;
@@ -848,9 +861,9 @@ HKD void direct_fused_kernel(FrameArgs A, ChannelArgs C0, ChannelArgs C1)
     finish_counts(A, x, y, n_top, n_emitter);
 }
 template <bool LDS, bool VD, bool VE>
-__global__ __launch_bounds__(256) void k_direct_fused(FrameArgs A, ChannelArgs C0, ChannelArgs C1)
+__global__ __launch_bounds__(256) void k_direct_fused(FrameArgs A, ChannelArgs C0, ChannelArgs C1, TileKeep K)
 {
-    direct_fused_kernel<LDS, VD, VE>(A, C0, C1);
+    direct_fused_kernel<LDS, VD, VE>(A, C0, C1, K);
 }
 // The fused launch on frames that are not emissive-validation frames, held to 4 waves per SIMD
 // (128 VGPRs): without the emissive validation block the body needs 117-137 VGPRs (the direct
@@ -859,9 +872,9 @@ __global__ __launch_bounds__(256) void k_direct_fused(FrameArgs A, ChannelArgs C
 // validation frames take this 4-wave kernel too (VE).
 template <bool LDS, bool VD, bool VE = false, bool SX = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_direct_fused_w4(FrameArgs A, ChannelArgs C0,
-                                                                                                   ChannelArgs C1)
+                                                                                                   ChannelArgs C1, TileKeep K)
 {
-    direct_fused_kernel<LDS, VD, VE, SX ? 1 : 0>(A, C0, C1);
+    direct_fused_kernel<LDS, VD, VE, SX ? 1 : 0>(A, C0, C1, K);
 }
 
 // Emitter walks of a workgroup as one compacted batch (the CW variant of the fused launch).  In city the
@@ -1512,8 +1525,9 @@ HKD bool indirect_body(const FrameArgs& A, const Scene& sc, const ChannelArgs& C
 // CS: the one-bounce path's shadow walks compacted per workgroup (compact_top_walks; option compact_shadow)
 // SX: fix_shared_xform's constant for the one-bounce kernel (-1: the flag at run time)
 template <bool MULTI, bool LDS, bool CS = false, int SX = -1>
-__global__ __launch_bounds__(256) void k_indirect(FrameArgs A, ChannelArgs C)
+__global__ __launch_bounds__(256) void k_indirect(FrameArgs A, ChannelArgs C, TileKeep K)
 {
+    if (tile_skipped(K)) return;  // (as direct_kernel)
     int32_t x, y;
     const bool active = tile_pixel<TRACE_ORDER>(A.F, A.F.s[0], A.F.s_row0, A.F.s_rows, x, y);
     // The one-bounce variant without LDS staging (scene, city) loads all of its pixel's texels up front: one round
@@ -1620,11 +1634,14 @@ __global__ __launch_bounds__(256) void k_indirect_persist(FrameArgs A, ChannelAr
 // max(park, scene) bytes per workgroup, as each kernel alone needs.
 template <bool VD, bool VE, bool LDS_I>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_light_merged(FrameArgs A, ChannelArgs C0,
-                                                                                                ChannelArgs C1, ChannelArgs C2)
+                                                                                                ChannelArgs C1, ChannelArgs C2,
+                                                                                                TileKeep KD, TileKeep KI)
 {
     // gridDim.z == 2: every direct workgroup (z = 0) is dispatched before the indirect ones
     const bool zsplit = gridDim.z == 2u;
     const uint32_t bx = zsplit ? blockIdx.x : blockIdx.x >> 1, gx = zsplit ? gridDim.x : gridDim.x >> 1;
+    // background tile skip, per role (KD: direct, KI: indirect)
+    if (tile_skipped((zsplit ? blockIdx.z == 1u : (blockIdx.x & 1u) != 0u) ? KI : KD, bx, blockIdx.y)) return;
     int32_t x, y;
     uint32_t n_top = 0, n_emitter = 0;
     const bool active = tile_pixel_at<TRACE_ORDER>(A.F, A.F.s[0], A.F.s_row0, A.F.s_rows, bx, blockIdx.y, gx, gridDim.y, x, y);
@@ -2641,7 +2658,7 @@ void launch_albedo(const FrameArgs& A, uint2* albedo, hipStream_t st)
 }
 // a validation frame of a direct-light pass: frame.number % interval == 0 (umod: interval 0 -> 0)
 static bool validation_frame(uint32_t number, uint32_t interval) { return interval == 0u || number % interval == 0u; }
-void launch_direct(const FrameArgs& A, const ChannelArgs& C, bool emissive_lit, hipStream_t st)
+void launch_direct(const FrameArgs& A, const ChannelArgs& C, bool emissive_lit, hipStream_t st, const TileKeep& keep)
 {
     dim3 g = tiles(A.F, A.F.s[0], A.F.s_rows);
     // staged since round 4 (stage_scene) on frames of >= direct_w4_min_px pixels: cornell 1080p under an orbiting
@@ -2652,15 +2669,15 @@ void launch_direct(const FrameArgs& A, const ChannelArgs& C, bool emissive_lit, 
     const bool val = validation_frame(A.F.number, emissive_lit ? A.F.emissive_validate_interval : A.F.direct_validate_interval);
     dispatch(
         [&](auto LDS, auto VAL) {
-            if (emissive_lit) hipLaunchKernelGGL((k_direct<true, false, LDS, VAL>), g, dim3(256), lds, st, A, C);
-            else if (big) hipLaunchKernelGGL((k_direct_lit_w4<LDS, VAL>), g, dim3(256), lds, st, A, C);
-            else hipLaunchKernelGGL((k_direct<false, true, LDS, VAL>), g, dim3(256), lds, st, A, C);
+            if (emissive_lit) hipLaunchKernelGGL((k_direct<true, false, LDS, VAL>), g, dim3(256), lds, st, A, C, keep);
+            else if (big) hipLaunchKernelGGL((k_direct_lit_w4<LDS, VAL>), g, dim3(256), lds, st, A, C, keep);
+            else hipLaunchKernelGGL((k_direct<false, true, LDS, VAL>), g, dim3(256), lds, st, A, C, keep);
         },
         lds != 0u, val);
 }
 template <bool LDS>
 static void launch_fused_v(const FrameArgs& A, const ChannelArgs& C0, const ChannelArgs& C1, bool vd, bool ve, dim3 g,
-                           uint32_t lds, hipStream_t st)
+                           uint32_t lds, hipStream_t st, const TileKeep& keep)
 {
     const bool w4 = A.opt.fused_w4 != 0;
     // The family: the 4-wave kernel takes an emissive-validation frame only unstaged (its validation blocks parked in
@@ -2671,14 +2688,14 @@ static void launch_fused_v(const FrameArgs& A, const ChannelArgs& C0, const Chan
         dispatch([&](auto VD, auto CS) { hipLaunchKernelGGL((k_direct_fused_cw<VD, CS>), g, dim3(256), lds, st, A, C0, C1); },
                  vd, A.opt.compact_shadow != 0);
     } else if (w4 && (!LDS || !ve)) {
-        dispatch([&](auto VD, auto VE, auto SX) { hipLaunchKernelGGL((k_direct_fused_w4<LDS, VD, VE, SX>), g, dim3(256), lds, st, A, C0, C1); },
+        dispatch([&](auto VD, auto VE, auto SX) { hipLaunchKernelGGL((k_direct_fused_w4<LDS, VD, VE, SX>), g, dim3(256), lds, st, A, C0, C1, keep); },
                  vd, ve, A.sc.shared_xform != 0u);
     } else {
-        dispatch([&](auto VD, auto VE) { hipLaunchKernelGGL((k_direct_fused<LDS, VD, VE>), g, dim3(256), lds, st, A, C0, C1); },
+        dispatch([&](auto VD, auto VE) { hipLaunchKernelGGL((k_direct_fused<LDS, VD, VE>), g, dim3(256), lds, st, A, C0, C1, keep); },
                  vd, ve);
     }
 }
-void launch_direct_fused(const FrameArgs& A, const ChannelArgs& C0, const ChannelArgs& C1, hipStream_t st)
+void launch_direct_fused(const FrameArgs& A, const ChannelArgs& C0, const ChannelArgs& C1, hipStream_t st, const TileKeep& keep)
 {
     dim3 g = tiles(A.F, A.F.s[0], A.F.s_rows);
     // staged by default since the staging copies chunks with their loads in flight (stage_scene): cornell 1080p
@@ -2686,8 +2703,8 @@ void launch_direct_fused(const FrameArgs& A, const ChannelArgs& C0, const Channe
     const uint32_t lds = lds_plan_bytes(A, PLAN_LIGHT, true);
     const bool vd = validation_frame(A.F.number, A.F.direct_validate_interval);
     const bool ve = validation_frame(A.F.number, A.F.emissive_validate_interval);
-    if (lds) launch_fused_v<true>(A, C0, C1, vd, ve, g, lds, st);
-    else launch_fused_v<false>(A, C0, C1, vd, ve, g, 0, st);
+    if (lds) launch_fused_v<true>(A, C0, C1, vd, ve, g, lds, st, keep);
+    else launch_fused_v<false>(A, C0, C1, vd, ve, g, 0, st, keep);
 }
 // workgroups of a persistent launch: what the device holds resident of this kernel, at most one 8x8 tile per wave
 static uint32_t persist_grid(const void* kernel, uint32_t lds, const Frame& F)
@@ -2726,7 +2743,7 @@ static uint32_t persist_grid(const void* kernel, uint32_t lds, const Frame& F)
     const uint32_t need = (tiles8 + 3u) / 4u;
     return need < g ? (need > 0u ? need : 1u) : g;
 }
-void launch_indirect(const FrameArgs& A, const ChannelArgs& C, bool multi, hipStream_t st)
+void launch_indirect(const FrameArgs& A, const ChannelArgs& C, bool multi, hipStream_t st, const TileKeep& keep)
 {
     dim3 g = tiles(A.F, A.F.s[0], A.F.s_rows);
     const uint32_t lds = lds_plan_bytes(A, PLAN_LIGHT, true);
@@ -2742,9 +2759,9 @@ void launch_indirect(const FrameArgs& A, const ChannelArgs& C, bool multi, hipSt
     // (only the staging flag goes through dispatch: there is no compacted multi-bounce kernel)
     dispatch(
         [&](auto L, auto SX) {
-            if (multi) hipLaunchKernelGGL((k_indirect<true, L>), g, dim3(256), lds, st, A, C);
-            else if (A.opt.compact_shadow) hipLaunchKernelGGL((k_indirect<false, L, true>), g, dim3(256), lds, st, A, C);
-            else hipLaunchKernelGGL((k_indirect<false, L, false, SX ? 1 : 0>), g, dim3(256), lds, st, A, C);
+            if (multi) hipLaunchKernelGGL((k_indirect<true, L>), g, dim3(256), lds, st, A, C, keep);
+            else if (A.opt.compact_shadow) hipLaunchKernelGGL((k_indirect<false, L, true>), g, dim3(256), lds, st, A, C, keep);
+            else hipLaunchKernelGGL((k_indirect<false, L, false, SX ? 1 : 0>), g, dim3(256), lds, st, A, C, keep);
         },
         lds != 0u, A.sc.shared_xform != 0u);
 }
@@ -2753,7 +2770,7 @@ uint32_t indirect_stash_bytes() { return (uint32_t)sizeof(IndStash); }
 static_assert(LDS_SCENE_MAX + sizeof(IndStash) <= LDS_WORKGROUP_MAX, "staged scene + stash exceed a workgroup's LDS");
 bool light_lds_direct(const FrameArgs& A) { return lds_plan_bytes(A, PLAN_LIGHT, false) != 0u; }
 void launch_light_merged(const FrameArgs& A, const ChannelArgs& C0, const ChannelArgs& C1, const ChannelArgs& C2,
-                         hipStream_t st)
+                         hipStream_t st, const TileKeep& keep_direct, const TileKeep& keep_indirect)
 {
     dim3 g = tiles(A.F, A.F.s[0], A.F.s_rows);
     // the direct workgroups are dispatched first (grid z 0, then the indirect ones at z 1): cornell 4-way stripe
@@ -2766,7 +2783,8 @@ void launch_light_merged(const FrameArgs& A, const ChannelArgs& C0, const Channe
     const uint32_t park = (vd || ve) ? (uint32_t)(PARK_WORDS * 256 * sizeof(float)) : 0u;
     const uint32_t ind = scene + (uint32_t)sizeof(IndStash);  // the indirect role: staged scene + stash
     const uint32_t lds = ind > park ? ind : park;
-    dispatch([&](auto VD, auto VE, auto S) { hipLaunchKernelGGL((k_light_merged<VD, VE, S>), g, dim3(256), lds, st, A, C0, C1, C2); },
+    dispatch([&](auto VD, auto VE, auto S) { hipLaunchKernelGGL((k_light_merged<VD, VE, S>), g, dim3(256), lds, st, A, C0, C1, C2, keep_direct,
+                                                                keep_indirect); },
              vd, ve, scene != 0u);
 }
 void launch_indirect_wavefront(const FrameArgs& A, const ChannelArgs& C, const WfArgs& W, hipStream_t st)

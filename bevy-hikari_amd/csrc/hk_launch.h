@@ -38,6 +38,15 @@ struct FrameArgs {
 inline uint32_t launch_cols(const Frame& F, uint32_t width) { return F.win_cols > 0 ? (uint32_t)F.win_cols : width; }
 inline int32_t launch_rows(const Frame& F, int32_t rows) { return F.win_rows > 0 ? F.win_rows : rows; }
 
+// Background tile skip (option bg_tile_skip): the tiles of a launch's own grid, [x0, x1) x [y0, y1), that can hold a
+// covered pixel or a background pixel whose constants are still due.  A workgroup outside them would store nothing
+// (every pixel background, every target already holding its constants: the runtime's tile_keep derives that from the
+// scene's screen bound and the elision masks' history) and returns at its first instruction.  TILE_KEEP_ALL: no skip.
+struct TileKeep {
+    uint32_t x0, y0, x1, y1;
+};
+constexpr TileKeep TILE_KEEP_ALL{0u, 0u, 0xFFFFFFFFu, 0xFFFFFFFFu};
+
 // One channel's bindings: group 5 (variance/render) + group 6 (reservoir pair) of light.rs:455-555.
 struct ChannelArgs {
     ResBuf prev;          // previous_reservoir_buffer  (read)
@@ -97,6 +106,10 @@ struct ViewArgs {
     // zero texels in every plane (position, normal, gradient, ids, velocity/uv, albedo); nullptr = off
     uint8_t* bg;
     uint32_t bg_need;
+    // background tile skip: the tiles to run, and the primary rays of the skipped tiles' counted pixels, which the
+    // workgroup of tile (0, 0) adds to the counter once
+    TileKeep keep;
+    uint32_t skipped_primary;
 };
 
 // All channels of one frame (post_process.rs:1199-1223 runs them one after another).
@@ -235,10 +248,13 @@ void launch_overlay(const OverlayArgs& A, bool run, hipStream_t st);
 
 bool lane_stats_take(unsigned long long out[2 * LANE_SLOTS], hipStream_t st);
 void launch_gbuffer(const FrameArgs& A, const ViewArgs& V, uint2* albedo, uint32_t stack_need, hipStream_t st);
-void launch_direct_fused(const FrameArgs& A, const ChannelArgs& C0, const ChannelArgs& C1, hipStream_t st);
+// keep (the light launches): the background tile skip's tiles, TILE_KEEP_ALL for none
+void launch_direct_fused(const FrameArgs& A, const ChannelArgs& C0, const ChannelArgs& C1, hipStream_t st,
+                         const TileKeep& keep = TILE_KEEP_ALL);
 void launch_albedo(const FrameArgs& A, uint2* albedo, hipStream_t st);
-void launch_direct(const FrameArgs& A, const ChannelArgs& C, bool emissive_lit, hipStream_t st);
-void launch_indirect(const FrameArgs& A, const ChannelArgs& C, bool multi, hipStream_t st);
+void launch_direct(const FrameArgs& A, const ChannelArgs& C, bool emissive_lit, hipStream_t st,
+                   const TileKeep& keep = TILE_KEEP_ALL);
+void launch_indirect(const FrameArgs& A, const ChannelArgs& C, bool multi, hipStream_t st, const TileKeep& keep = TILE_KEEP_ALL);
 // the indirect pass's pixel stash per workgroup (IndStash: static in k_indirect, behind the scene in k_light_merged)
 uint32_t indirect_stash_bytes();
 // the wavefront indirect pass (one bounce): gen + compaction, bounce trace, bin scan, scatter by
@@ -248,8 +264,10 @@ void launch_spatial(const FrameArgs& A, const ChannelArgs& C, bool emissive_lit,
 // the direct-light passes stage the scene in LDS (option lds_scene = 2 with a small enough scene)
 bool light_lds_direct(const FrameArgs& A);
 // direct_lit + emissive (fused per pixel) and the one-bounce indirect pass in one launch (k_light_merged)
+// (keep_direct / keep_indirect: per role)
 void launch_light_merged(const FrameArgs& A, const ChannelArgs& C0, const ChannelArgs& C1, const ChannelArgs& C2,
-                         hipStream_t st);
+                         hipStream_t st, const TileKeep& keep_direct = TILE_KEEP_ALL,
+                         const TileKeep& keep_indirect = TILE_KEEP_ALL);
 void launch_demod(const FrameArgs& A, const DenoiseArgs& D, hipStream_t st);
 void launch_denoise(const FrameArgs& A, const DenoiseArgs& D, int level, hipStream_t st);
 void launch_tone(const FrameArgs& A, const ToneArgs& T, hipStream_t st);

@@ -67,6 +67,7 @@ enum Opt {
     OPT_FSR_TILED,           // EASU with its input footprint staged in LDS (hk_fsr.hip)
     OPT_PRESENT_RUN,         // hk_present stores 16-byte row runs where the viewport's runs are aligned (hk_overlay.hip)
     OPT_SHARED_XFORM,        // one local ray per walk where every instance carries the same transform (Scene::shared_xform)
+    OPT_BG_TILE_SKIP,        // workgroups outside the scene's screen bound return at once (TileKeep)
     OPT_COUNT
 };
 struct OptDef {
@@ -83,7 +84,7 @@ constexpr OptDef OPTS[OPT_COUNT] = {
     {"gbuffer_lds_max_px", 6e5, 0.0, 1e12},
     {"direct_w4_min_px", 4e5, 0.0, 1e12},  {"fused_w4", 1, 0, 1},          {"persistent_indirect", 0, 0, 1},
     {"compact_emitter", 0, 0, 1},          {"compact_shadow", 0, 0, 1},    {"fsr_tiled", 1, 0, 1},
-    {"present_run", 1, 0, 1},              {"shared_xform", 1, 0, 1},
+    {"present_run", 1, 0, 1},              {"shared_xform", 1, 0, 1},      {"bg_tile_skip", 1, 0, 1},
 };
 
 // One slot of the planes k_gbuffer double-buffers (hk_ctx::g / g_prev: swapped on each hk_render_gbuffer) so a
@@ -282,6 +283,63 @@ struct FrameSchedule : ScheduleState {
     // k_gbuffer waited for that tail or a later one (dn_stream is in order)
     bool slot_covered() const { return gb_fresh() && rslot_seq[rslot] <= gb_tail_seq; }
 };
+
+// Background tile skip (option bg_tile_skip).
+// The guard band of the scene's screen bound (hks_screen_bounds), in pixels: the bound is exact in double and already
+// holds the prepass jitter (< 1 px); what is left is the f32 rounding of a primary ray's direction and of the walk's
+// box tests, some 1e-6 of the frame's width, so 4 px is three orders of magnitude above it.
+constexpr uint32_t TILE_SKIP_GUARD = 4;
+// A pixel rectangle [x0, x1) x [y0, y1) in frame coordinates.
+struct PxRect {
+    int32_t x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+    bool empty() const { return x1 <= x0 || y1 <= y0; }
+    static PxRect all() { return PxRect{0, 0, INT32_MAX, INT32_MAX}; }
+    PxRect join(const PxRect& o) const
+    {
+        if (empty()) return o;
+        if (o.empty()) return *this;
+        return PxRect{std::min(x0, o.x0), std::min(y0, o.y0), std::max(x1, o.x1), std::max(y1, o.y1)};
+    }
+};
+// What the host knows of an elision mask's bytes (gbmask, bgmask[k]) without reading them.  The kernels' rule
+// (k_gbuffer, bg_elide): a covered pixel zeroes its byte; a background pixel sets the bits its launch asks for and
+// keeps the others, but for the pair bit (4), which a launch that does not ask for it clears.  So bit b is set in
+// every byte outside cover[b], the bounding rectangle of the screen bounds of every masked launch since (and
+// including) the last one that asked for b: that launch set it there, or skipped a tile because it was set already,
+// and every pixel there has been background since.  known[b] is false until such a launch ran on the mask as it is
+// (reset: the mask was zero-filled or dropped).
+struct MaskHistory {
+    static constexpr int BITS = 5;
+    PxRect cover[BITS];
+    bool known[BITS] = {};
+    void reset()
+    {
+        for (bool& k : known) k = false;
+    }
+    // A masked launch asking for the bits `need`, all of whose pixels outside `now` are background.  true: outside
+    // `keep` every byte already has all of `need`, so a workgroup there stores nothing and writes no byte.
+    bool launch(uint32_t need, const PxRect& now, PxRect& keep)
+    {
+        bool ok = true;
+        keep = now;
+        for (int b = 0; b < BITS; ++b) {
+            if (!(need >> b & 1u)) continue;
+            if (!known[b]) ok = false;
+            else keep = keep.join(cover[b]);
+        }
+        for (int b = 0; b < BITS; ++b) {
+            if (need >> b & 1u) {
+                cover[b] = now;
+                known[b] = true;
+            } else if (b == 4) {
+                known[b] = false;
+            } else if (known[b]) {
+                cover[b] = cover[b].join(now);
+            }
+        }
+        return ok;
+    }
+};
 }  // namespace
 
 struct hk_ctx {
@@ -371,6 +429,15 @@ struct hk_ctx {
     uint4* sp_view = nullptr;   // spatial view planes of the indirect channel (ChannelArgs::view), 3 x res_n
     bool gb_valid = false;
     int32_t gb_key[2] = {};
+    // Background tile skip: the world box of every instance while the host knows it (hk_scene_upload from the
+    // records, the instance updates from their models and local boxes; not after hk_update_meshes), the screen
+    // bound of the k_gbuffer that wrote each G-buffer slot (the whole plane: none), the masks' histories (gbmask,
+    // bgmask[0..1]) and the workgroups the last frame's launches skipped (k_gbuffer, direct / emissive, indirect)
+    double scene_box[6] = {};
+    bool scene_box_valid = false;
+    PxRect grect[2] = {PxRect::all(), PxRect::all()};
+    MaskHistory gb_hist, bg_hist[2];
+    uint32_t tiles_skipped[3] = {};
     // denoise
     uint4* dn_rgb[4] = {};        // a-trous level inputs, the 3 channels packed (DenoiseArgs::rgb / bi)
     uint2* dn_bi[4] = {};
@@ -566,6 +633,8 @@ void free_targets(hk_ctx* c)
 {
     for (const Target& t : targets(c)) release(*t.ptr);
     c->bg_valid[0] = c->bg_valid[1] = c->gb_valid = false;
+    c->grect[0] = c->grect[1] = PxRect::all();
+    c->tiles_skipped[0] = c->tiles_skipped[1] = c->tiles_skipped[2] = 0;
     c->upscale_wh[0] = c->upscale_wh[1] = c->taa_wh[0] = c->taa_wh[1] = 0;
     c->present_wh[0] = c->present_wh[1] = 0;
     c->accum_n = 0;
@@ -946,6 +1015,42 @@ uint64_t gbuffer_primary_rays(const FrameArgs& A)
     return hi > lo && x1 > x0 ? (uint64_t)(x1 - x0) * (uint64_t)(hi - lo) : 0u;
 }
 
+// Background tile skip: the tiles of launch A's grid (over a plane `width` wide whose local row 0 is frame row
+// `row0`) that meet the pixel rectangle `keep`, grown outward to the grid's own 16x16 tiles; *skipped: the
+// workgroups outside them.  TILE_KEEP_ALL when none is.  Interleaved stripes keep every tile (their rows are not
+// contiguous in the frame).
+TileKeep tile_keep(const FrameArgs& A, uint32_t width, int32_t row0, int32_t rows, const PxRect& keep, uint32_t* skipped)
+{
+    const Frame& F = A.F;
+    *skipped = 0;
+    if (F.stripe_n >= 2) return TILE_KEEP_ALL;
+    const int64_t ox = F.win_cols > 0 ? F.win_col0 : 0, oy = (int64_t)row0 + (F.win_rows > 0 ? F.win_row0 : 0);
+    const int64_t gx = (launch_cols(F, width) + 15u) / 16u, gy = ((uint32_t)launch_rows(F, rows) + 15u) / 16u;
+    auto lo = [](int64_t p, int64_t o, int64_t g) { return std::clamp<int64_t>(p - o, 0, 16 * g) / 16; };
+    auto hi = [](int64_t p, int64_t o, int64_t g) { return (std::clamp<int64_t>(p - o, 0, 16 * g) + 15) / 16; };
+    TileKeep K{(uint32_t)lo(keep.x0, ox, gx), (uint32_t)lo(keep.y0, oy, gy), (uint32_t)hi(keep.x1, ox, gx),
+               (uint32_t)hi(keep.y1, oy, gy)};
+    if (keep.empty() || K.x1 <= K.x0 || K.y1 <= K.y0) K = TileKeep{0u, 0u, 0u, 0u};
+    *skipped = (uint32_t)(gx * gy) - (K.x1 - K.x0) * (K.y1 - K.y0);
+    return *skipped ? K : TILE_KEEP_ALL;
+}
+// the primary rays k_gbuffer would count on the tiles outside K (gbuffer_primary_rays less the kept tiles' share)
+uint64_t gbuffer_skipped_rays(const FrameArgs& A, const TileKeep& K)
+{
+    const Frame& F = A.F;
+    const uint64_t all = gbuffer_primary_rays(A);
+    if (K.x1 <= K.x0 || K.y1 <= K.y0) return all;
+    const int32_t w0 = F.win_rows > 0 ? F.win_row0 : 0, w1 = w0 + launch_rows(F, F.S_rows);
+    const int32_t c0 = F.win_cols > 0 ? F.win_col0 : 0, c1 = c0 + (int32_t)launch_cols(F, F.S[0]);
+    // the kept tiles' active pixels, in frame coordinates, within the counted region
+    const int32_t ky0 = std::min<int64_t>(w0 + 16 * (int64_t)K.y0, w1), ky1 = std::min<int64_t>(w0 + 16 * (int64_t)K.y1, w1);
+    const int32_t kx0 = std::min<int64_t>(c0 + 16 * (int64_t)K.x0, c1), kx1 = std::min<int64_t>(c0 + 16 * (int64_t)K.x1, c1);
+    const int32_t lo = std::max(F.S_row0 + ky0, F.count_Sy0), hi = std::min(F.S_row0 + ky1, F.count_Sy1);
+    const int32_t x0 = std::max(kx0, F.count_x0), x1 = std::min(kx1, F.count_x1);
+    const uint64_t kept = hi > lo && x1 > x0 ? (uint64_t)(x1 - x0) * (uint64_t)(hi - lo) : 0u;
+    return all - kept;
+}
+
 int check_ready(hk_ctx* c, bool need_scene)
 {
     if (!c) return HK_ERR_INVALID;
@@ -1191,6 +1296,7 @@ int hk_scene_upload(hk_ctx* c, const hk_scene_desc* d)
         return fail(c, HK_ERR_INVALID, "scene needs at least one instance and one material");
     c->gen++;
     c->shared_transform = false;
+    c->scene_box_valid = false;
     for (int i = 0; i < 9; ++i)
         if (arr[i]->count && !arr[i]->data) return fail(c, HK_ERR_INVALID, "scene array with count but no data");
     HK_HIP(c, hipStreamSynchronize(c->stream));
@@ -1286,6 +1392,20 @@ int hk_scene_upload(hk_ctx* c, const hk_scene_desc* d)
         std::vector<float> itm(16 * (size_t)d->instances.count);
         for (uint32_t k = 0; k < d->instances.count; ++k) std::memcpy(&itm[16 * (size_t)k], inst[k].inverse_transpose_model, 64);
         c->shared_transform = hks_shared_transform(itm.data(), d->instances.count) != 0;
+    }
+    {   // the world box of the instances (background tile skip): their records' boxes, which the TLAS leaves carry
+        double* b = c->scene_box;
+        for (int a = 0; a < 3; ++a) {
+            b[a] = INFINITY;
+            b[3 + a] = -INFINITY;
+        }
+        c->scene_box_valid = true;
+        for (uint32_t k = 0; k < d->instances.count; ++k)
+            for (int a = 0; a < 3; ++a) {
+                c->scene_box_valid &= std::isfinite(inst[k].min[a]) && std::isfinite(inst[k].max[a]);
+                b[a] = std::fmin(b[a], (double)inst[k].min[a]);
+                b[3 + a] = std::fmax(b[3 + a], (double)inst[k].max[a]);
+            }
     }
     c->has_scene = true;
     return HK_OK;
@@ -1500,6 +1620,7 @@ static int rebuild_instances(hk_ctx* c, const float* models, const float* local_
     HK_TRY(c->sch.gb_serialize(false));
     c->gen++;
     c->shared_transform = false;  // (the general walks, should this call fail half-way)
+    c->scene_box_valid = false;   // (likewise: no tile skip)
     struct Moved {  // the previous models of the set before, where reserve_set moved them: freed on every way out
         float* p = nullptr;
         ~Moved() { release(p); }
@@ -1631,6 +1752,10 @@ static int rebuild_instances(hk_ctx* c, const float* models, const float* local_
     // one kernel derives every record's inverse_transpose_model from its model with the same code: equal model bits
     // give equal record bits
     c->shared_transform = hks_shared_transform(models, n) != 0;
+    // the instances' world box from what the device derived their boxes from; after a mesh rebuild the local boxes
+    // are the caller's word about vertices the host has not looked at, so the box stays unknown (no tile skip) until
+    // the next instance update or upload
+    c->scene_box_valid = !ml && hks_instance_bounds(models, local_aabbs, n, c->scene_box) != 0;
     return HK_OK;
 }
 
@@ -1802,6 +1927,24 @@ int hk_scene_shared_transform(const hk_ctx* c, int32_t* shared)
     if (!c || !shared) return HK_ERR_INVALID;
     if (!c->has_scene) return HK_ERR_STATE;
     *shared = c->shared_transform ? 1 : 0;
+    return HK_OK;
+}
+
+int hk_tile_skip_info(const hk_ctx* c, uint32_t skipped[3], int32_t bound[4], int32_t* bounded)
+{
+    if (!c) return HK_ERR_INVALID;
+    if (!c->sized) return HK_ERR_STATE;
+    if (skipped)
+        for (int k = 0; k < 3; ++k) skipped[k] = c->tiles_skipped[k];
+    const PxRect& r = c->grect[c->sch.gslot];
+    const bool none = r.x1 == INT32_MAX;
+    if (bound) {
+        bound[0] = none ? 0 : r.x0;
+        bound[1] = none ? 0 : r.y0;
+        bound[2] = none ? (int32_t)c->S[0] : r.x1;
+        bound[3] = none ? (int32_t)c->S[1] : r.y1;
+    }
+    if (bounded) *bounded = none ? 0 : 1;
     return HK_OK;
 }
 
@@ -2101,6 +2244,7 @@ int hk_render_gbuffer(hk_ctx* c, const hk_frame_inputs* in, void* stream)
             q.gb_on_gs = false;
             q.gb_calls++;
             c->primary_reused += gbuffer_primary_rays(W);
+            c->tiles_skipped[0] = 0;  // (no launch)
             return HK_OK;
         }
     }
@@ -2156,17 +2300,35 @@ int hk_render_gbuffer(hk_ctx* c, const hk_frame_inputs* in, void* stream)
     A = pass_window(c, A, GBUFFER_REACH);
     V.bg = nullptr;
     V.bg_need = 0;
+    // background tile skip: this frame's screen bound of the scene, kept with the slot for the light passes
+    V.keep = TILE_KEEP_ALL;
+    V.skipped_primary = 0;
+    c->tiles_skipped[0] = 0;
+    PxRect now = PxRect::all();
+    int32_t bound[4];
+    if (c->scene_box_valid && hks_screen_bounds(c->scene_box, &in->view, c->S[0], c->S[1], TILE_SKIP_GUARD, bound))
+        now = PxRect{bound[0], bound[1], bound[2], bound[3]};
+    c->grect[q.gslot] = now;
     if (bg_elision_off(c)) {
         c->gb_valid = false;  // the mask is rebuilt from zero when elision is switched back on
+        c->gb_hist.reset();
     } else {
         if (!c->gb_valid || c->gb_key[0] != A.F.win_row0 || c->gb_key[1] != A.F.win_rows) {
             HK_HIP(c, hipMemsetAsync(c->gbmask, 0, (size_t)c->S[0] * c->S_rows, gs));
             c->gb_valid = true;
             c->gb_key[0] = A.F.win_row0;
             c->gb_key[1] = A.F.win_rows;
+            c->gb_hist.reset();
         }
         V.bg = c->gbmask;
         V.bg_need = 1u << q.gslot;  // the planes' physical slot (swapped with gslot above)
+        // a tile outside the bounds of every launch since this slot's last one holds the slot's bit in every byte
+        // (MaskHistory): its workgroup would trace 256 misses and store nothing
+        PxRect keep;
+        if (c->gb_hist.launch(V.bg_need, now, keep) && c->on(OPT_BG_TILE_SKIP)) {
+            V.keep = tile_keep(A, c->S[0], c->S_row0, c->S_rows, keep, &c->tiles_skipped[0]);
+            if (c->tiles_skipped[0]) V.skipped_primary = (uint32_t)gbuffer_skipped_rays(A, V.keep);
+        }
     }
     for (const void* plane : std::initializer_list<const void*>{c->g.position, c->g.velocity_uv, c->g.normal, c->g.depth_gradient,
                                                                 c->g.instance_material, c->g.albedo})
@@ -2213,6 +2375,8 @@ int hk_set_gbuffer_plane(hk_ctx* c, int plane, const void* data, size_t bytes, i
     if (bytes != need) return fail(c, HK_ERR_INVALID, "G-buffer plane size mismatch");
     c->gen++;
     c->gb_valid = false;  // host planes: the G-buffer elision mask no longer describes the slots
+    c->grect[0] = c->grect[1] = PxRect::all();  // ... nor does a screen bound
+    c->tiles_skipped[0] = 0;
     // host planes may carry any velocity: the identity-reprojection paths (fused launch, band row windows,
     // the direct pair's elision) stay off until the next k_gbuffer of a static frame
     c->velocity_zero = false;
@@ -2256,12 +2420,19 @@ static ChannelArgs channel(hk_ctx* c, uint32_t number, int ch)
 // The background elision mask k (0: direct/emissive pair, 1: indirect) for a launch over window A
 // of this frame, or nullptr when the launch does not use it (use = false: another kernel writes the
 // channel's targets this frame, so the mask is dropped and rebuilt from zero the next time).
-static int bg_mask(hk_ctx* c, int k, const FrameArgs& A, bool use, bool pair, hipStream_t st, ChannelArgs& C)
+// K: the launch's tiles under the background tile skip.  A tile is left out when the G-buffer the pass reads (use:
+// k_gbuffer's, at ratio 1; its screen bound is grect) is background on all of it and every byte there holds all of
+// bg_need (MaskHistory) — with the pair among them: without it a background pixel still stores the pair (BG_SKIP_OWN:
+// the direct pair under motion, a channel whose spatial reuse rewrites it).
+static int bg_mask(hk_ctx* c, int k, const FrameArgs& A, bool use, bool pair, hipStream_t st, ChannelArgs& C, TileKeep& K)
 {
     C.bg = nullptr;
     C.bg_need = 0;
+    K = TILE_KEEP_ALL;
+    c->tiles_skipped[1 + k] = 0;
     if (!use || bg_elision_off(c)) {
         c->bg_valid[k] = false;
+        c->bg_hist[k].reset();
         return HK_OK;
     }
     if (!c->bg_valid[k] || c->bg_key[k][0] != A.F.win_row0 || c->bg_key[k][1] != A.F.win_rows) {
@@ -2269,11 +2440,15 @@ static int bg_mask(hk_ctx* c, int k, const FrameArgs& A, bool use, bool pair, hi
         c->bg_valid[k] = true;
         c->bg_key[k][0] = A.F.win_row0;
         c->bg_key[k][1] = A.F.win_rows;
+        c->bg_hist[k].reset();
     }
     C.bg = c->bgmask[k];
     // targets of this frame: reservoir parity (the temporal buffer), render / variance slot, and
     // (pair: no spatial reuse pass rewrites it) the spatial pair, both of whose buffers are stored
     C.bg_need = (1u << (A.F.number & 1u)) | (4u << c->sch.rslot) | (pair ? 16u : 0u);
+    PxRect keep;
+    if (c->bg_hist[k].launch(C.bg_need, c->grect[c->sch.gslot], keep) && pair && c->on(OPT_BG_TILE_SKIP))
+        K = tile_keep(A, c->s[0], c->s_row0, c->s_rows, keep, &c->tiles_skipped[1 + k]);
     return HK_OK;
 }
 
@@ -2418,27 +2593,39 @@ int hk_render_frame(hk_ctx* c, const hk_settings* settings, const hk_frame_input
         }
         fork_events = true;
     }
-    HK_TRY(bg_mask(c, 0, AE, elide, identity && !settings->emissive_spatial_reuse, st, C0));
+    // background tile skip (bg_mask): the tiles each channel group runs; the opt-in variants that take no TileKeep
+    // (compacted, persistent, wavefront) run every tile
+    TileKeep KD, KI;
+    const bool no_keep = A.opt.compact_emitter || A.opt.compact_shadow || A.opt.persistent_indirect || wf;
+    auto keep_all = [&](TileKeep& K, int k) {
+        if (!no_keep) return;
+        K = TILE_KEEP_ALL;
+        c->tiles_skipped[1 + k] = 0;
+    };
+    HK_TRY(bg_mask(c, 0, AE, elide, identity && !settings->emissive_spatial_reuse, st, C0, KD));
+    keep_all(KD, 0);
     C1.bg = C0.bg;
     C1.bg_need = C0.bg_need;
     if (merge) {
         // (the elision mask of the indirect channel is prepared on the launch stream)
-        HK_TRY(bg_mask(c, 1, A, elide, !settings->indirect_spatial_reuse, st, C2));
-        timed(c, "light_merged", st, [&] { launch_light_merged(A, C0, C1, C2, st); });
+        HK_TRY(bg_mask(c, 1, A, elide, !settings->indirect_spatial_reuse, st, C2, KI));
+        keep_all(KI, 1);
+        timed(c, "light_merged", st, [&] { launch_light_merged(A, C0, C1, C2, st, KD, KI); });
         if (settings->emissive_spatial_reuse)
             timed(c, "emissive_spatial_reuse", st, [&] { launch_spatial(AS, C1, true, st); });
         if (settings->indirect_spatial_reuse)
             timed(c, "indirect_spatial_reuse", st, [&] { launch_spatial(AS, C2, false, st); });
     } else {
         if (fuse) {
-            timed(c, "direct_lit_emissive", st, [&] { launch_direct_fused(AE, C0, C1, st); });
+            timed(c, "direct_lit_emissive", st, [&] { launch_direct_fused(AE, C0, C1, st, KD); });
         } else {
-            timed(c, "direct_lit", st, [&] { launch_direct(AE, C0, false, st); });
-            timed(c, "direct_emissive", s1, [&] { launch_direct(AE, C1, true, s1); });
+            timed(c, "direct_lit", st, [&] { launch_direct(AE, C0, false, st, KD); });
+            timed(c, "direct_emissive", s1, [&] { launch_direct(AE, C1, true, s1, KD); });
         }
         if (settings->emissive_spatial_reuse) timed(c, "emissive_spatial_reuse", s1, [&] { launch_spatial(AS, C1, true, s1); });
         // (the wavefront pass elides in its generation stage, which classifies every pixel)
-        HK_TRY(bg_mask(c, 1, A, elide, !settings->indirect_spatial_reuse, s2, C2));
+        HK_TRY(bg_mask(c, 1, A, elide, !settings->indirect_spatial_reuse, s2, C2, KI));
+        keep_all(KI, 1);
         if (wf) {
             HK_TRY(ensure_wavefront(c));
             WfArgs W{c->wf_queue1, c->wf_keys, c->wf_queue2, c->wf_hit, c->wf_hit_t, c->wf_ctl, c->count[6] + 1u,
@@ -2446,7 +2633,7 @@ int hk_render_frame(hk_ctx* c, const hk_settings* settings, const hk_frame_input
             HK_HIP(c, hipMemsetAsync(W.ctl, 0, (size_t)wf_ctl_words(W.bins) * 4, s2));
             timed(c, "indirect_wavefront", s2, [&] { launch_indirect_wavefront(A, C2, W, s2); });
         } else {
-            timed(c, multi ? "indirect_multiple_bounces" : "indirect_lit_ambient", s2, [&] { launch_indirect(A, C2, multi, s2); });
+            timed(c, multi ? "indirect_multiple_bounces" : "indirect_lit_ambient", s2, [&] { launch_indirect(A, C2, multi, s2, KI); });
         }
         if (settings->indirect_spatial_reuse) timed(c, "indirect_spatial_reuse", s2, [&] { launch_spatial(AS, C2, false, s2); });
     }

@@ -547,4 +547,86 @@ int hks_shared_transform(const float* matrices, uint32_t n)
     return 1;
 }
 
+// The world box of n instances from their models and local boxes (Bevy Aabb: centre, half extents), 8 corners each
+// in double, grown outward by a relative 1e-5: it holds the f32 boxes the device derives from the same inputs.
+int hks_instance_bounds(const float* models, const float* local_aabbs, uint32_t n, double aabb[6])
+{
+    if (!models || !local_aabbs || !aabb || n == 0) return 0;
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (uint32_t k = 0; k < n; ++k) {
+        const float* m = models + 16 * (size_t)k;
+        const float* b = local_aabbs + 6 * (size_t)k;
+        for (int corner = 0; corner < 8; ++corner) {
+            double p[3];
+            for (int a = 0; a < 3; ++a) p[a] = (double)b[a] + ((corner >> a & 1) ? (double)b[3 + a] : -(double)b[3 + a]);
+            for (int a = 0; a < 3; ++a) {
+                const double w = (double)m[a] * p[0] + (double)m[4 + a] * p[1] + (double)m[8 + a] * p[2] + (double)m[12 + a];
+                if (!std::isfinite(w)) return 0;
+                lo[a] = std::fmin(lo[a], w);
+                hi[a] = std::fmax(hi[a], w);
+            }
+        }
+    }
+    for (int a = 0; a < 3; ++a) {
+        const double grow = 1e-5 * std::fmax(std::fmax(std::fabs(lo[a]), std::fabs(hi[a])), hi[a] - lo[a]);
+        aabb[a] = lo[a] - grow;
+        aabb[3 + a] = hi[a] + grow;
+    }
+    return 1;
+}
+
+// The 8 corners through view_proj in double.  A perspective view projects every point of the box into the corners'
+// pixel box only while the whole box is in front of the eye: a corner with clip w at or below the near distance
+// (projection[3].z of Bevy's infinite reverse-z perspective) gives no rectangle, and so does a world_position that is
+// not the projection's centre (the primary rays start there).  An orthographic view (projection[3].w == 1) maps the box
+// affinely; a corner behind the near plane (reverse z: ndc z >= 1) gives no rectangle either.
+int hks_screen_bounds(const double aabb[6], const hk_view* view, uint32_t width, uint32_t height, uint32_t guard,
+                      int32_t rect[4])
+{
+    if (!aabb || !view || !rect || width == 0 || height == 0) return 0;
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(aabb[a]) || !std::isfinite(aabb[3 + a]) || aabb[a] > aabb[3 + a]) return 0;
+    const float* m = view->view_proj;
+    const bool ortho = view->projection[15] == 1.0f;
+    auto clip = [m](const double* p, double* c) {
+        for (int r = 0; r < 4; ++r) c[r] = (double)m[r] * p[0] + (double)m[4 + r] * p[1] + (double)m[8 + r] * p[2] + (double)m[12 + r];
+    };
+    double near_w = 0.0;
+    if (!ortho) {
+        const double eye[3] = {view->world_position[0], view->world_position[1], view->world_position[2]};
+        double c[4];
+        clip(eye, c);
+        // the centre of projection has clip x = y = w = 0 (each against the size of its row's terms)
+        for (int r : {0, 1, 3}) {
+            const double scale = std::fabs((double)m[r]) * std::fabs(eye[0]) + std::fabs((double)m[4 + r]) * std::fabs(eye[1]) +
+                                 std::fabs((double)m[8 + r]) * std::fabs(eye[2]) + std::fabs((double)m[12 + r]);
+            if (!(std::fabs(c[r]) <= 1e-4 * scale + 1e-12)) return 0;
+        }
+        near_w = std::fmax(0.0, (double)view->projection[14]);
+    }
+    double lo[2] = {INFINITY, INFINITY}, hi[2] = {-INFINITY, -INFINITY};
+    for (int corner = 0; corner < 8; ++corner) {
+        const double p[3] = {aabb[(corner & 1) ? 3 : 0], aabb[(corner & 2) ? 4 : 1], aabb[(corner & 4) ? 5 : 2]};
+        double c[4];
+        clip(p, c);
+        if (!std::isfinite(c[0]) || !std::isfinite(c[1]) || !std::isfinite(c[2]) || !std::isfinite(c[3])) return 0;
+        if (ortho ? !(c[3] > 0.0 && c[2] < c[3]) : !(c[3] > near_w && c[3] > 1e-9)) return 0;
+        // primary_ray: pixel centre px -> ndc (px / W * 2 - 1, 1 - py / H * 2)
+        const double px = (c[0] / c[3] + 1.0) * 0.5 * (double)width, py = (1.0 - c[1] / c[3]) * 0.5 * (double)height;
+        lo[0] = std::fmin(lo[0], px);
+        hi[0] = std::fmax(hi[0], px);
+        lo[1] = std::fmin(lo[1], py);
+        hi[1] = std::fmax(hi[1], py);
+    }
+    // pixel x is hit when x + 0.5 - jitter (0 <= jitter < 1) lies in [lo, hi]: x in [lo - 0.5, hi + 0.5]
+    const double size[2] = {(double)width, (double)height};
+    for (int a = 0; a < 2; ++a) {
+        const double p0 = std::floor(lo[a] - 0.5) - (double)guard, p1 = std::ceil(hi[a] + 0.5) + 1.0 + (double)guard;
+        rect[a] = (int32_t)std::fmin(std::fmax(p0, 0.0), size[a]);
+        rect[2 + a] = (int32_t)std::fmin(std::fmax(p1, 0.0), size[a]);
+    }
+    if (rect[2] <= rect[0] || rect[3] <= rect[1]) rect[0] = rect[1] = rect[2] = rect[3] = 0;  // off screen
+    return 1;
+}
+
 }  // extern "C"

@@ -250,6 +250,9 @@ def lib() -> C.CDLL:
         "hks_build": (i32, [vp, i32]),
         "hks_get_desc": (i32, [vp, C.POINTER(hk_scene_desc)]),
         "hks_shared_transform": (i32, [vp, u32]),
+        "hks_instance_bounds": (i32, [vp, vp, u32, C.POINTER(C.c_double)]),
+        "hks_screen_bounds": (i32, [C.POINTER(C.c_double), C.POINTER(hk_view), u32, u32, u32, C.POINTER(i32)]),
+        "hk_tile_skip_info": (i32, [vp, C.POINTER(u32), C.POINTER(i32), C.POINTER(i32)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -269,6 +272,7 @@ EXPORTED_SYMBOLS = [
     "hk_load_reservoirs", "hk_reset_counters", "hk_read_counters", "hk_enable_kernel_timing", "hk_kernel_timing", "hk_set_kernel_timing_interval",
     "hk_trace", "hk_selftest_f16", "hk_selftest_div", "hk_selftest_rcp", "hk_selftest_count", "hk_selftest_texture", "hk_selftest_math", "hks_create", "hks_destroy", "hks_last_error", "hks_add_mesh", "hks_add_material",
     "hks_add_instance", "hks_build", "hks_get_desc", "hk_scene_shared_transform", "hks_shared_transform",
+    "hks_instance_bounds", "hks_screen_bounds", "hk_tile_skip_info",
 ]
 
 

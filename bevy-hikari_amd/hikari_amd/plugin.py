@@ -334,6 +334,15 @@ class HikariRenderer:
         _check(self.ctx, self._L.hk_scene_shared_transform(self.ctx, C.byref(out)), "hk_scene_shared_transform")
         return bool(out.value)
 
+    def tile_skip_info(self) -> dict:
+        """The last frame's background tile skip (hk_tile_skip_info, option bg_tile_skip): workgroups skipped in the
+        G-buffer, direct / emissive and indirect launches, and the current G-buffer's screen bound (x0, y0, x1, y1),
+        None while there is none."""
+        skipped, bound, bounded = (C.c_uint32 * 3)(), (C.c_int32 * 4)(), C.c_int32()
+        _check(self.ctx, self._L.hk_tile_skip_info(self.ctx, skipped, bound, C.byref(bounded)), "hk_tile_skip_info")
+        return {"gbuffer": skipped[0], "direct": skipped[1], "indirect": skipped[2],
+                "bound": tuple(bound) if bounded.value else None}
+
     def scene_array(self, array: int, dtype, count: int) -> np.ndarray:
         """Device copy of group-2 scene array `array` (hk_scene_desc order) as `count` records."""
         out = np.empty(count, dtype)

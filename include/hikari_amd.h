@@ -239,6 +239,10 @@ void hk_settings_default(hk_settings* out);
  *   shared_xform (1)         in a scene whose instances all carry one bit-identical transform
  *                            (hk_scene_shared_transform) a walk computes its instance-local ray once instead of at
  *                            every instance it enters; 0: always the general walk
+ *   bg_tile_skip (1)         workgroups of k_gbuffer and of the light passes whose 16x16 tile lies outside the scene's
+ *                            screen bound (hikari_scene.h hks_screen_bounds, from the instances' world box), and whose
+ *                            targets already hold a background pixel's constants (the bg_elision masks' history),
+ *                            return at their first instruction; 0: every workgroup runs (hk_tile_skip_info)
  * hk_set_option returns HK_ERR_INVALID for an unknown key, a value outside the key's range, or a fractional value
  * for any key but the pixel-count thresholds (*_px). */
 int hk_set_option(hk_ctx* ctx, const char* key, double value);
@@ -339,6 +343,13 @@ int hk_scene_counts(const hk_ctx* ctx, uint32_t counts[9]);
  * hk_update_instances / hk_update_meshes / hk_set_instances after them), 0 otherwise.  It does not depend on option
  * shared_xform, which decides whether the walks use it.  HK_ERR_STATE without a scene. */
 int hk_scene_shared_transform(const hk_ctx* ctx, int32_t* shared);
+/* Background tile skip (option bg_tile_skip) of the last frame: skipped[0..2] = the workgroups that returned at once in
+ * its hk_render_gbuffer launch, in hk_render_frame's direct / emissive launch(es) (per launch) and in its indirect
+ * launch (0 where nothing was skipped: the option off, bg_elision off, no screen bound, a mask whose history does not
+ * reach back far enough yet, a pass whose background pixels still store).  bound: the pixel rectangle [x0, y0, x1, y1)
+ * of the current G-buffer's screen bound, *bounded = 1; the whole frame and 0 while there is none (host planes, the
+ * eye inside the scene's box, after hk_update_meshes).  Any out pointer may be NULL.  HK_ERR_STATE before hk_resize. */
+int hk_tile_skip_info(const hk_ctx* ctx, uint32_t skipped[3], int32_t bound[4], int32_t* bounded);
 /* The host arithmetic hk_set_instances sizes its allocations and launches with (needs no device or context): the
  * nine counts after `set` replaces the instances of the host-built `uploaded` scene: the instances, 3n - 2 TLAS
  * nodes, the emitters (255 * emissive[3] * |emissive.rgb| > 0 in float, so a NaN does not emit; `materials`, if

@@ -49,6 +49,19 @@ int hks_get_desc(const hks_scene* scene, hk_scene_desc* out);
  * property behind hk_scene_shared_transform, for callers that want it without a device. */
 int hks_shared_transform(const float* matrices, uint32_t n);
 
+/* The world box (min xyz, max xyz) of n instances from their column-major models and local boxes (6 floats each: centre
+ * xyz, half extents xyz), every corner transformed in double and the box grown outward by a relative 1e-5.  Returns 1,
+ * or 0 without a box (n == 0, a null pointer, a non-finite corner). */
+int hks_instance_bounds(const float* models, const float* local_aabbs, uint32_t n, double aabb[6]);
+/* A conservative pixel rectangle [rect[0], rect[2]) x [rect[1], rect[3]) of a width x height frame outside which no
+ * primary ray of `view` (hk_render_gbuffer, any prepass jitter) can meet the box: the pixel box of its 8 projected
+ * corners, grown by `guard` pixels and clipped to the frame; all zeros when the box is off screen.  Returns 1, or 0 when
+ * there is no such rectangle: a corner at or behind the near plane (the eye inside or next to the box), a perspective
+ * view whose world_position is not its centre of projection, non-finite input.  This is the bound behind option
+ * bg_tile_skip. */
+int hks_screen_bounds(const double aabb[6], const hk_view* view, uint32_t width, uint32_t height, uint32_t guard,
+                      int32_t rect[4]);
+
 #ifdef __cplusplus
 }
 #endif
