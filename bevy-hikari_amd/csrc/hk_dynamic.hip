@@ -1,5 +1,5 @@
-// hk_dynamic.hip — dynamic instances, deforming meshes and changed instance sets
-//  on the device.
+// hk_dynamic.hip — dynamic instances, deforming meshes, changed instance sets
+//  and appended meshes on the device.
 //
 // The reference re-runs `prepare_instances` on the CPU whenever a transform changes
 // (instance.rs:284-437: instance records with world AABBs and inverse-transpose models, the
@@ -548,6 +548,59 @@ __global__ __launch_bounds__(256) void k_build_mesh_bvh(const MeshUpdate* tab, c
                    seg + 2u * (size_t)m.shape0, levels + m.slot);
 }
 
+// ---- appended meshes (mesh.rs:77-166 prepare_mesh_assets on AssetEvent::Created, mod.rs:379-467 GpuMesh::try_from;
+// hk_scene.cpp hks_add_mesh + hks_build "concatenate").  One thread per vertex of the new meshes: the
+// whole hk_vertex (position, u | normal, v) from the three staged attribute streams, as two 16-byte stores.  Then one
+// thread per triangle: its three mesh-local indices (a list: 3t, 3t + 1, 3t + 2; a strip: t, t + 1, t + 2 with the
+// first two swapped for an odd mesh-local t, as hks_add_mesh winds it; no indices: the identity), the whole
+// hk_primitive as three 16-byte stores (position, index per corner), and its shape box folded as
+// k_update_mesh_geometry folds it.  The triangles read the staged positions, not the vertex array, so the two halves
+// do not depend on each other.  Every index was checked against vertex_count on the host (hk_add_meshes).
+__global__ __launch_bounds__(256) void k_assemble_meshes(const MeshUpdate* tab, const MeshSource* sources,
+                                                         uint32_t n_meshes, uint32_t n_vertices, uint32_t n_shapes,
+                                                         const float* positions, const float* normals, const float* uvs,
+                                                         const uint32_t* indices, hk_vertex* vertices,
+                                                         hk_primitive* prims, BBox* shapes)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n_vertices) {
+        const MeshUpdate& m = tab[mesh_of(tab, n_meshes, i, false)];
+        const uint32_t v = i - m.vertex0;
+        if (v >= m.vertex_count) return;
+        const float* p = positions + 3u * (size_t)i;
+        const float* n = normals + 3u * (size_t)i;
+        const float* t = uvs + 2u * (size_t)i;
+        float4* out = reinterpret_cast<float4*>(vertices + m.vertex + v);
+        out[0] = make_float4(p[0], p[1], p[2], t[0]);
+        out[1] = make_float4(n[0], n[1], n[2], t[1]);
+        return;
+    }
+    const uint32_t j = i - n_vertices;
+    if (j >= n_shapes) return;
+    const uint32_t k = mesh_of(tab, n_meshes, j, true);
+    const MeshUpdate& m = tab[k];
+    const MeshSource s = sources[k];
+    const uint32_t t = j - m.shape0;
+    if (t >= m.shapes) return;
+    const uint32_t odd = s.strip ? (t & 1u) : 0u;
+    const uint32_t first = s.strip ? t : 3u * t;
+    const uint32_t at[3] = {first + odd, first + 1u - odd, first + 2u};
+    float4* out = reinterpret_cast<float4*>(prims + m.primitive + t);
+    const float inf = __uint_as_float(0x7F800000u);
+    float mn[3] = {inf, inf, inf}, mx[3] = {-inf, -inf, -inf};
+    for (int c = 0; c < 3; ++c) {
+        const uint32_t v = s.index0 == MESH_NO_INDICES ? at[c] : indices[(size_t)s.index0 + at[c]];
+        const float* p = positions + 3u * (size_t)(m.vertex0 + v);
+        const float x[3] = {p[0], p[1], p[2]};
+        for (int a = 0; a < 3; ++a) {
+            mn[a] = host_fmin(mn[a], x[a]);
+            mx[a] = host_fmax(mx[a], x[a]);
+        }
+        out[c] = make_float4(x[0], x[1], x[2], __uint_as_float(v));
+    }
+    shapes[j] = BBox{{mn[0], mn[1], mn[2]}, {mx[0], mx[1], mx[2]}};
+}
+
 // ---- instance records (instance.rs:284-330; hk_scene.cpp hks_build "instances")
 HKD void transform_point(const float* m, const float* p, float* o)
 {
@@ -903,11 +956,8 @@ void launch_set_instances(const DynamicArgs& D, const SetArgs& S, hipStream_t st
 }
 
 // tab: the LDS-sized meshes first (n_lds of them), then the others; levels[slot]: each mesh's split levels
-void launch_mesh_update(const MeshUpdateArgs& M, hipStream_t st)
+static void launch_mesh_builds(const MeshUpdateArgs& M, hipStream_t st)
 {
-    const uint32_t items = M.n_vertices + M.n_shapes;
-    hipLaunchKernelGGL(k_update_mesh_geometry, dim3((items + 255u) / 256u), dim3(256), 0, st, M.table, M.n_meshes,
-                       M.n_vertices, M.n_shapes, M.positions, M.normals, M.vertices, M.primitives, (BBox*)M.shapes);
     if (M.n_lds)
         hipLaunchKernelGGL(k_build_mesh_bvh<true>, dim3(M.n_lds), dim3(256), 0, st, M.table_by_size, (const BBox*)M.shapes,
                            M.buckets, M.blas, M.idx, (Segment*)M.segments, M.levels);
@@ -915,6 +965,22 @@ void launch_mesh_update(const MeshUpdateArgs& M, hipStream_t st)
         hipLaunchKernelGGL(k_build_mesh_bvh<false>, dim3(M.n_meshes - M.n_lds), dim3(256), 0, st,
                            M.table_by_size + M.n_lds, (const BBox*)M.shapes, M.buckets, M.blas, M.idx,
                            (Segment*)M.segments, M.levels);
+}
+void launch_mesh_update(const MeshUpdateArgs& M, hipStream_t st)
+{
+    const uint32_t items = M.n_vertices + M.n_shapes;
+    hipLaunchKernelGGL(k_update_mesh_geometry, dim3((items + 255u) / 256u), dim3(256), 0, st, M.table, M.n_meshes,
+                       M.n_vertices, M.n_shapes, M.positions, M.normals, M.vertices, M.primitives, (BBox*)M.shapes);
+    launch_mesh_builds(M, st);
+}
+void launch_mesh_add(const MeshAddArgs& A, hipStream_t st)
+{
+    const MeshUpdateArgs& M = A.M;
+    const uint32_t items = M.n_vertices + M.n_shapes;
+    hipLaunchKernelGGL(k_assemble_meshes, dim3((items + 255u) / 256u), dim3(256), 0, st, M.table, A.sources, M.n_meshes,
+                       M.n_vertices, M.n_shapes, M.positions, M.normals, A.uvs, A.indices, M.vertices, M.primitives,
+                       (BBox*)M.shapes);
+    launch_mesh_builds(M, st);
 }
 uint32_t mesh_lds_shapes() { return BVH_LDS_SHAPES; }
 

@@ -214,6 +214,23 @@ struct MeshUpdateArgs {
 void launch_mesh_update(const MeshUpdateArgs& M, hipStream_t st);
 uint32_t mesh_lds_shapes();
 
+// Appended meshes (hk_add_meshes, hk_dynamic.hip): beside each mesh's MeshUpdate record (its destination slices past
+// the arrays' ends, vertex0 / shape0 its place in the staged streams; has_normals is not read), where its indices lie
+// and how its triangles read them.
+constexpr uint32_t MESH_NO_INDICES = 0xFFFFFFFFu;
+struct MeshSource {
+    uint32_t index0;  // its first index in the staged index stream; MESH_NO_INDICES: 0 .. vertex_count - 1
+    uint32_t strip;   // 1: a TriangleStrip (triangle t: t, t + 1, t + 2, the first two swapped for odd t), 0: a list
+};
+struct MeshAddArgs {
+    MeshUpdateArgs M;            // M.positions / M.normals: the staged streams, vertex_count x 3 per mesh
+    const MeshSource* sources;   // M.n_meshes records in list order
+    const float* uvs;            // n_vertices x 2
+    const uint32_t* indices;     // the indexed meshes' indices, one after another
+};
+// vertex and primitive records written whole with the shape boxes (one launch), then launch_mesh_update's builds
+void launch_mesh_add(const MeshAddArgs& A, hipStream_t st);
+
 // Post-process (hk_post.hip over include/hk_post.h)
 struct PostArgs {
     hk_pp_frame frame;

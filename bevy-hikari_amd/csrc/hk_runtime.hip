@@ -377,7 +377,8 @@ struct hk_ctx {
     size_t cap[9] = {};
     size_t collapse_cap = 0;
     std::vector<float> emissive;
-    uint32_t* blas_aux = nullptr;
+    uint32_t* blas_aux = nullptr;  // three rows (primitive offset, node base, node count) of aux_stride words each
+    size_t aux_stride = 0;         // = cap[2]: hk_add_meshes grows the rows with the asset nodes
     void* mesh_scratch = nullptr;
     size_t mesh_bytes = 0;
     // GlobalTransformQueue[1] of every instance (transform.rs:32-44): the models as of the previous
@@ -1344,11 +1345,12 @@ int hk_scene_upload(hk_ctx* c, const hk_scene_desc* d)
     c->mesh_bytes = 0;
     release(c->blas_aux);
     uint32_t*& d_aux = c->blas_aux;
-    HK_HIP(c, hipMalloc(&d_aux, (size_t)(n_blas ? n_blas : 1) * 12));
+    const size_t stride = c->aux_stride = c->cap[2];
+    HK_HIP(c, hipMalloc(&d_aux, stride * 12));
     if (n_blas) {
         HK_HIP(c, hipMemcpy(d_aux, prim_offset.data(), (size_t)n_blas * 4, hipMemcpyHostToDevice));
-        HK_HIP(c, hipMemcpy(d_aux + n_blas, node_base.data(), (size_t)n_blas * 4, hipMemcpyHostToDevice));
-        HK_HIP(c, hipMemcpy(d_aux + 2 * (size_t)n_blas, node_count.data(), (size_t)n_blas * 4, hipMemcpyHostToDevice));
+        HK_HIP(c, hipMemcpy(d_aux + stride, node_base.data(), (size_t)n_blas * 4, hipMemcpyHostToDevice));
+        HK_HIP(c, hipMemcpy(d_aux + 2 * stride, node_count.data(), (size_t)n_blas * 4, hipMemcpyHostToDevice));
     }
     launch_fill_leaves((hk_node*)c->buf[2], n_blas, d_aux, (const hk_primitive*)c->buf[1], (hk_node*)c->buf[5],
                        n_tlas, (const hk_instance*)c->buf[4], c->count[4], c->stream);
@@ -1362,8 +1364,7 @@ int hk_scene_upload(hk_ctx* c, const hk_scene_desc* d)
     // stage_scene without rounding)
     HK_HIP(c, hipMalloc(&c->blas_wide, (size_t)(n_blas ? n_blas : 1) * WIDE_NODE_BYTES));
     HK_HIP(c, hipMalloc(&c->tlas_wide, (size_t)(n_tlas ? n_tlas : 1) * WIDE_NODE_BYTES));
-    launch_build_wide((const hk_node*)c->buf[2], n_blas, d_aux + n_blas, d_aux + 2 * (size_t)n_blas, c->blas_wide,
-                      c->stream);
+    launch_build_wide((const hk_node*)c->buf[2], n_blas, d_aux + stride, d_aux + 2 * stride, c->blas_wide, c->stream);
     launch_build_wide((const hk_node*)c->buf[5], n_tlas, nullptr, nullptr, c->tlas_wide, c->stream);
     // the light walks' node copies, leaf-collapsed (k_collapse_decide); the arrays above stay as
     // uploaded (hk_read_scene_array, the wide layout and hk_update_instances read them)
@@ -1376,7 +1377,7 @@ int hk_scene_upload(hk_ctx* c, const hk_scene_desc* d)
     HK_HIP(c, hipMemcpyAsync(c->walk_nodes[1], c->buf[5], (size_t)n_tlas * sizeof(hk_node), hipMemcpyDeviceToDevice,
                              c->stream));
     if (c->on(OPT_LEAF_COLLAPSE)) {
-        launch_collapse_leaves(c->walk_nodes[0], n_blas, d_aux + n_blas, d_aux + 2 * (size_t)n_blas, c->collapse_scratch,
+        launch_collapse_leaves(c->walk_nodes[0], n_blas, d_aux + stride, d_aux + 2 * stride, c->collapse_scratch,
                                c->stream);
         launch_collapse_leaves(c->walk_nodes[1], n_tlas, nullptr, nullptr, c->collapse_scratch, c->stream);
     }
@@ -1551,18 +1552,17 @@ static int plan_instance_set(const uint32_t* count, const std::vector<hk_ctx::Me
     return HK_OK;
 }
 
-// device-only derivatives of the asset nodes, over the whole array: leaf boxes, the G-buffer wide layout and the light
-// walks' copy with its leaf collapse (as hk_scene_upload derives them)
-static void refresh_blas_derivatives(hk_ctx* c, hipStream_t st)
+// device-only derivatives of the asset nodes, over the whole array of n_blas nodes: leaf boxes, the G-buffer wide layout
+// and the light walks' copy with its leaf collapse (as hk_scene_upload derives them)
+static void refresh_blas_derivatives(hk_ctx* c, hipStream_t st, uint32_t n_blas)
 {
-    const uint32_t n_blas = c->count[2];
     launch_fill_leaves((hk_node*)c->buf[2], n_blas, c->blas_aux, (const hk_primitive*)c->buf[1], nullptr, 0, nullptr, 0,
                        st);
-    launch_build_wide((const hk_node*)c->buf[2], n_blas, c->blas_aux + n_blas, c->blas_aux + 2 * (size_t)n_blas,
+    launch_build_wide((const hk_node*)c->buf[2], n_blas, c->blas_aux + c->aux_stride, c->blas_aux + 2 * c->aux_stride,
                       c->blas_wide, st);
     (void)hipMemcpyAsync(c->walk_nodes[0], c->buf[2], (size_t)n_blas * sizeof(hk_node), hipMemcpyDeviceToDevice, st);
     if (c->on(OPT_LEAF_COLLAPSE))
-        launch_collapse_leaves(c->walk_nodes[0], n_blas, c->blas_aux + n_blas, c->blas_aux + 2 * (size_t)n_blas,
+        launch_collapse_leaves(c->walk_nodes[0], n_blas, c->blas_aux + c->aux_stride, c->blas_aux + 2 * c->aux_stride,
                                c->collapse_scratch, st);
 }
 
@@ -1629,19 +1629,18 @@ static int rebuild_instances(hk_ctx* c, const float* models, const float* local_
     if (set) {
         HK_TRY(reserve_set(c, set->counts, &old_prev.p));
         if (!set->fresh.empty()) {  // register the new slices: their rows of the per-node mesh tables, then the derivatives
-            const uint32_t n_blas = c->count[2];
             for (const hk_ctx::MeshSlice& f : set->fresh) {
                 const hk_mesh_index& x = f.index;
                 const uint32_t value[3] = {x.primitive, x.node[0], x.node[1]};
                 std::vector<uint32_t> row(x.node[1]);
                 for (int k = 0; k < 3; ++k) {
                     std::fill(row.begin(), row.end(), value[k]);
-                    HK_HIP(c, hipMemcpy(c->blas_aux + k * (size_t)n_blas + x.node[0], row.data(), row.size() * 4,
+                    HK_HIP(c, hipMemcpy(c->blas_aux + k * c->aux_stride + x.node[0], row.data(), row.size() * 4,
                                         hipMemcpyHostToDevice));
                 }
                 c->meshes.push_back(f);
             }
-            refresh_blas_derivatives(c, st);
+            refresh_blas_derivatives(c, st, c->count[2]);
         }
         for (hk_ctx::MeshSlice& s : c->meshes) s.used = 0;
         for (uint32_t k : set->slice) c->meshes[k].used++;
@@ -1873,7 +1872,7 @@ int hk_update_meshes(hk_ctx* c, const hk_mesh_update* meshes, uint32_t mesh_coun
     M.levels = (uint32_t*)part[7];
     timed(c, "update_meshes", st, [&] {
         launch_mesh_update(M, st);
-        refresh_blas_derivatives(c, st);
+        refresh_blas_derivatives(c, st, c->count[2]);
     });
     HK_HIP(c, hipGetLastError());
     ml.device = (const uint32_t*)part[7];
@@ -1919,6 +1918,310 @@ int hk_scene_counts(const hk_ctx* c, uint32_t counts[9])
     if (!c || !counts) return HK_ERR_INVALID;
     if (!c->has_scene) return HK_ERR_STATE;
     std::memcpy(counts, c->count, sizeof(c->count));
+    return HK_OK;
+}
+
+// ---- hk_add_meshes
+// What hk_add_meshes decides on the host before any device work: each mesh's appended slice, its triangles, the
+// vertices its indices reach (MeshSlice::vertex_need, from the scan that refuses an index out of range) and the counts
+// after.
+struct MeshAddPlan {
+    std::vector<hk_mesh_index> slices;
+    std::vector<uint32_t> tris, vertex_need;
+    uint32_t after[9] = {};
+    uint64_t n_vertices = 0, n_shapes = 0, n_indices = 0;  // sums over the list (indices: of the indexed meshes)
+};
+constexpr uint64_t MESH_TOTAL_MAX = 0x40000000u;  // hk_update_meshes' bound on vertices and primitives
+
+static int plan_add_meshes(const uint32_t* before, const hk_mesh_desc* meshes, uint32_t n, MeshAddPlan* out,
+                           std::string* why)
+{
+    auto no = [&](const std::string& text) {
+        *why = text;
+        return HK_ERR_INVALID;
+    };
+    if (!meshes) return no("null mesh list");
+    if (n == 0) return no("an empty mesh list");
+    out->slices.resize(n);
+    out->tris.resize(n);
+    out->vertex_need.resize(n);
+    uint64_t at[3] = {before[0], before[1], before[2]};
+    for (uint32_t k = 0; k < n; ++k) {
+        const hk_mesh_desc& m = meshes[k];
+        const std::string who = "mesh " + std::to_string(k) + ": ";
+        // hks_add_mesh's checks, in its order
+        if (!m.positions) return no(who + "MissingAttributePosition");
+        if (!m.normals) return no(who + "MissingAttributeNormal");
+        if (!m.uvs) return no(who + "MissingAttributeUV");
+        const uint32_t ni = m.indices ? m.index_count : m.vertex_count;
+        uint32_t top = 0;
+        if (m.indices) {
+            for (uint32_t i = 0; i < ni; ++i) {
+                if (m.indices[i] >= m.vertex_count) return no(who + "index out of range");
+                top = std::max(top, m.indices[i]);
+            }
+        } else if (ni) {
+            top = ni - 1u;
+        }
+        uint32_t tris = 0;
+        if (m.topology == HKS_TRIANGLE_LIST) {
+            if (ni % 3u != 0) return no(who + "IncompatiblePrimitiveTopology");
+            tris = ni / 3u;
+        } else if (m.topology == HKS_TRIANGLE_STRIP) {
+            tris = ni >= 3u ? ni - 2u : 0u;
+        } else {
+            return no(who + "IncompatiblePrimitiveTopology");
+        }
+        if (tris == 0) return no(who + "NoPrimitive");
+        out->slices[k] = hk_mesh_index{(uint32_t)at[0], (uint32_t)at[1], {(uint32_t)at[2], 3u * tris - 2u}};
+        out->tris[k] = tris;
+        out->vertex_need[k] = top + 1u;
+        at[0] += m.vertex_count;
+        at[1] += tris;
+        at[2] += 3u * (uint64_t)tris - 2u;
+        out->n_vertices += m.vertex_count;
+        out->n_shapes += tris;
+        if (m.indices) out->n_indices += ni;
+        if (at[0] > MESH_TOTAL_MAX || at[1] > MESH_TOTAL_MAX || at[2] > MESH_TOTAL_MAX || out->n_indices > MESH_TOTAL_MAX)
+            return no("too many vertices, primitives or nodes");
+    }
+    std::memcpy(out->after, before, sizeof(out->after));
+    for (int i = 0; i < 3; ++i) out->after[i] = (uint32_t)at[i];
+    return HK_OK;
+}
+
+// the message of the calling thread's last hk_add_meshes_counts, which has no context to keep it (empty: it succeeded)
+static thread_local std::string counts_error;
+const char* hk_add_meshes_counts_error(void) { return counts_error.c_str(); }
+
+int hk_add_meshes_counts(const uint32_t before[9], const hk_mesh_desc* meshes, uint32_t mesh_count,
+                         hk_mesh_index* slices, uint32_t after[9])
+{
+    counts_error.clear();
+    auto no = [&](const std::string& text) {
+        counts_error = "hk_add_meshes: " + text;
+        return HK_ERR_INVALID;
+    };
+    if (!before) return no("null counts");
+    if (!slices) return no("null slices");
+    MeshAddPlan plan;
+    std::string why;
+    const int rc = plan_add_meshes(before, meshes, mesh_count, &plan, &why);
+    if (rc != HK_OK) return no(why);
+    std::memcpy(slices, plan.slices.data(), plan.slices.size() * sizeof(hk_mesh_index));
+    if (after) std::memcpy(after, plan.after, sizeof(plan.after));
+    return HK_OK;
+}
+
+int hk_add_meshes(hk_ctx* c, const hk_mesh_desc* meshes, uint32_t mesh_count, hk_mesh_index* slices, void* stream)
+{
+    if (!c) return HK_ERR_INVALID;
+    if (!c->has_scene) return fail(c, HK_ERR_STATE, "no scene uploaded (hk_scene_upload)");
+    if (!slices) return fail(c, HK_ERR_INVALID, "hk_add_meshes: null slices");
+    MeshAddPlan plan;
+    {
+        std::string why;
+        const int rc = plan_add_meshes(c->count, meshes, mesh_count, &plan, &why);
+        if (rc != HK_OK) return fail(c, rc, "hk_add_meshes: " + why);
+    }
+    const uint32_t n_vertices = (uint32_t)plan.n_vertices, n_shapes = (uint32_t)plan.n_shapes;
+    const uint32_t n_indices = (uint32_t)plan.n_indices;
+    (void)hipSetDevice(c->device);
+    hipStream_t st = pick(c, stream);
+    HK_TRY(c->sch.gb_join(st));
+    HK_TRY(c->sch.gb_serialize(false));
+    // the tables: the meshes in list order and by size, and where each mesh's indices lie
+    std::vector<MeshUpdate> tab(mesh_count), by_size;
+    std::vector<MeshSource> sources(mesh_count);
+    uint32_t n_lds = 0;
+    {
+        uint32_t v0 = 0, s0 = 0, i0 = 0;
+        for (uint32_t k = 0; k < mesh_count; ++k) {
+            const hk_mesh_index& x = plan.slices[k];
+            tab[k] = MeshUpdate{x.vertex, meshes[k].vertex_count, x.primitive, plan.tris[k], x.node[0], v0, s0, k, 1u};
+            sources[k] = MeshSource{meshes[k].indices ? i0 : MESH_NO_INDICES, meshes[k].topology == HKS_TRIANGLE_STRIP ? 1u : 0u};
+            v0 += meshes[k].vertex_count;
+            s0 += plan.tris[k];
+            if (meshes[k].indices) i0 += meshes[k].index_count;
+            n_lds += plan.tris[k] <= mesh_lds_shapes() ? 1u : 0u;
+        }
+        for (int big = 0; big < 2; ++big)
+            for (const MeshUpdate& m : tab)
+                if ((m.shapes > mesh_lds_shapes()) == (big == 1)) by_size.push_back(m);
+    }
+    // scratch: the tables, the attribute and index streams, and the builds' shape boxes, indices, segments and levels
+    auto align = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t sz[] = {align((size_t)mesh_count * sizeof(MeshUpdate)), align((size_t)mesh_count * sizeof(MeshUpdate)),
+                         align((size_t)mesh_count * sizeof(MeshSource)),
+                         align((size_t)n_vertices * 12), align((size_t)n_vertices * 12), align((size_t)n_vertices * 8),
+                         align((size_t)(n_indices ? n_indices : 1) * 4),
+                         align((size_t)n_shapes * 24),   align((size_t)n_shapes * 8),
+                         align((size_t)n_shapes * 24),   align((size_t)mesh_count * 4)};
+    constexpr int PARTS = sizeof(sz) / sizeof(sz[0]);
+    size_t total = 0;
+    for (size_t b : sz) total += b;
+    // Room (hikari_amd.h hk_add_meshes "Capacity").  First every allocation the call needs, with the context untouched:
+    // a failure here frees them and leaves the context as it was.  Then the grown arrays take their contents, copied on
+    // the stream, and a zeroed tail; the buffers they leave are freed after the call's one wait, or on the way out.
+    struct Buffers {
+        std::vector<void*> p;
+        ~Buffers()
+        {
+            for (void* q : p) (void)hipFree(q);
+        }
+    } fresh, old;
+    auto grown = [](size_t need, size_t cap) { return std::max(need, cap + cap / 2); };
+    auto alloc = [&](size_t bytes) -> void* {
+        void* nb = nullptr;
+        if (hipMalloc(&nb, bytes) != hipSuccess) return nullptr;
+        fresh.p.push_back(nb);
+        return nb;
+    };
+    size_t cap[3];
+    void* nbuf[3] = {};
+    bool ok = true;
+    for (int i = 0; i < 3; ++i) {
+        cap[i] = plan.after[i] > c->cap[i] ? grown(plan.after[i], c->cap[i]) : c->cap[i];
+        if (cap[i] != c->cap[i]) ok = ok && (nbuf[i] = alloc(staged_alloc_bytes(cap[i], SCENE_ELEM[i])));
+    }
+    void *n_wide = nullptr, *n_walk = nullptr, *n_aux = nullptr, *n_collapse = nullptr, *n_scratch = nullptr;
+    if (cap[2] != c->cap[2])
+        ok = ok && (n_wide = alloc(cap[2] * WIDE_NODE_BYTES)) && (n_walk = alloc(cap[2] * sizeof(hk_node))) &&
+             (n_aux = alloc(cap[2] * 12));
+    size_t collapse_cap = c->collapse_cap;
+    {
+        const size_t need = std::max<size_t>(1, std::max(plan.after[2], c->count[5]));
+        if (need > collapse_cap) {
+            collapse_cap = grown(need, collapse_cap);
+            ok = ok && (n_collapse = alloc(collapse_cap * 4));
+        }
+    }
+    if (c->mesh_bytes < total) ok = ok && (n_scratch = alloc(total));
+    if (!ok) return fail(c, HK_ERR_HIP, "hk_add_meshes: out of device memory");
+    fresh.p.clear();  // (all of them go into the context below)
+    // (the pointers first, so that nothing allocated is lost on a failed enqueue)
+    void** slot[] = {&c->buf[0], &c->buf[1], &c->buf[2], (void**)&c->blas_wide, (void**)&c->walk_nodes[0]};
+    void* repl[] = {nbuf[0], nbuf[1], nbuf[2], n_wide, n_walk};
+    void* was[5];
+    for (int k = 0; k < 5; ++k) {
+        was[k] = *slot[k];
+        if (!repl[k]) continue;
+        old.p.push_back(*slot[k]);
+        *slot[k] = repl[k];
+    }
+    uint32_t* aux_was = c->blas_aux;
+    const size_t stride_was = c->aux_stride, have = c->count[2];
+    if (n_aux) {
+        old.p.push_back(c->blas_aux);
+        c->blas_aux = (uint32_t*)n_aux;
+        c->aux_stride = cap[2];
+    }
+    if (n_collapse) {
+        old.p.push_back(c->collapse_scratch);
+        c->collapse_scratch = (uint32_t*)n_collapse;
+        c->collapse_cap = collapse_cap;
+    }
+    if (n_scratch) {
+        old.p.push_back(c->mesh_scratch);
+        c->mesh_scratch = n_scratch;
+        c->mesh_bytes = total;
+    }
+    for (int i = 0; i < 3; ++i) c->cap[i] = cap[i];
+    {
+        const size_t elem[5] = {SCENE_ELEM[0], SCENE_ELEM[1], SCENE_ELEM[2], WIDE_NODE_BYTES, sizeof(hk_node)};
+        const int of[5] = {0, 1, 2, 2, 2};
+        for (int k = 0; k < 5; ++k) {
+            if (!repl[k]) continue;
+            const size_t keep = (size_t)c->count[of[k]] * elem[k];
+            const size_t bytes = k < 3 ? staged_alloc_bytes(cap[of[k]], elem[k]) : cap[2] * elem[k];
+            if (keep) HK_HIP(c, hipMemcpyAsync(repl[k], was[k], keep, hipMemcpyDeviceToDevice, st));
+            if (bytes > keep) HK_HIP(c, hipMemsetAsync((char*)repl[k] + keep, 0, bytes - keep, st));
+        }
+    }
+    if (n_aux) {  // the per-node mesh tables, re-laid at the new stride: unregistered nodes read U32_MAX
+        HK_HIP(c, hipMemsetAsync(n_aux, 0xFF, cap[2] * 12, st));
+        for (size_t k = 0; k < 3 && have; ++k)
+            HK_HIP(c, hipMemcpyAsync((uint32_t*)n_aux + k * cap[2], aux_was + k * stride_was, have * 4,
+                                     hipMemcpyDeviceToDevice, st));
+    }
+    char* part[PARTS];
+    {
+        char* p = (char*)c->mesh_scratch;
+        for (int k = 0; k < PARTS; ++k) {
+            part[k] = p;
+            p += sz[k];
+        }
+    }
+    HK_HIP(c, hipMemcpyAsync(part[0], tab.data(), tab.size() * sizeof(MeshUpdate), hipMemcpyHostToDevice, st));
+    HK_HIP(c, hipMemcpyAsync(part[1], by_size.data(), by_size.size() * sizeof(MeshUpdate), hipMemcpyHostToDevice, st));
+    HK_HIP(c, hipMemcpyAsync(part[2], sources.data(), sources.size() * sizeof(MeshSource), hipMemcpyHostToDevice, st));
+    for (uint32_t k = 0; k < mesh_count; ++k) {
+        const size_t v0 = tab[k].vertex0, nv = meshes[k].vertex_count;
+        if (nv) {
+            HK_HIP(c, hipMemcpyAsync(part[3] + v0 * 12, meshes[k].positions, nv * 12, hipMemcpyHostToDevice, st));
+            HK_HIP(c, hipMemcpyAsync(part[4] + v0 * 12, meshes[k].normals, nv * 12, hipMemcpyHostToDevice, st));
+            HK_HIP(c, hipMemcpyAsync(part[5] + v0 * 8, meshes[k].uvs, nv * 8, hipMemcpyHostToDevice, st));
+        }
+        if (meshes[k].indices)
+            HK_HIP(c, hipMemcpyAsync(part[6] + (size_t)sources[k].index0 * 4, meshes[k].indices,
+                                     (size_t)meshes[k].index_count * 4, hipMemcpyHostToDevice, st));
+    }
+    // the new meshes' rows of the per-node mesh tables: primitive offset, node base, node count
+    const uint32_t n_before = c->count[2], n_new = plan.after[2] - n_before;
+    std::vector<uint32_t> rows[3];
+    for (std::vector<uint32_t>& r : rows) r.reserve(n_new);
+    for (const hk_mesh_index& x : plan.slices) {
+        rows[0].insert(rows[0].end(), x.node[1], x.primitive);
+        rows[1].insert(rows[1].end(), x.node[1], x.node[0]);
+        rows[2].insert(rows[2].end(), x.node[1], x.node[1]);
+    }
+    for (size_t k = 0; k < 3; ++k)
+        HK_HIP(c, hipMemcpyAsync(c->blas_aux + k * c->aux_stride + n_before, rows[k].data(), (size_t)n_new * 4,
+                                 hipMemcpyHostToDevice, st));
+    MeshAddArgs A;
+    MeshUpdateArgs& M = A.M;
+    M.table = (const MeshUpdate*)part[0];
+    M.table_by_size = (const MeshUpdate*)part[1];
+    M.n_meshes = mesh_count;
+    M.n_lds = n_lds;
+    M.n_vertices = n_vertices;
+    M.n_shapes = n_shapes;
+    M.positions = (const float*)part[3];
+    M.normals = (const float*)part[4];
+    M.vertices = (hk_vertex*)c->buf[0];
+    M.primitives = (hk_primitive*)c->buf[1];
+    M.blas = (hk_node*)c->buf[2];
+    M.buckets = 6;  // bvh 0.7.1 NUM_BUCKETS (hks_build default)
+    M.shapes = part[7];
+    M.idx = (uint32_t*)part[8];
+    M.segments = part[9];
+    M.levels = (uint32_t*)part[10];
+    A.sources = (const MeshSource*)part[2];
+    A.uvs = (const float*)part[5];
+    A.indices = (const uint32_t*)part[6];
+    timed(c, "add_meshes", st, [&] {
+        launch_mesh_add(A, st);
+        refresh_blas_derivatives(c, st, plan.after[2]);  // over the whole array, as hk_update_meshes
+    });
+    HK_HIP(c, hipGetLastError());
+    std::vector<uint32_t> levels(mesh_count);
+    HK_HIP(c, hipMemcpyAsync(levels.data(), part[10], levels.size() * 4, hipMemcpyDeviceToHost, st));
+    HK_HIP(c, hipStreamSynchronize(st));
+    // the counts, the registry and the G-buffer reuse generation move together, once the device is done
+    for (int i = 0; i < 3; ++i) c->count[i] = plan.after[i];
+    c->gen++;
+    for (uint32_t k = 0; k < mesh_count; ++k) {
+        c->meshes.push_back(hk_ctx::MeshSlice{plan.slices[k], plan.vertex_need[k], levels[k], 0u});
+        slices[k] = plan.slices[k];
+    }
+    return HK_OK;
+}
+
+int hk_scene_capacity(const hk_ctx* c, uint32_t capacity[9])
+{
+    if (!c || !capacity) return HK_ERR_INVALID;
+    if (!c->has_scene) return HK_ERR_STATE;
+    for (int i = 0; i < 9; ++i) capacity[i] = (uint32_t)c->cap[i];
     return HK_OK;
 }
 

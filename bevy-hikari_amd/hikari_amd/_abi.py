@@ -72,6 +72,12 @@ class hk_mesh_update(C.Structure):
                 ("normals", C.c_void_p)]
 
 
+class hk_mesh_desc(C.Structure):
+    """include/hikari_amd.h hk_mesh_desc (one new mesh of hk_add_meshes, as hks_add_mesh takes it)."""
+    _fields_ = [("positions", C.c_void_p), ("normals", C.c_void_p), ("uvs", C.c_void_p), ("vertex_count", C.c_uint32),
+                ("indices", C.c_void_p), ("index_count", C.c_uint32), ("topology", C.c_uint32)]
+
+
 HK_INSTANCE_NEW = 0xFFFFFFFF
 
 
@@ -217,6 +223,11 @@ def lib() -> C.CDLL:
         "hk_update_meshes": (i32, [vp, C.POINTER(hk_mesh_update), u32, vp, vp, u32, vp]),
         "hk_set_instances": (i32, [vp, C.POINTER(hk_instance_desc), vp, vp, u32, vp, vp]),
         "hk_scene_counts": (i32, [vp, C.POINTER(u32)]),
+        "hk_add_meshes": (i32, [vp, C.POINTER(hk_mesh_desc), u32, C.POINTER(hk_mesh_index), vp]),
+        "hk_add_meshes_counts": (i32, [C.POINTER(u32), C.POINTER(hk_mesh_desc), u32, C.POINTER(hk_mesh_index),
+                                       C.POINTER(u32)]),
+        "hk_add_meshes_counts_error": (C.c_char_p, []),
+        "hk_scene_capacity": (i32, [vp, C.POINTER(u32)]),
         "hk_scene_shared_transform": (i32, [vp, C.POINTER(i32)]),
         "hk_instance_set_counts": (i32, [C.POINTER(hk_scene_desc), C.POINTER(hk_instance_desc), u32, vp, C.POINTER(u32)]),
         "hk_read_scene_array": (i32, [vp, i32, vp, C.c_size_t]),
@@ -273,6 +284,7 @@ EXPORTED_SYMBOLS = [
     "hk_trace", "hk_selftest_f16", "hk_selftest_div", "hk_selftest_rcp", "hk_selftest_count", "hk_selftest_texture", "hk_selftest_math", "hks_create", "hks_destroy", "hks_last_error", "hks_add_mesh", "hks_add_material",
     "hks_add_instance", "hks_build", "hks_get_desc", "hk_scene_shared_transform", "hks_shared_transform",
     "hks_instance_bounds", "hks_screen_bounds", "hk_tile_skip_info",
+    "hk_add_meshes", "hk_add_meshes_counts", "hk_add_meshes_counts_error", "hk_scene_capacity",
 ]
 
 

@@ -116,6 +116,37 @@ def instance_set_counts(uploaded, scene: Scene, materials: bool = False):
     return list(out)
 
 
+def _mesh_descs(meshes):
+    """(ctypes array of hk_mesh_desc, the numpy arrays it points into) for a list of Mesh objects, as Scene.build hands
+    them to hks_add_mesh.  A mesh without an attribute gets a NULL there (hk_add_meshes refuses it)."""
+    out = (_abi.hk_mesh_desc * max(1, len(meshes)))()
+    keep = []
+    for d, m in zip(out, meshes):
+        p, n, u = (None if a is None else np.ascontiguousarray(a, np.float32) for a in (m.positions, m.normals, m.uvs))
+        ix = None if m.indices is None else np.ascontiguousarray(m.indices, np.uint32).reshape(-1)
+        keep += [p, n, u, ix]
+        d.positions, d.normals, d.uvs = (None if a is None else a.ctypes.data for a in (p, n, u))
+        d.vertex_count = 0 if p is None else len(p.reshape(-1, 3))
+        d.indices = None if ix is None else ix.ctypes.data
+        d.index_count = 0 if ix is None else len(ix)
+        d.topology = int(m.topology)
+    return out, keep
+
+
+def add_meshes_counts(before, meshes):
+    """(slices, counts after) of hk_add_meshes_counts: the (vertex, primitive, node0, node_count) slices `meshes` (Mesh
+    objects) take when appended to arrays of the nine element counts `before`, and the nine counts after.  Host
+    arithmetic only: needs no device."""
+    L = _abi.lib()
+    descs, keep = _mesh_descs(meshes)
+    slices = (_abi.hk_mesh_index * max(1, len(meshes)))()
+    after = (C.c_uint32 * 9)()
+    rc = L.hk_add_meshes_counts((C.c_uint32 * 9)(*before), descs, len(meshes), slices, after)
+    if rc != 0:
+        raise _abi.HikariError(f"hk_add_meshes_counts failed ({rc}): {L.hk_add_meshes_counts_error().decode()}")
+    return [(s.vertex, s.primitive, s.node[0], s.node[1]) for s in slices[:len(meshes)]], list(after)
+
+
 class HikariRenderer:
     """A camera's integrator context (hk_ctx)."""
 
@@ -325,6 +356,23 @@ class HikariRenderer:
         """The current element counts of the nine scene arrays, hk_scene_desc order (hk_scene_counts)."""
         out = (C.c_uint32 * 9)()
         _check(self.ctx, self._L.hk_scene_counts(self.ctx, out), "hk_scene_counts")
+        return list(out)
+
+    def add_meshes(self, meshes, stream=None) -> list:
+        """Mesh assets that arrive after the upload (hk_add_meshes): the GPU appends the vertices and primitives of
+        each hikari_amd.Mesh in `meshes` to the scene's arrays and builds its BLAS; the instance set and the picture
+        stay.  Returns each mesh's slice (vertex, primitive, node0, node_count), which set_instances then spawns: a
+        Scene whose mesh list is the uploaded one followed by these gives the same slices (Scene.mesh_index)."""
+        descs, keep = _mesh_descs(meshes)
+        slices = (_abi.hk_mesh_index * max(1, len(meshes)))()
+        _check(self.ctx, self._L.hk_add_meshes(self.ctx, descs, len(meshes), slices, _stream(stream)), "hk_add_meshes")
+        return [(s.vertex, s.primitive, s.node[0], s.node[1]) for s in slices[:len(meshes)]]
+
+    def scene_capacity(self) -> list:
+        """The element capacities of the nine scene arrays, hk_scene_desc order (hk_scene_capacity): what each holds
+        before set_instances or add_meshes has to allocate."""
+        out = (C.c_uint32 * 9)()
+        _check(self.ctx, self._L.hk_scene_capacity(self.ctx, out), "hk_scene_capacity")
         return list(out)
 
     def scene_shared_transform(self) -> bool:
@@ -587,6 +635,10 @@ class HikariPlugin:
     def update_meshes(self, scene: Scene, mesh_ids, models=None, local_aabbs=None, stream=None) -> None:
         """`prepare_mesh_assets` for modified meshes of unchanged topology (HikariRenderer.update_meshes)."""
         self.renderer.update_meshes(scene, mesh_ids, models, local_aabbs, stream)
+
+    def add_meshes(self, meshes, stream=None) -> list:
+        """HikariRenderer.add_meshes: mesh assets created after the scene was uploaded (AssetEvent::Created)."""
+        return self.renderer.add_meshes(meshes, stream=stream)
 
     def set_instances(self, scene: Scene, previous=None, materials: bool = False, stream=None) -> None:
         """`prepare_instances` for spawned, despawned, hidden or re-materialed entities (HikariRenderer.set_instances)."""

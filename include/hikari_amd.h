@@ -338,6 +338,55 @@ int hk_set_instances(hk_ctx* ctx, const hk_instance_desc* set, const float* mode
                      uint32_t count, const hk_material* materials, void* stream);
 /* the current element counts of the nine scene arrays, hk_scene_desc order */
 int hk_scene_counts(const hk_ctx* ctx, uint32_t counts[9]);
+
+/* Appended meshes: what the reference does for `AssetEvent::Created` (mesh.rs:77-166
+ * prepare_mesh_assets runs GpuMesh::try_from on a mesh asset that arrives after the scene was uploaded, as under
+ * asynchronous glTF loading, and concatenates it behind the others, mesh.rs:140-163), ON THE GPU and in place.  After
+ * hk_add_meshes the vertices, primitives and asset nodes (arrays 0, 1, 2) are what hks_build + hk_scene_upload give
+ * when the same meshes are added with hks_add_mesh, in this order, after the meshes already there (the reference's
+ * order is its BTreeMap's; the caller supplies it, as at upload).  Every earlier slice keeps its bytes and offsets
+ * (node indices are mesh-relative); arrays 3-8, the instance set and the picture are untouched.  The device writes each
+ * hk_vertex and hk_primitive whole from the attribute streams, folds the triangles' shape boxes with the host's
+ * std::fmin / std::fmax and builds each BLAS with the host builder's exact operations (as hk_update_meshes).
+ * slices[k]: mesh k's appended slice; a mesh of k triangles takes 3k - 2 nodes.  Each new mesh is a known slice at
+ * once, carried by no instance: hk_set_instances spawns it and hk_update_meshes deforms it like any other, its leaves
+ * carry their triangle boxes and it has its entries in the device-only derivatives, which are refreshed over the
+ * whole array.  The G-buffer walk's stack bound does not move until an instance carries the mesh.  Waits for the
+ * stream once (the BLAS depths).
+ *   Capacity: arrays 0-2 and their device-only derivatives keep a capacity beside their count (hk_scene_capacity); a
+ * call allocates only for a count above its capacity, and then max(count, 1.5 x capacity), the contents kept.  Nothing
+ * shrinks before hk_scene_upload or hk_destroy, which reset them.  REMOVAL IS NOT OFFERED: a mesh no instance carries
+ * keeps its bytes until the next hk_scene_upload.
+ *   HK_ERR_INVALID with a message naming hks_add_mesh's error, decided on the host before any device work, the context
+ * unchanged and usable: a null list or null `slices`; mesh_count == 0; positions / normals / uvs missing
+ * (MissingAttributePosition / MissingAttributeNormal / MissingAttributeUV); an index >= vertex_count; a topology
+ * that is neither, or a list whose index count is no multiple of 3 (IncompatiblePrimitiveTopology); fewer than 3
+ * indices (NoPrimitive); totals past 0x40000000 vertices, primitives or nodes.  HK_ERR_STATE without a scene.
+ *   HK_ERR_HIP "out of device memory": every allocation the call needs is made before anything changes, so the
+ * context is as it was.  Any other HK_ERR_HIP (a copy, launch or wait that failed after that): the counts and the
+ * known slices have not moved, they change together after the wait, but the arrays' contents are undefined; the
+ * context is then good for hk_scene_upload and hk_destroy only. */
+typedef struct hk_mesh_desc {      /* a Bevy `Mesh` as hks_add_mesh takes it */
+    const float* positions;       /* vertex_count x 3 */
+    const float* normals;         /* vertex_count x 3 */
+    const float* uvs;             /* vertex_count x 2 */
+    uint32_t vertex_count;
+    const uint32_t* indices;      /* NULL: 0 .. vertex_count-1 */
+    uint32_t index_count;         /* ignored when indices is NULL */
+    uint32_t topology;            /* HKS_TRIANGLE_LIST (0) / HKS_TRIANGLE_STRIP (1), hikari_scene.h */
+} hk_mesh_desc;
+int hk_add_meshes(hk_ctx* ctx, const hk_mesh_desc* meshes, uint32_t mesh_count, hk_mesh_index* slices, void* stream);
+/* The host arithmetic hk_add_meshes sizes its allocations and launches with (needs no device or context): the slices
+ * of `meshes` appended to arrays of `before` elements and the nine counts after (only [0..2] change).  The same
+ * refusals with the same codes as hk_add_meshes; their message is what hk_add_meshes_counts_error() returns on the
+ * calling thread until its next hk_add_meshes_counts (an empty string after a success).  `after` may be NULL. */
+int hk_add_meshes_counts(const uint32_t before[9], const hk_mesh_desc* meshes, uint32_t mesh_count,
+                         hk_mesh_index* slices, uint32_t after[9]);
+const char* hk_add_meshes_counts_error(void);
+/* the element capacities beside hk_scene_counts' counts, hk_scene_desc order: what each array holds before a call
+ * has to allocate (hk_set_instances: 3, 4, 5, 7, 8; hk_add_meshes: 0, 1, 2; array 6 never grows).  HK_ERR_STATE
+ * without a scene. */
+int hk_scene_capacity(const hk_ctx* ctx, uint32_t capacity[9]);
 /* *shared = 1 when every instance of the current scene carries the same transform, bit for bit (hikari_scene.h
  * hks_shared_transform over the records' inverse_transpose_model at hk_scene_upload, over the models given to
  * hk_update_instances / hk_update_meshes / hk_set_instances after them), 0 otherwise.  It does not depend on option
