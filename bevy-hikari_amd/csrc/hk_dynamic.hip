@@ -1,5 +1,5 @@
 // hk_dynamic.hip — dynamic instances, deforming meshes, changed instance sets
-//  and appended meshes on the device.
+// (DESIGN §0 f8), appended meshes and new mesh lists on the device.
 //
 // The reference re-runs `prepare_instances` on the CPU whenever a transform changes
 // (instance.rs:284-437: instance records with world AABBs and inverse-transpose models, the
@@ -601,6 +601,53 @@ __global__ __launch_bounds__(256) void k_assemble_meshes(const MeshUpdate* tab, 
     shapes[j] = BBox{{mn[0], mn[1], mn[2]}, {mx[0], mx[1], mx[2]}};
 }
 
+// ---- a new mesh asset list (mesh.rs:89-92, 123-126 AssetEvent::Removed, mesh.rs:140-163 the three buffers rebuilt in
+// the BTreeMap's order).  The kept meshes' vertices, primitives and asset nodes gathered out of place
+// into their slices of the new layout: one thread per 16-byte chunk of the destination arrays (a vertex is 2 chunks, a
+// primitive 3, a node 2), the vertices' chunks first, then the primitives', then the nodes'.  A thread finds its list
+// entry by mesh_of's search over the destination starts, which ascend, and does one 16-byte load and one 16-byte
+// store; consecutive lanes read and write consecutive addresses inside a slice.  The bytes move verbatim: vertex and
+// node indices are mesh-relative.  A new mesh's chunks are left to k_assemble_meshes and k_build_mesh_bvh.  The thread
+// of a node's first chunk, kept or new, also writes the node's three words of the per-node mesh tables (primitive
+// offset, node base, node count) at `stride`.
+HKD uint32_t move_of(const MeshMove* tab, uint32_t n, uint32_t e, int array)
+{
+    uint32_t lo = 0, hi = n;  // the last entry whose first destination element is <= e
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (tab[mid].dst[array] <= e) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+__global__ __launch_bounds__(256) void k_move_mesh_slices(const MeshMove* tab, uint32_t n_meshes, uint32_t n_vertices,
+                                                          uint32_t n_prims, uint32_t n_nodes, const uint4* src_vertices,
+                                                          const uint4* src_prims, const uint4* src_nodes,
+                                                          uint4* vertices, uint4* prims, uint4* nodes, uint32_t* aux,
+                                                          size_t stride)
+{
+    // (3 x 2^30 primitive chunks pass 32 bits: the chunk index is 64-bit, the table holds elements)
+    uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const uint64_t chunks[3] = {2u * (uint64_t)n_vertices, 3u * (uint64_t)n_prims, 2u * (uint64_t)n_nodes};
+    int array = 0;
+    while (array < 3 && i >= chunks[array]) i -= chunks[array++];
+    if (array == 3) return;
+    const uint32_t per = array == 1 ? 3u : 2u;
+    const uint32_t e = (uint32_t)(i / per), sub = (uint32_t)(i - (uint64_t)e * per);
+    const MeshMove& m = tab[move_of(tab, n_meshes, e, array)];
+    const uint32_t off = e - m.dst[array];
+    if (off >= m.count[array]) return;  // (the entries tile the arrays; never taken)
+    if (array == 2 && sub == 0) {
+        aux[e] = m.dst[1];
+        aux[stride + e] = m.dst[2];
+        aux[2 * stride + e] = m.count[2];
+    }
+    if (m.src[0] == MESH_MOVE_NEW) return;
+    const uint4* from = array == 0 ? src_vertices : array == 1 ? src_prims : src_nodes;
+    uint4* to = array == 0 ? vertices : array == 1 ? prims : nodes;
+    to[i] = from[((uint64_t)m.src[array] + off) * per + sub];
+}
+
 // ---- instance records (instance.rs:284-330; hk_scene.cpp hks_build "instances")
 HKD void transform_point(const float* m, const float* p, float* o)
 {
@@ -981,6 +1028,13 @@ void launch_mesh_add(const MeshAddArgs& A, hipStream_t st)
                        M.n_vertices, M.n_shapes, M.positions, M.normals, A.uvs, A.indices, M.vertices, M.primitives,
                        (BBox*)M.shapes);
     launch_mesh_builds(M, st);
+}
+void launch_mesh_move(const MeshMoveArgs& V, hipStream_t st)
+{
+    const uint64_t chunks = 2u * (uint64_t)V.n_vertices + 3u * (uint64_t)V.n_prims + 2u * (uint64_t)V.n_nodes;
+    hipLaunchKernelGGL(k_move_mesh_slices, dim3((uint32_t)((chunks + 255u) / 256u)), dim3(256), 0, st, V.table, V.n_meshes,
+                       V.n_vertices, V.n_prims, V.n_nodes, (const uint4*)V.src[0], (const uint4*)V.src[1],
+                       (const uint4*)V.src[2], (uint4*)V.dst[0], (uint4*)V.dst[1], (uint4*)V.dst[2], V.aux, V.stride);
 }
 uint32_t mesh_lds_shapes() { return BVH_LDS_SHAPES; }
 

@@ -231,6 +231,27 @@ struct MeshAddArgs {
 // vertex and primitive records written whole with the shape boxes (one launch), then launch_mesh_update's builds
 void launch_mesh_add(const MeshAddArgs& A, hipStream_t st);
 
+// A new mesh asset list (hk_set_meshes, hk_dynamic.hip k_move_mesh_slices): one record per list entry in list order,
+// so every dst ascends and the entries tile the new arrays.  All in elements, not 16-byte chunks: 3 x 2^30 primitive
+// chunks pass 32 bits, the kernel multiplies in 64.
+constexpr uint32_t MESH_MOVE_NEW = 0xFFFFFFFFu;
+struct MeshMove {
+    uint32_t dst[3];    // its first vertex, primitive and node in the new arrays
+    uint32_t src[3];    // a kept entry: the same in the current arrays; src[0] == MESH_MOVE_NEW: built by this call
+    uint32_t count[3];  // its vertices, primitives and nodes
+};
+struct MeshMoveArgs {
+    const MeshMove* table;
+    uint32_t n_meshes;
+    uint32_t n_vertices, n_prims, n_nodes;  // the new counts of arrays 0-2
+    const void* src[3];                     // the current arrays 0-2
+    void* dst[3];                           // the new ones: other buffers
+    uint32_t* aux;                          // the per-node mesh tables, three rows of `stride` words
+    size_t stride;
+};
+// the kept entries' bytes gathered into the new arrays and every entry's rows of the per-node mesh tables (one launch)
+void launch_mesh_move(const MeshMoveArgs& V, hipStream_t st);
+
 // Post-process (hk_post.hip over include/hk_post.h)
 struct PostArgs {
     hk_pp_frame frame;

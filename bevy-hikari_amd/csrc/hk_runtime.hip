@@ -381,6 +381,10 @@ struct hk_ctx {
     size_t aux_stride = 0;         // = cap[2]: hk_add_meshes grows the rows with the asset nodes
     void* mesh_scratch = nullptr;
     size_t mesh_bytes = 0;
+    // hk_set_meshes: one spare buffer per array 0-2 (null before the first call), which a call fills and swaps with
+    // buf[i]; spare_cap: its elements
+    void* spare[3] = {};
+    size_t spare_cap[3] = {};
     // GlobalTransformQueue[1] of every instance (transform.rs:32-44): the models as of the previous
     // k_gbuffer, read by its motion vectors; refreshed after a k_gbuffer that followed an update
     float* prev_models = nullptr;
@@ -1127,6 +1131,7 @@ void hk_destroy(hk_ctx* c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     free_targets(c);
     for (int i = 0; i < 9; ++i) release(c->buf[i]);
+    for (int i = 0; i < 3; ++i) release(c->spare[i]);
     release(c->blas_wide);
     release(c->tlas_wide);
     release(c->walk_nodes[0]);
@@ -1301,6 +1306,10 @@ int hk_scene_upload(hk_ctx* c, const hk_scene_desc* d)
     for (int i = 0; i < 9; ++i)
         if (arr[i]->count && !arr[i]->data) return fail(c, HK_ERR_INVALID, "scene array with count but no data");
     HK_HIP(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < 3; ++i) {
+        release(c->spare[i]);
+        c->spare_cap[i] = 0;
+    }
     for (int i = 0; i < 9; ++i) {
         release(c->buf[i]);
         size_t bytes = staged_alloc_bytes(arr[i]->count, elem[i]);
@@ -1445,6 +1454,17 @@ struct SliceReader {
 
 static bool ranges_meet(size_t a, size_t na, size_t b, size_t nb) { return a < b + nb && b < a + na; }
 
+// A slice's shape against the array counts (check_new_slice, and hk_set_meshes for a kept slice); null: it fits
+static const char* slice_shape_error(const hk_mesh_index& x, const uint32_t* count)
+{
+    const uint32_t nc = x.node[1], k = (nc + 2u) / 3u;
+    if (nc == 0 || (nc + 2u) % 3u != 0) return "its BLAS is not 3k - 2 nodes over k primitives";
+    if ((size_t)x.primitive + k > count[1]) return "its primitives reach past the primitive array";
+    if ((size_t)x.node[0] + nc > count[2]) return "its nodes reach past the asset nodes";
+    if (x.vertex >= count[0]) return "its vertices begin past the vertex array";
+    return nullptr;
+}
+
 // A slice no instance has carried so far (hikari_amd.h hk_set_instances "mesh"): its shape against the array counts,
 // against every slice known so far, and what upload records for an instanced mesh.  `why` says what failed.
 static int check_new_slice(const hk_mesh_index& x, const uint32_t* count, const std::vector<hk_ctx::MeshSlice>& known,
@@ -1456,10 +1476,7 @@ static int check_new_slice(const hk_mesh_index& x, const uint32_t* count, const 
         *why = text;
         return HK_ERR_INVALID;
     };
-    if (nc == 0 || (nc + 2u) % 3u != 0) return no("its BLAS is not 3k - 2 nodes over k primitives");
-    if ((size_t)x.primitive + k > count[1]) return no("its primitives reach past the primitive array");
-    if ((size_t)x.node[0] + nc > count[2]) return no("its nodes reach past the asset nodes");
-    if (x.vertex >= count[0]) return no("its vertices begin past the vertex array");
+    if (const char* shape = slice_shape_error(x, count)) return no(shape);
     for (const std::vector<hk_ctx::MeshSlice>* list : {&known, &fresh})
         for (const hk_ctx::MeshSlice& o : *list)
             if (ranges_meet(x.primitive, k, o.index.primitive, (o.index.node[1] + 2u) / 3u) ||
@@ -1491,10 +1508,11 @@ static bool material_emits(const float* e)
 }
 
 // The host arithmetic of a new instance set: every refusal that needs no device, the slices to register and the nine
-// counts after the set (count: the counts before; emissive: 4 floats per material)
+// counts after the set (count: the counts before; emissive: 4 floats per material).  closed: `known` is every slice
+// there is (hk_set_meshes' new list), so an unknown one is refused, not registered.
 static int plan_instance_set(const uint32_t* count, const std::vector<hk_ctx::MeshSlice>& known, const float* emissive,
                              const hk_instance_desc* set, uint32_t n, const SliceReader& rd, SetChange* out,
-                             std::string* why)
+                             std::string* why, bool closed = false)
 {
     if (n == 0) {
         *why = "an empty instance set (hk_scene_upload refuses an empty scene too)";
@@ -1522,6 +1540,10 @@ static int plan_instance_set(const uint32_t* count, const std::vector<hk_ctx::Me
         }
         const std::array<uint32_t, 4> key{d.mesh.vertex, d.mesh.primitive, d.mesh.node[0], d.mesh.node[1]};
         auto it = at.find(key);
+        if (it == at.end() && closed) {
+            *why = who + "its mesh is not in the new list";
+            return HK_ERR_INVALID;
+        }
         if (it == at.end()) {
             hk_ctx::MeshSlice f;
             std::string text;
@@ -1879,25 +1901,31 @@ int hk_update_meshes(hk_ctx* c, const hk_mesh_update* meshes, uint32_t mesh_coun
     return rebuild_instances(c, models, local_aabbs, count, st, &ml);
 }
 
+// the checks hk_set_instances and hk_set_meshes share before the set is planned: the scene's BVHs can be rebuilt, and
+// the previous indices name the set before, each once
+static int set_args_ok(hk_ctx* c, const hk_instance_desc* set, uint32_t count, const char* who)
+{
+    if (c->count[5] != 3u * c->count[4] - 2u || (c->count[8] && c->count[7] != 3u * c->count[8] - 2u))
+        return fail(c, HK_ERR_STATE, "scene BVHs are not bvh-0.7.1 flattened (3n - 2 nodes); cannot rebuild");
+    std::vector<bool> taken(c->count[4], false);
+    for (uint32_t i = 0; i < count; ++i) {
+        const uint32_t p = set[i].previous;
+        if (p == HK_INSTANCE_NEW) continue;
+        const std::string at = std::string(who) + ": instance " + std::to_string(i);
+        if (p >= c->count[4]) return fail(c, HK_ERR_INVALID, at + ": previous is not an index of the set before");
+        if (taken[p]) return fail(c, HK_ERR_INVALID, at + ": previous is used twice");
+        taken[p] = true;
+    }
+    return HK_OK;
+}
+
 int hk_set_instances(hk_ctx* c, const hk_instance_desc* set, const float* models, const float* local_aabbs,
                      uint32_t count, const hk_material* materials, void* stream)
 {
     if (!c) return HK_ERR_INVALID;
     if (!set || !models || !local_aabbs) return fail(c, HK_ERR_INVALID, "hk_set_instances: null pointer");
     if (!c->has_scene) return fail(c, HK_ERR_STATE, "no scene uploaded (hk_scene_upload)");
-    if (c->count[5] != 3u * c->count[4] - 2u || (c->count[8] && c->count[7] != 3u * c->count[8] - 2u))
-        return fail(c, HK_ERR_STATE, "scene BVHs are not bvh-0.7.1 flattened (3n - 2 nodes); cannot rebuild");
-    // the previous indices against the set before
-    std::vector<bool> taken(c->count[4], false);
-    for (uint32_t i = 0; i < count; ++i) {
-        const uint32_t p = set[i].previous;
-        if (p == HK_INSTANCE_NEW) continue;
-        if (p >= c->count[4])
-            return fail(c, HK_ERR_INVALID, "hk_set_instances: instance " + std::to_string(i) + ": previous is not an index of the set before");
-        if (taken[p])
-            return fail(c, HK_ERR_INVALID, "hk_set_instances: instance " + std::to_string(i) + ": previous is used twice");
-        taken[p] = true;
-    }
+    HK_TRY(set_args_ok(c, set, count, "hk_set_instances"));
     (void)hipSetDevice(c->device);
     std::vector<float> emissive;
     if (materials) {
@@ -1933,6 +1961,38 @@ struct MeshAddPlan {
 };
 constexpr uint64_t MESH_TOTAL_MAX = 0x40000000u;  // hk_update_meshes' bound on vertices and primitives
 
+// hks_add_mesh's checks of one new mesh, in its order: null when it passes, with its triangles and the vertices its
+// indices reach (plan_add_meshes and plan_set_meshes)
+static const char* new_mesh_error(const hk_mesh_desc& m, uint32_t* tris_out, uint32_t* need_out)
+{
+    if (!m.positions) return "MissingAttributePosition";
+    if (!m.normals) return "MissingAttributeNormal";
+    if (!m.uvs) return "MissingAttributeUV";
+    const uint32_t ni = m.indices ? m.index_count : m.vertex_count;
+    uint32_t top = 0;
+    if (m.indices) {
+        for (uint32_t i = 0; i < ni; ++i) {
+            if (m.indices[i] >= m.vertex_count) return "index out of range";
+            top = std::max(top, m.indices[i]);
+        }
+    } else if (ni) {
+        top = ni - 1u;
+    }
+    uint32_t tris = 0;
+    if (m.topology == HKS_TRIANGLE_LIST) {
+        if (ni % 3u != 0) return "IncompatiblePrimitiveTopology";
+        tris = ni / 3u;
+    } else if (m.topology == HKS_TRIANGLE_STRIP) {
+        tris = ni >= 3u ? ni - 2u : 0u;
+    } else {
+        return "IncompatiblePrimitiveTopology";
+    }
+    if (tris == 0) return "NoPrimitive";
+    *tris_out = tris;
+    *need_out = top + 1u;
+    return nullptr;
+}
+
 static int plan_add_meshes(const uint32_t* before, const hk_mesh_desc* meshes, uint32_t n, MeshAddPlan* out,
                            std::string* why)
 {
@@ -1949,39 +2009,17 @@ static int plan_add_meshes(const uint32_t* before, const hk_mesh_desc* meshes, u
     for (uint32_t k = 0; k < n; ++k) {
         const hk_mesh_desc& m = meshes[k];
         const std::string who = "mesh " + std::to_string(k) + ": ";
-        // hks_add_mesh's checks, in its order
-        if (!m.positions) return no(who + "MissingAttributePosition");
-        if (!m.normals) return no(who + "MissingAttributeNormal");
-        if (!m.uvs) return no(who + "MissingAttributeUV");
-        const uint32_t ni = m.indices ? m.index_count : m.vertex_count;
-        uint32_t top = 0;
-        if (m.indices) {
-            for (uint32_t i = 0; i < ni; ++i) {
-                if (m.indices[i] >= m.vertex_count) return no(who + "index out of range");
-                top = std::max(top, m.indices[i]);
-            }
-        } else if (ni) {
-            top = ni - 1u;
-        }
-        uint32_t tris = 0;
-        if (m.topology == HKS_TRIANGLE_LIST) {
-            if (ni % 3u != 0) return no(who + "IncompatiblePrimitiveTopology");
-            tris = ni / 3u;
-        } else if (m.topology == HKS_TRIANGLE_STRIP) {
-            tris = ni >= 3u ? ni - 2u : 0u;
-        } else {
-            return no(who + "IncompatiblePrimitiveTopology");
-        }
-        if (tris == 0) return no(who + "NoPrimitive");
+        uint32_t tris = 0, need = 0;
+        if (const char* text = new_mesh_error(m, &tris, &need)) return no(who + text);
         out->slices[k] = hk_mesh_index{(uint32_t)at[0], (uint32_t)at[1], {(uint32_t)at[2], 3u * tris - 2u}};
         out->tris[k] = tris;
-        out->vertex_need[k] = top + 1u;
+        out->vertex_need[k] = need;
         at[0] += m.vertex_count;
         at[1] += tris;
         at[2] += 3u * (uint64_t)tris - 2u;
         out->n_vertices += m.vertex_count;
         out->n_shapes += tris;
-        if (m.indices) out->n_indices += ni;
+        if (m.indices) out->n_indices += m.index_count;
         if (at[0] > MESH_TOTAL_MAX || at[1] > MESH_TOTAL_MAX || at[2] > MESH_TOTAL_MAX || out->n_indices > MESH_TOTAL_MAX)
             return no("too many vertices, primitives or nodes");
     }
@@ -2013,6 +2051,108 @@ int hk_add_meshes_counts(const uint32_t before[9], const hk_mesh_desc* meshes, u
     return HK_OK;
 }
 
+// The new meshes of hk_add_meshes and hk_set_meshes on their way to the device: the tables in list order and by size,
+// where each mesh's indices lie, and the scratch they, the attribute and index streams and the builds' shape boxes,
+// indices, segments and levels take (sz: one entry per part; the last is the caller's own, `extra` bytes).
+struct MeshStaging {
+    std::vector<MeshUpdate> tab, by_size;
+    std::vector<MeshSource> sources;
+    uint32_t n_lds = 0, n_vertices = 0, n_shapes = 0, n_indices = 0;
+    static constexpr int PARTS = 12;
+    size_t sz[PARTS] = {};
+    size_t total = 0;
+};
+
+// meshes[k] goes to slices[k] with tris[k] triangles
+static void plan_mesh_staging(const std::vector<const hk_mesh_desc*>& meshes, const hk_mesh_index* slices,
+                              const uint32_t* tris, uint64_t n_vertices, uint64_t n_shapes, uint64_t n_indices,
+                              size_t extra, MeshStaging* S)
+{
+    const uint32_t n = (uint32_t)meshes.size();
+    S->tab.resize(n);
+    S->sources.resize(n);
+    S->n_vertices = (uint32_t)n_vertices;
+    S->n_shapes = (uint32_t)n_shapes;
+    S->n_indices = (uint32_t)n_indices;
+    uint32_t v0 = 0, s0 = 0, i0 = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+        const hk_mesh_index& x = slices[k];
+        const hk_mesh_desc& m = *meshes[k];
+        S->tab[k] = MeshUpdate{x.vertex, m.vertex_count, x.primitive, tris[k], x.node[0], v0, s0, k, 1u};
+        S->sources[k] = MeshSource{m.indices ? i0 : MESH_NO_INDICES, m.topology == HKS_TRIANGLE_STRIP ? 1u : 0u};
+        v0 += m.vertex_count;
+        s0 += tris[k];
+        if (m.indices) i0 += m.index_count;
+        S->n_lds += tris[k] <= mesh_lds_shapes() ? 1u : 0u;
+    }
+    for (int big = 0; big < 2; ++big)
+        for (const MeshUpdate& m : S->tab)
+            if ((m.shapes > mesh_lds_shapes()) == (big == 1)) S->by_size.push_back(m);
+    auto align = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t nv = S->n_vertices, ns = S->n_shapes;
+    const size_t sz[MeshStaging::PARTS] = {
+        align((size_t)n * sizeof(MeshUpdate)), align((size_t)n * sizeof(MeshUpdate)), align((size_t)n * sizeof(MeshSource)),
+        align(nv * 12), align(nv * 12), align(nv * 8), align((size_t)(S->n_indices ? S->n_indices : 1) * 4),
+        align(ns * 24), align(ns * 8), align(ns * 24), align((size_t)n * 4), align(extra)};
+    S->total = 0;
+    for (int k = 0; k < MeshStaging::PARTS; ++k) S->total += (S->sz[k] = sz[k]);
+}
+
+// The tables and streams copied into c->mesh_scratch (at least S.total bytes) on `st`, and the launch arguments over
+// them, the destinations c->buf[0..2].  *extra: the caller's part.
+static int enqueue_mesh_staging(hk_ctx* c, const std::vector<const hk_mesh_desc*>& meshes, const MeshStaging& S,
+                                hipStream_t st, MeshAddArgs* A, char** extra)
+{
+    char* part[MeshStaging::PARTS];
+    {
+        char* p = (char*)c->mesh_scratch;
+        for (int k = 0; k < MeshStaging::PARTS; ++k) {
+            part[k] = p;
+            p += S.sz[k];
+        }
+    }
+    const size_t n = meshes.size();
+    if (n) {
+        HK_HIP(c, hipMemcpyAsync(part[0], S.tab.data(), n * sizeof(MeshUpdate), hipMemcpyHostToDevice, st));
+        HK_HIP(c, hipMemcpyAsync(part[1], S.by_size.data(), n * sizeof(MeshUpdate), hipMemcpyHostToDevice, st));
+        HK_HIP(c, hipMemcpyAsync(part[2], S.sources.data(), n * sizeof(MeshSource), hipMemcpyHostToDevice, st));
+    }
+    for (size_t k = 0; k < n; ++k) {
+        const hk_mesh_desc& m = *meshes[k];
+        const size_t v0 = S.tab[k].vertex0, nv = m.vertex_count;
+        if (nv) {
+            HK_HIP(c, hipMemcpyAsync(part[3] + v0 * 12, m.positions, nv * 12, hipMemcpyHostToDevice, st));
+            HK_HIP(c, hipMemcpyAsync(part[4] + v0 * 12, m.normals, nv * 12, hipMemcpyHostToDevice, st));
+            HK_HIP(c, hipMemcpyAsync(part[5] + v0 * 8, m.uvs, nv * 8, hipMemcpyHostToDevice, st));
+        }
+        if (m.indices)
+            HK_HIP(c, hipMemcpyAsync(part[6] + (size_t)S.sources[k].index0 * 4, m.indices, (size_t)m.index_count * 4,
+                                     hipMemcpyHostToDevice, st));
+    }
+    MeshUpdateArgs& M = A->M;
+    M.table = (const MeshUpdate*)part[0];
+    M.table_by_size = (const MeshUpdate*)part[1];
+    M.n_meshes = (uint32_t)n;
+    M.n_lds = S.n_lds;
+    M.n_vertices = S.n_vertices;
+    M.n_shapes = S.n_shapes;
+    M.positions = (const float*)part[3];
+    M.normals = (const float*)part[4];
+    M.vertices = (hk_vertex*)c->buf[0];
+    M.primitives = (hk_primitive*)c->buf[1];
+    M.blas = (hk_node*)c->buf[2];
+    M.buckets = 6;  // bvh 0.7.1 NUM_BUCKETS (hks_build default)
+    M.shapes = part[7];
+    M.idx = (uint32_t*)part[8];
+    M.segments = part[9];
+    M.levels = (uint32_t*)part[10];
+    A->sources = (const MeshSource*)part[2];
+    A->uvs = (const float*)part[5];
+    A->indices = (const uint32_t*)part[6];
+    if (extra) *extra = part[11];
+    return HK_OK;
+}
+
 int hk_add_meshes(hk_ctx* c, const hk_mesh_desc* meshes, uint32_t mesh_count, hk_mesh_index* slices, void* stream)
 {
     if (!c) return HK_ERR_INVALID;
@@ -2024,42 +2164,15 @@ int hk_add_meshes(hk_ctx* c, const hk_mesh_desc* meshes, uint32_t mesh_count, hk
         const int rc = plan_add_meshes(c->count, meshes, mesh_count, &plan, &why);
         if (rc != HK_OK) return fail(c, rc, "hk_add_meshes: " + why);
     }
-    const uint32_t n_vertices = (uint32_t)plan.n_vertices, n_shapes = (uint32_t)plan.n_shapes;
-    const uint32_t n_indices = (uint32_t)plan.n_indices;
     (void)hipSetDevice(c->device);
     hipStream_t st = pick(c, stream);
     HK_TRY(c->sch.gb_join(st));
     HK_TRY(c->sch.gb_serialize(false));
-    // the tables: the meshes in list order and by size, and where each mesh's indices lie
-    std::vector<MeshUpdate> tab(mesh_count), by_size;
-    std::vector<MeshSource> sources(mesh_count);
-    uint32_t n_lds = 0;
-    {
-        uint32_t v0 = 0, s0 = 0, i0 = 0;
-        for (uint32_t k = 0; k < mesh_count; ++k) {
-            const hk_mesh_index& x = plan.slices[k];
-            tab[k] = MeshUpdate{x.vertex, meshes[k].vertex_count, x.primitive, plan.tris[k], x.node[0], v0, s0, k, 1u};
-            sources[k] = MeshSource{meshes[k].indices ? i0 : MESH_NO_INDICES, meshes[k].topology == HKS_TRIANGLE_STRIP ? 1u : 0u};
-            v0 += meshes[k].vertex_count;
-            s0 += plan.tris[k];
-            if (meshes[k].indices) i0 += meshes[k].index_count;
-            n_lds += plan.tris[k] <= mesh_lds_shapes() ? 1u : 0u;
-        }
-        for (int big = 0; big < 2; ++big)
-            for (const MeshUpdate& m : tab)
-                if ((m.shapes > mesh_lds_shapes()) == (big == 1)) by_size.push_back(m);
-    }
-    // scratch: the tables, the attribute and index streams, and the builds' shape boxes, indices, segments and levels
-    auto align = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t sz[] = {align((size_t)mesh_count * sizeof(MeshUpdate)), align((size_t)mesh_count * sizeof(MeshUpdate)),
-                         align((size_t)mesh_count * sizeof(MeshSource)),
-                         align((size_t)n_vertices * 12), align((size_t)n_vertices * 12), align((size_t)n_vertices * 8),
-                         align((size_t)(n_indices ? n_indices : 1) * 4),
-                         align((size_t)n_shapes * 24),   align((size_t)n_shapes * 8),
-                         align((size_t)n_shapes * 24),   align((size_t)mesh_count * 4)};
-    constexpr int PARTS = sizeof(sz) / sizeof(sz[0]);
-    size_t total = 0;
-    for (size_t b : sz) total += b;
+    std::vector<const hk_mesh_desc*> list(mesh_count);
+    for (uint32_t k = 0; k < mesh_count; ++k) list[k] = meshes + k;
+    MeshStaging stage;
+    plan_mesh_staging(list, plan.slices.data(), plan.tris.data(), plan.n_vertices, plan.n_shapes, plan.n_indices, 0, &stage);
+    const size_t total = stage.total;
     // Room (hikari_amd.h hk_add_meshes "Capacity").  First every allocation the call needs, with the context untouched:
     // a failure here frees them and leaves the context as it was.  Then the grown arrays take their contents, copied on
     // the stream, and a zeroed tail; the buffers they leave are freed after the call's one wait, or on the way out.
@@ -2144,28 +2257,8 @@ int hk_add_meshes(hk_ctx* c, const hk_mesh_desc* meshes, uint32_t mesh_count, hk
             HK_HIP(c, hipMemcpyAsync((uint32_t*)n_aux + k * cap[2], aux_was + k * stride_was, have * 4,
                                      hipMemcpyDeviceToDevice, st));
     }
-    char* part[PARTS];
-    {
-        char* p = (char*)c->mesh_scratch;
-        for (int k = 0; k < PARTS; ++k) {
-            part[k] = p;
-            p += sz[k];
-        }
-    }
-    HK_HIP(c, hipMemcpyAsync(part[0], tab.data(), tab.size() * sizeof(MeshUpdate), hipMemcpyHostToDevice, st));
-    HK_HIP(c, hipMemcpyAsync(part[1], by_size.data(), by_size.size() * sizeof(MeshUpdate), hipMemcpyHostToDevice, st));
-    HK_HIP(c, hipMemcpyAsync(part[2], sources.data(), sources.size() * sizeof(MeshSource), hipMemcpyHostToDevice, st));
-    for (uint32_t k = 0; k < mesh_count; ++k) {
-        const size_t v0 = tab[k].vertex0, nv = meshes[k].vertex_count;
-        if (nv) {
-            HK_HIP(c, hipMemcpyAsync(part[3] + v0 * 12, meshes[k].positions, nv * 12, hipMemcpyHostToDevice, st));
-            HK_HIP(c, hipMemcpyAsync(part[4] + v0 * 12, meshes[k].normals, nv * 12, hipMemcpyHostToDevice, st));
-            HK_HIP(c, hipMemcpyAsync(part[5] + v0 * 8, meshes[k].uvs, nv * 8, hipMemcpyHostToDevice, st));
-        }
-        if (meshes[k].indices)
-            HK_HIP(c, hipMemcpyAsync(part[6] + (size_t)sources[k].index0 * 4, meshes[k].indices,
-                                     (size_t)meshes[k].index_count * 4, hipMemcpyHostToDevice, st));
-    }
+    MeshAddArgs A;
+    HK_TRY(enqueue_mesh_staging(c, list, stage, st, &A, nullptr));
     // the new meshes' rows of the per-node mesh tables: primitive offset, node base, node count
     const uint32_t n_before = c->count[2], n_new = plan.after[2] - n_before;
     std::vector<uint32_t> rows[3];
@@ -2178,34 +2271,13 @@ int hk_add_meshes(hk_ctx* c, const hk_mesh_desc* meshes, uint32_t mesh_count, hk
     for (size_t k = 0; k < 3; ++k)
         HK_HIP(c, hipMemcpyAsync(c->blas_aux + k * c->aux_stride + n_before, rows[k].data(), (size_t)n_new * 4,
                                  hipMemcpyHostToDevice, st));
-    MeshAddArgs A;
-    MeshUpdateArgs& M = A.M;
-    M.table = (const MeshUpdate*)part[0];
-    M.table_by_size = (const MeshUpdate*)part[1];
-    M.n_meshes = mesh_count;
-    M.n_lds = n_lds;
-    M.n_vertices = n_vertices;
-    M.n_shapes = n_shapes;
-    M.positions = (const float*)part[3];
-    M.normals = (const float*)part[4];
-    M.vertices = (hk_vertex*)c->buf[0];
-    M.primitives = (hk_primitive*)c->buf[1];
-    M.blas = (hk_node*)c->buf[2];
-    M.buckets = 6;  // bvh 0.7.1 NUM_BUCKETS (hks_build default)
-    M.shapes = part[7];
-    M.idx = (uint32_t*)part[8];
-    M.segments = part[9];
-    M.levels = (uint32_t*)part[10];
-    A.sources = (const MeshSource*)part[2];
-    A.uvs = (const float*)part[5];
-    A.indices = (const uint32_t*)part[6];
     timed(c, "add_meshes", st, [&] {
         launch_mesh_add(A, st);
         refresh_blas_derivatives(c, st, plan.after[2]);  // over the whole array, as hk_update_meshes
     });
     HK_HIP(c, hipGetLastError());
     std::vector<uint32_t> levels(mesh_count);
-    HK_HIP(c, hipMemcpyAsync(levels.data(), part[10], levels.size() * 4, hipMemcpyDeviceToHost, st));
+    HK_HIP(c, hipMemcpyAsync(levels.data(), A.M.levels, levels.size() * 4, hipMemcpyDeviceToHost, st));
     HK_HIP(c, hipStreamSynchronize(st));
     // the counts, the registry and the G-buffer reuse generation move together, once the device is done
     for (int i = 0; i < 3; ++i) c->count[i] = plan.after[i];
@@ -2215,6 +2287,282 @@ int hk_add_meshes(hk_ctx* c, const hk_mesh_desc* meshes, uint32_t mesh_count, hk
         slices[k] = plan.slices[k];
     }
     return HK_OK;
+}
+
+// ---- hk_set_meshes
+// What hk_set_meshes decides on the host before any device work: every entry's slice in the new layout, the registry
+// after the call (the list; a new entry's depth comes from its build), the new entries apart for the build, and the
+// counts after.
+struct MeshSetPlan {
+    std::vector<hk_mesh_index> slices;
+    std::vector<MeshMove> moves;               // one per entry, list order
+    std::vector<hk_ctx::MeshSlice> registry;   // one per entry, list order
+    std::vector<uint32_t> source_entry;        // the list index of each new entry
+    std::vector<const hk_mesh_desc*> sources;  // the new entries, in list order, with their slices and triangles
+    std::vector<hk_mesh_index> source_slices;
+    std::vector<uint32_t> tris;
+    uint32_t after[9] = {};
+    uint64_t n_vertices = 0, n_shapes = 0, n_indices = 0;  // sums over the new entries
+};
+
+// known / rd: the context's registry and arrays; both null: the context-free arithmetic of hk_set_meshes_counts, which
+// cannot look a kept slice up or read it back and checks it against the counts and the other kept slices alone.
+static int plan_set_meshes(const uint32_t* before, const std::vector<hk_ctx::MeshSlice>* known, const SliceReader* rd,
+                           const hk_mesh_entry* list, uint32_t n, MeshSetPlan* out, std::string* why)
+{
+    auto no = [&](const std::string& text) {
+        *why = text;
+        return HK_ERR_INVALID;
+    };
+    if (!list) return no("null mesh list");
+    if (n == 0) return no("an empty mesh list");
+    out->slices.resize(n);
+    out->moves.resize(n);
+    out->registry.resize(n);
+    struct Kept {
+        hk_mesh_index x;
+        uint32_t vertices;
+    };
+    std::vector<Kept> kept;
+    std::vector<hk_ctx::MeshSlice> fresh;  // the kept slices this call registers
+    uint64_t at[3] = {0, 0, 0};
+    for (uint32_t k = 0; k < n; ++k) {
+        const hk_mesh_entry& e = list[k];
+        const std::string who = "mesh " + std::to_string(k) + ": ";
+        uint32_t tris = 0, need = 0, depth = 0, vertices = 0;
+        MeshMove& mv = out->moves[k];
+        if (e.source) {
+            if (const char* text = new_mesh_error(*e.source, &tris, &need)) return no(who + text);
+            vertices = e.source->vertex_count;
+            mv.src[0] = mv.src[1] = mv.src[2] = MESH_MOVE_NEW;
+            out->source_entry.push_back(k);
+            out->sources.push_back(e.source);
+            out->tris.push_back(tris);
+            out->n_vertices += vertices;
+            out->n_shapes += tris;
+            if (e.source->indices) out->n_indices += e.source->index_count;
+        } else {
+            const hk_mesh_index& x = e.keep;
+            vertices = e.vertex_count;
+            if (const char* text = slice_shape_error(x, before)) return no(who + "kept slice refused: " + text);
+            tris = (x.node[1] + 2u) / 3u;
+            for (const Kept& o : kept)
+                if (std::memcmp(&o.x, &x, sizeof(x)) == 0) return no(who + "the slice is kept twice");
+            if (known) {
+                const hk_ctx::MeshSlice* s = nullptr;
+                for (const hk_ctx::MeshSlice& o : *known)
+                    if (std::memcmp(&o.index, &x, sizeof(x)) == 0) s = &o;
+                hk_ctx::MeshSlice f;
+                if (!s) {
+                    std::string text;
+                    const int rc = check_new_slice(x, before, *known, fresh, *rd, &f, &text);
+                    if (rc != HK_OK) {
+                        *why = who + "kept slice refused: " + text;
+                        return rc;
+                    }
+                    fresh.push_back(f);
+                    s = &f;
+                }
+                if (s->vertex_need == HK_U32_MAX)
+                    return no(who + "kept slice refused: its BLAS is not 3k - 2 nodes over k primitives of the scene");
+                need = s->vertex_need;
+                depth = s->depth;
+            }
+            if (vertices < std::max(need, 1u))
+                return no(who + "vertex_count does not cover the vertex indices of its primitives");
+            if ((uint64_t)x.vertex + vertices > before[0]) return no(who + "vertex_count reaches past the vertex array");
+            for (const Kept& o : kept) {
+                if (ranges_meet(x.primitive, tris, o.x.primitive, (o.x.node[1] + 2u) / 3u) ||
+                    ranges_meet(x.node[0], x.node[1], o.x.node[0], o.x.node[1]))
+                    return no(who + "it partly overlaps another kept slice");
+                if (ranges_meet(x.vertex, vertices, o.x.vertex, o.vertices))
+                    return no(who + "vertex_count reaches into another kept slice's vertices");
+            }
+            kept.push_back(Kept{x, vertices});
+            mv.src[0] = x.vertex;
+            mv.src[1] = x.primitive;
+            mv.src[2] = x.node[0];
+        }
+        const uint32_t nodes = 3u * tris - 2u;
+        const hk_mesh_index to{(uint32_t)at[0], (uint32_t)at[1], {(uint32_t)at[2], nodes}};
+        out->slices[k] = to;
+        if (e.source) out->source_slices.push_back(to);
+        out->registry[k] = hk_ctx::MeshSlice{to, need, depth, 0u};
+        mv.dst[0] = to.vertex;
+        mv.dst[1] = to.primitive;
+        mv.dst[2] = to.node[0];
+        mv.count[0] = vertices;
+        mv.count[1] = tris;
+        mv.count[2] = nodes;
+        at[0] += vertices;
+        at[1] += tris;
+        at[2] += nodes;
+        if (at[0] > MESH_TOTAL_MAX || at[1] > MESH_TOTAL_MAX || at[2] > MESH_TOTAL_MAX || out->n_indices > MESH_TOTAL_MAX)
+            return no("too many vertices, primitives or nodes");
+    }
+    std::memcpy(out->after, before, sizeof(out->after));
+    for (int i = 0; i < 3; ++i) out->after[i] = (uint32_t)at[i];
+    return HK_OK;
+}
+
+// (as counts_error, for hk_set_meshes_counts)
+static thread_local std::string set_counts_error;
+const char* hk_set_meshes_counts_error(void) { return set_counts_error.c_str(); }
+
+int hk_set_meshes_counts(const uint32_t before[9], const hk_mesh_entry* list, uint32_t mesh_count, hk_mesh_index* slices,
+                         uint32_t after[9])
+{
+    set_counts_error.clear();
+    auto no = [&](const std::string& text) {
+        set_counts_error = "hk_set_meshes: " + text;
+        return HK_ERR_INVALID;
+    };
+    if (!before) return no("null counts");
+    if (!slices) return no("null slices");
+    MeshSetPlan plan;
+    std::string why;
+    const int rc = plan_set_meshes(before, nullptr, nullptr, list, mesh_count, &plan, &why);
+    if (rc != HK_OK) return no(why);
+    std::memcpy(slices, plan.slices.data(), plan.slices.size() * sizeof(hk_mesh_index));
+    if (after) std::memcpy(after, plan.after, sizeof(plan.after));
+    return HK_OK;
+}
+
+int hk_set_meshes(hk_ctx* c, const hk_mesh_entry* list, uint32_t mesh_count, hk_mesh_index* slices,
+                  const hk_instance_desc* set, const float* models, const float* local_aabbs, uint32_t count,
+                  const hk_material* materials, void* stream)
+{
+    if (!c) return HK_ERR_INVALID;
+    if (!c->has_scene) return fail(c, HK_ERR_STATE, "no scene uploaded (hk_scene_upload)");
+    if (!slices) return fail(c, HK_ERR_INVALID, "hk_set_meshes: null slices");
+    if (!set || !models || !local_aabbs) return fail(c, HK_ERR_INVALID, "hk_set_meshes: null pointer");
+    (void)hipSetDevice(c->device);
+    // everything the host can refuse, first: the list against the current arrays and registry, then the set against
+    // the new ones
+    const SliceReader rd{nullptr, c};
+    MeshSetPlan plan;
+    std::string why;
+    int rc = plan_set_meshes(c->count, &c->meshes, &rd, list, mesh_count, &plan, &why);
+    if (rc != HK_OK) return fail(c, rc, "hk_set_meshes: " + why);
+    HK_TRY(set_args_ok(c, set, count, "hk_set_meshes"));
+    std::vector<float> emissive;
+    if (materials) {
+        emissive.resize(4 * (size_t)c->count[6]);
+        for (uint32_t k = 0; k < c->count[6]; ++k) std::memcpy(&emissive[4 * (size_t)k], materials[k].emissive, 16);
+    }
+    SetChange change;
+    rc = plan_instance_set(plan.after, plan.registry, materials ? emissive.data() : c->emissive.data(), set, count, rd,
+                           &change, &why, true);
+    if (rc != HK_OK) return fail(c, rc, "hk_set_meshes: " + why);
+    change.materials = materials;
+    hipStream_t st = pick(c, stream);
+    HK_TRY(c->sch.gb_join(st));
+    HK_TRY(c->sch.gb_serialize(false));
+    const uint32_t n_sources = (uint32_t)plan.sources.size();
+    MeshStaging stage;
+    plan_mesh_staging(plan.sources, plan.source_slices.data(), plan.tris.data(), plan.n_vertices, plan.n_shapes,
+                      plan.n_indices, (size_t)mesh_count * sizeof(MeshMove), &stage);
+    // Room (hikari_amd.h hk_set_meshes "Capacity"), every allocation first as in hk_add_meshes.  The move is out of
+    // place: arrays 0-2 are written into their spares, which are then the arrays, and the arrays the spares.  A spare
+    // smaller than the capacity the call needs is allocated anew; the derivatives, which are rewritten whole, only
+    // where the node capacity grows.
+    struct Buffers {
+        std::vector<void*> p;
+        ~Buffers()
+        {
+            for (void* q : p) (void)hipFree(q);
+        }
+    } fresh, old;
+    auto grown = [](size_t need, size_t cap) { return std::max(need, cap + cap / 2); };
+    auto alloc = [&](size_t bytes) -> void* {
+        void* nb = nullptr;
+        if (hipMalloc(&nb, bytes) != hipSuccess) return nullptr;
+        fresh.p.push_back(nb);
+        return nb;
+    };
+    size_t cap[3];
+    void* nspare[3] = {};
+    bool ok = true;
+    for (int i = 0; i < 3; ++i) {
+        cap[i] = plan.after[i] > c->cap[i] ? grown(plan.after[i], c->cap[i]) : c->cap[i];
+        if (c->spare_cap[i] < cap[i]) ok = ok && (nspare[i] = alloc(staged_alloc_bytes(cap[i], SCENE_ELEM[i])));
+        else cap[i] = c->spare_cap[i];
+    }
+    void *n_wide = nullptr, *n_walk = nullptr, *n_aux = nullptr, *n_collapse = nullptr, *n_scratch = nullptr;
+    if (cap[2] != c->cap[2])
+        ok = ok && (n_wide = alloc(cap[2] * WIDE_NODE_BYTES)) && (n_walk = alloc(cap[2] * sizeof(hk_node))) &&
+             (n_aux = alloc(cap[2] * 12));
+    size_t collapse_cap = c->collapse_cap;
+    {
+        const size_t need = std::max<size_t>(1, std::max(plan.after[2], std::max(c->count[5], change.counts[5])));
+        if (need > collapse_cap) {
+            collapse_cap = grown(need, collapse_cap);
+            ok = ok && (n_collapse = alloc(collapse_cap * 4));
+        }
+    }
+    if (c->mesh_bytes < stage.total) ok = ok && (n_scratch = alloc(stage.total));
+    if (!ok) return fail(c, HK_ERR_HIP, "hk_set_meshes: out of device memory");
+    fresh.p.clear();  // (all of them go into the context below)
+    const void* from[3];
+    for (int i = 0; i < 3; ++i) {
+        if (nspare[i]) {
+            if (c->spare[i]) old.p.push_back(c->spare[i]);
+            c->spare[i] = nspare[i];
+            c->spare_cap[i] = cap[i];
+        }
+        from[i] = c->buf[i];
+        std::swap(c->buf[i], c->spare[i]);
+        std::swap(c->cap[i], c->spare_cap[i]);
+    }
+    void** slot[] = {(void**)&c->blas_wide, (void**)&c->walk_nodes[0], (void**)&c->blas_aux, (void**)&c->collapse_scratch,
+                     &c->mesh_scratch};
+    void* repl[] = {n_wide, n_walk, n_aux, n_collapse, n_scratch};
+    for (int k = 0; k < 5; ++k) {
+        if (!repl[k]) continue;
+        old.p.push_back(*slot[k]);
+        *slot[k] = repl[k];
+    }
+    c->aux_stride = c->cap[2];
+    if (n_collapse) c->collapse_cap = collapse_cap;
+    if (n_scratch) c->mesh_bytes = stage.total;
+    for (int i = 0; i < 3; ++i) {  // the tail behind the new count, zeroed
+        const size_t at = (size_t)plan.after[i] * SCENE_ELEM[i], end = staged_alloc_bytes(c->cap[i], SCENE_ELEM[i]);
+        if (end > at) HK_HIP(c, hipMemsetAsync((char*)c->buf[i] + at, 0, end - at, st));
+    }
+    if (n_wide) HK_HIP(c, hipMemsetAsync(n_wide, 0, c->cap[2] * WIDE_NODE_BYTES, st));
+    if (n_walk) HK_HIP(c, hipMemsetAsync(n_walk, 0, c->cap[2] * sizeof(hk_node), st));
+    HK_HIP(c, hipMemsetAsync(c->blas_aux, 0xFF, c->aux_stride * 12, st));  // (behind the count: U32_MAX, as at upload)
+    MeshAddArgs A;
+    char* table = nullptr;
+    HK_TRY(enqueue_mesh_staging(c, plan.sources, stage, st, &A, &table));
+    HK_HIP(c, hipMemcpyAsync(table, plan.moves.data(), (size_t)mesh_count * sizeof(MeshMove), hipMemcpyHostToDevice, st));
+    MeshMoveArgs V;
+    V.table = (const MeshMove*)table;
+    V.n_meshes = mesh_count;
+    V.n_vertices = plan.after[0];
+    V.n_prims = plan.after[1];
+    V.n_nodes = plan.after[2];
+    for (int i = 0; i < 3; ++i) {
+        V.src[i] = from[i];
+        V.dst[i] = c->buf[i];
+    }
+    V.aux = c->blas_aux;
+    V.stride = c->aux_stride;
+    timed(c, "move_meshes", st, [&] { launch_mesh_move(V, st); });
+    timed(c, "set_meshes", st, [&] {
+        if (n_sources) launch_mesh_add(A, st);
+        refresh_blas_derivatives(c, st, plan.after[2]);
+    });
+    HK_HIP(c, hipGetLastError());
+    std::vector<uint32_t> levels(n_sources);
+    if (n_sources) HK_HIP(c, hipMemcpyAsync(levels.data(), A.M.levels, levels.size() * 4, hipMemcpyDeviceToHost, st));
+    HK_HIP(c, hipStreamSynchronize(st));
+    // the counts and the registry move together, once the device is done; then the set, planned against them
+    for (uint32_t k = 0; k < n_sources; ++k) plan.registry[plan.source_entry[k]].depth = levels[k];
+    for (int i = 0; i < 3; ++i) c->count[i] = plan.after[i];
+    c->meshes = plan.registry;
+    std::memcpy(slices, plan.slices.data(), plan.slices.size() * sizeof(hk_mesh_index));
+    return rebuild_instances(c, models, local_aabbs, count, st, nullptr, &change);
 }
 
 int hk_scene_capacity(const hk_ctx* c, uint32_t capacity[9])

@@ -78,6 +78,11 @@ class hk_mesh_desc(C.Structure):
                 ("indices", C.c_void_p), ("index_count", C.c_uint32), ("topology", C.c_uint32)]
 
 
+class hk_mesh_entry(C.Structure):
+    """include/hikari_amd.h hk_mesh_entry (one entry of hk_set_meshes' list: a new mesh, or a kept slice)."""
+    _fields_ = [("source", C.POINTER(hk_mesh_desc)), ("keep", hk_mesh_index), ("vertex_count", C.c_uint32)]
+
+
 HK_INSTANCE_NEW = 0xFFFFFFFF
 
 
@@ -228,6 +233,11 @@ def lib() -> C.CDLL:
                                        C.POINTER(u32)]),
         "hk_add_meshes_counts_error": (C.c_char_p, []),
         "hk_scene_capacity": (i32, [vp, C.POINTER(u32)]),
+        "hk_set_meshes": (i32, [vp, C.POINTER(hk_mesh_entry), u32, C.POINTER(hk_mesh_index),
+                                C.POINTER(hk_instance_desc), vp, vp, u32, vp, vp]),
+        "hk_set_meshes_counts": (i32, [C.POINTER(u32), C.POINTER(hk_mesh_entry), u32, C.POINTER(hk_mesh_index),
+                                       C.POINTER(u32)]),
+        "hk_set_meshes_counts_error": (C.c_char_p, []),
         "hk_scene_shared_transform": (i32, [vp, C.POINTER(i32)]),
         "hk_instance_set_counts": (i32, [C.POINTER(hk_scene_desc), C.POINTER(hk_instance_desc), u32, vp, C.POINTER(u32)]),
         "hk_read_scene_array": (i32, [vp, i32, vp, C.c_size_t]),
@@ -285,6 +295,7 @@ EXPORTED_SYMBOLS = [
     "hks_add_instance", "hks_build", "hks_get_desc", "hk_scene_shared_transform", "hks_shared_transform",
     "hks_instance_bounds", "hks_screen_bounds", "hk_tile_skip_info",
     "hk_add_meshes", "hk_add_meshes_counts", "hk_add_meshes_counts_error", "hk_scene_capacity",
+    "hk_set_meshes", "hk_set_meshes_counts", "hk_set_meshes_counts_error",
 ]
 
 

@@ -16,7 +16,7 @@ from typing import Optional
 import numpy as np
 
 from . import _abi
-from .scene import Scene, load_noise, texture_array
+from .scene import Mesh, Scene, load_noise, texture_array
 from .settings import HikariSettings, HikariUniversalSettings, PresentFormat
 
 RESERVOIR_DTYPE = np.dtype([("radiance", "<u4", 2), ("random", "<u4", 2), ("visible_position", "<f4", 4),
@@ -145,6 +145,38 @@ def add_meshes_counts(before, meshes):
     if rc != 0:
         raise _abi.HikariError(f"hk_add_meshes_counts failed ({rc}): {L.hk_add_meshes_counts_error().decode()}")
     return [(s.vertex, s.primitive, s.node[0], s.node[1]) for s in slices[:len(meshes)]], list(after)
+
+
+def _mesh_entries(entries):
+    """(ctypes array of hk_mesh_entry, what it points into) for the list of set_meshes: an item is a Mesh (a new mesh),
+    or ((vertex, primitive, node0, node_count), vertex_count): a slice of the current arrays, kept."""
+    new = [e for e in entries if isinstance(e, Mesh)]
+    descs, keep = _mesh_descs(new)
+    out = (_abi.hk_mesh_entry * max(1, len(entries)))()
+    k = 0
+    for d, e in zip(out, entries):
+        if isinstance(e, Mesh):
+            d.source = C.pointer(descs[k])
+            k += 1
+        else:
+            (v, pr, n0, nc), count = e
+            d.keep = _abi.hk_mesh_index(int(v), int(pr), (C.c_uint32 * 2)(int(n0), int(nc)))
+            d.vertex_count = int(count)
+    return out, (descs, keep)
+
+
+def set_meshes_counts(before, entries):
+    """(slices, counts after) of hk_set_meshes_counts: the (vertex, primitive, node0, node_count) slice of every entry
+    of `entries` (HikariRenderer.set_meshes) in the new layout, and the nine counts after ([3:] are `before`'s: they
+    follow the instance set).  Host arithmetic only: needs no device."""
+    L = _abi.lib()
+    arr, keep = _mesh_entries(entries)
+    slices = (_abi.hk_mesh_index * max(1, len(entries)))()
+    after = (C.c_uint32 * 9)()
+    rc = L.hk_set_meshes_counts((C.c_uint32 * 9)(*before), arr, len(entries), slices, after)
+    if rc != 0:
+        raise _abi.HikariError(f"hk_set_meshes_counts failed ({rc}): {L.hk_set_meshes_counts_error().decode()}")
+    return [(s.vertex, s.primitive, s.node[0], s.node[1]) for s in slices[:len(entries)]], list(after)
 
 
 class HikariRenderer:
@@ -367,6 +399,30 @@ class HikariRenderer:
         slices = (_abi.hk_mesh_index * max(1, len(meshes)))()
         _check(self.ctx, self._L.hk_add_meshes(self.ctx, descs, len(meshes), slices, _stream(stream)), "hk_add_meshes")
         return [(s.vertex, s.primitive, s.node[0], s.node[1]) for s in slices[:len(meshes)]]
+
+    def set_meshes(self, scene: Scene, entries, previous=None, materials: bool = False, models=None, local_aabbs=None,
+                   stream=None) -> list:
+        """A new mesh asset list and instance set (hk_set_meshes): meshes removed, replaced by ones of another
+        topology, inserted or reordered, without a host rebuild.  entries: the new list, an item a hikari_amd.Mesh (a
+        new mesh, built on the GPU) or ((vertex, primitive, node0, node_count), vertex_count) (a slice of the current
+        arrays, kept and moved to its place).  `scene` is the host scene of the new list and set: scene.meshes[k] is
+        the mesh entry k stands for, and its instances, models and local boxes are used as in set_instances (previous,
+        materials, models, local_aabbs: as there).  Returns the slices of the new layout, which equal
+        scene.mesh_index(k)."""
+        m = np.ascontiguousarray(scene.instance_models() if models is None else models, np.float32).reshape(-1, 16)
+        a = np.ascontiguousarray(scene.instance_local_aabbs() if local_aabbs is None else local_aabbs,
+                                 np.float32).reshape(-1, 6)
+        if len(m) != len(a) or len(m) != len(scene.instances):
+            raise ValueError("models and local_aabbs need one record per instance")
+        if len(entries) != len(scene.meshes):
+            raise ValueError("entries needs one item per mesh of the scene")
+        arr, keep = _mesh_entries(entries)
+        slices = (_abi.hk_mesh_index * max(1, len(entries)))()
+        mats = material_records(scene) if materials else None
+        _check(self.ctx, self._L.hk_set_meshes(self.ctx, arr, len(entries), slices, instance_descs(scene, previous),
+                                               m.ctypes.data, a.ctypes.data, len(m), mats, _stream(stream)),
+               "hk_set_meshes")
+        return [(s.vertex, s.primitive, s.node[0], s.node[1]) for s in slices[:len(entries)]]
 
     def scene_capacity(self) -> list:
         """The element capacities of the nine scene arrays, hk_scene_desc order (hk_scene_capacity): what each holds
@@ -639,6 +695,12 @@ class HikariPlugin:
     def add_meshes(self, meshes, stream=None) -> list:
         """HikariRenderer.add_meshes: mesh assets created after the scene was uploaded (AssetEvent::Created)."""
         return self.renderer.add_meshes(meshes, stream=stream)
+
+    def set_meshes(self, scene: Scene, entries, previous=None, materials: bool = False, models=None, local_aabbs=None,
+                   stream=None) -> list:
+        """HikariRenderer.set_meshes: mesh assets removed, replaced or reordered (AssetEvent::Removed / Modified with
+        another topology, the BTreeMap's order) together with the instance set."""
+        return self.renderer.set_meshes(scene, entries, previous, materials, models, local_aabbs, stream)
 
     def set_instances(self, scene: Scene, previous=None, materials: bool = False, stream=None) -> None:
         """`prepare_instances` for spawned, despawned, hidden or re-materialed entities (HikariRenderer.set_instances)."""

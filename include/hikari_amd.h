@@ -267,7 +267,8 @@ int hk_update_instances(hk_ctx* ctx, const float* models, const float* local_aab
 /* Deforming meshes: what the reference does for `AssetEvent::Modified` (mesh.rs:77-166
  * extract_mesh_assets / prepare_mesh_assets run GpuMesh::try_from again, mod.rs:379-467: vertices, primitives and a
  * fresh bvh 0.7.1 BLAS; prepare_instances, instance.rs:284-437, then runs on the new mesh slices), ON THE GPU and in
- * place, for meshes whose topology is unchanged: the primitives keep their stored vertex indices and the uvs stay.
+ * place, for meshes whose topology is unchanged (another triangle or vertex count: hk_set_meshes, below, with the mesh
+ * as a new entry at its position): the primitives keep their stored vertex indices and the uvs stay.
  * For each listed mesh the device rewrites hk_vertex.position and hk_vertex.normal of the slice (normals NULL: the
  * uploaded normals stay), the three positions of each hk_primitive from the new vertices, and rebuilds the mesh's
  * BLAS with the host builder's exact operations (hikari_scene.h hks_build: 6 buckets, node indices relative to the
@@ -355,8 +356,8 @@ int hk_scene_counts(const hk_ctx* ctx, uint32_t counts[9]);
  * stream once (the BLAS depths).
  *   Capacity: arrays 0-2 and their device-only derivatives keep a capacity beside their count (hk_scene_capacity); a
  * call allocates only for a count above its capacity, and then max(count, 1.5 x capacity), the contents kept.  Nothing
- * shrinks before hk_scene_upload or hk_destroy, which reset them.  REMOVAL IS NOT OFFERED: a mesh no instance carries
- * keeps its bytes until the next hk_scene_upload.
+ * shrinks before hk_scene_upload or hk_destroy, which reset them.  hk_add_meshes only appends: a mesh no instance carries
+ * keeps its bytes until hk_set_meshes (below) leaves it out of its list, or the next hk_scene_upload.
  *   HK_ERR_INVALID with a message naming hks_add_mesh's error, decided on the host before any device work, the context
  * unchanged and usable: a null list or null `slices`; mesh_count == 0; positions / normals / uvs missing
  * (MissingAttributePosition / MissingAttributeNormal / MissingAttributeUV); an index >= vertex_count; a topology
@@ -383,6 +384,59 @@ int hk_add_meshes(hk_ctx* ctx, const hk_mesh_desc* meshes, uint32_t mesh_count, 
 int hk_add_meshes_counts(const uint32_t before[9], const hk_mesh_desc* meshes, uint32_t mesh_count,
                          hk_mesh_index* slices, uint32_t after[9]);
 const char* hk_add_meshes_counts_error(void);
+
+/* A new mesh asset list: what the reference does when mesh assets are removed (`AssetEvent::Removed`,
+ * mesh.rs:89-92, 123-126), modified with another triangle or vertex count, or created with a handle that sorts ahead
+ * of others: prepare_mesh_assets rebuilds the three buffers from its BTreeMap<Handle<Mesh>, GpuMesh> in key order
+ * (mesh.rs:140-163), a new GpuMesh from GpuMesh::try_from (mod.rs:379-467).  hk_set_meshes does that ON THE GPU, and
+ * the instance set with it: the counterpart of hk_set_instances for arrays 0, 1, 2.  After the call the scene is, byte
+ * for byte, what hks_build + hk_scene_upload give when the meshes of `list` are added with hks_add_mesh in list order
+ * (a kept entry standing for the mesh that produced its slice) and the instances of `set` in theirs: all nine arrays
+ * and their counts.
+ *   list[k]: source != NULL: a new mesh, assembled and its BLAS built as by hk_add_meshes.  source == NULL: the slice
+ * `keep` of the current arrays is kept: its vertex_count vertices (the registry knows only the largest index its
+ * primitives store; the host builder concatenates all of a mesh's vertices, unreferenced trailing ones too, so the
+ * count is the caller's, as hk_mesh_update's), its primitives and its nodes move verbatim, node and vertex indices
+ * being mesh-relative.  A kept slice is a known slice, or one that passes hk_set_instances' checks of a slice no
+ * instance has carried and is registered by this call.  A slice that is not listed is gone.  A mesh replaced by one
+ * of another topology is a new entry at the old one's position, the old slice not listed.
+ *   slices[k]: entry k's slice in the new layout, by the running sums of vertices, primitives and 3k - 2 nodes.
+ * set[i].mesh names a slice of the NEW layout (hk_set_meshes_counts gives them beforehand); previous, materials,
+ * models and local_aabbs are hk_set_instances': an instance of a replaced mesh carries its old index as `previous`
+ * and keeps its motion vectors.  After the call the known slices are exactly the list's, so every leaf of arrays 2
+ * carries its triangle's box and hk_update_meshes deforms any of them.  Waits for the stream twice (the BLAS depths,
+ * then hk_set_instances' wait).
+ *   Capacity: counts 0-2 may fall, the capacities (hk_scene_capacity) never do before hk_scene_upload / hk_destroy.
+ * The move is out of place, since a reorder lets source and destination ranges overlap in any way: the context keeps
+ * one spare buffer per array 0-2, of at least the array's capacity from the first call on; a call writes the new
+ * arrays into the spares, zeroes their tails behind the new counts, and swaps.  A call allocates where a count passes
+ * its capacity (max(count, 1.5 x capacity)) or a spare is smaller than the capacity needed, so a steady cycle of
+ * removals and additions allocates nothing from its second call on.  The device-only derivatives are rewritten whole.
+ *   HK_ERR_INVALID with a message, decided on the host before any device work, the context unchanged and usable: a
+ * null list, null `slices`, mesh_count == 0; for a new entry every refusal of hk_add_meshes, in its words ("mesh k:
+ * MissingAttributeNormal" ...); a kept slice that fails hk_set_instances' slice checks ("kept slice refused: ...");
+ * a kept vertex_count below what its primitives index, reaching past the vertex array or into another kept slice's
+ * vertices; a slice kept twice; totals past 0x40000000; every refusal of hk_set_instances for the set, against the
+ * new layout, and an instance whose mesh is none of slices[]: "its mesh is not in the new list".  HK_ERR_STATE
+ * without a scene.  HK_ERR_HIP "out of device memory" from the allocations for arrays 0-2 and their derivatives, all
+ * made first: the context is as it was (the set's own arrays grow as in hk_set_instances).  Any later HK_ERR_HIP: as
+ * documented for hk_add_meshes.  A singular model fails after the rebuild, as in hk_set_instances. */
+typedef struct hk_mesh_entry {
+    const hk_mesh_desc* source;  /* non-NULL: a new mesh */
+    hk_mesh_index keep;          /* source == NULL: a slice of the current arrays 0-2, kept */
+    uint32_t vertex_count;       /* source == NULL: the kept mesh's vertex count */
+} hk_mesh_entry;
+int hk_set_meshes(hk_ctx* ctx, const hk_mesh_entry* list, uint32_t mesh_count, hk_mesh_index* slices,
+                  const hk_instance_desc* set, const float* models, const float* local_aabbs, uint32_t count,
+                  const hk_material* materials, void* stream);
+/* The host arithmetic of the list (needs no device or context): entry k's slice in the new layout and the nine counts
+ * after (only [0..2] change: [3..8] follow the set, hk_instance_set_counts).  With no context a kept slice is checked
+ * against `before` and the other kept slices alone; the other refusals of the list are hk_set_meshes', with its codes.
+ * The message is what hk_set_meshes_counts_error() returns on the calling thread until its next hk_set_meshes_counts
+ * (an empty string after a success).  `after` may be NULL. */
+int hk_set_meshes_counts(const uint32_t before[9], const hk_mesh_entry* list, uint32_t mesh_count,
+                         hk_mesh_index* slices, uint32_t after[9]);
+const char* hk_set_meshes_counts_error(void);
 /* the element capacities beside hk_scene_counts' counts, hk_scene_desc order: what each array holds before a call
  * has to allocate (hk_set_instances: 3, 4, 5, 7, 8; hk_add_meshes: 0, 1, 2; array 6 never grows).  HK_ERR_STATE
  * without a scene. */
