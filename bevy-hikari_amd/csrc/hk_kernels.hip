@@ -2839,12 +2839,25 @@ void launch_denoise(const FrameArgs& A, const DenoiseArgs& D, int level, hipStre
         },
         D.channels == 3);
 }
-void launch_tone(const FrameArgs& A, const ToneArgs& T, hipStream_t st)
+uint32_t tone_run_px(const FrameArgs& A)
 {
     const Frame& F = A.F;
-    const int32_t ly0 = F.win_rows > 0 ? F.win_row0 : 0, rows = launch_rows(F, F.s_rows);
+    const int32_t rows = launch_rows(F, F.s_rows);
     const int32_t x0 = F.win_cols > 0 ? F.win_col0 : 0, cols = (int32_t)launch_cols(F, F.s[0]);
-    if (F.s[0] % (uint32_t)TONE_RUN == 0u && x0 % TONE_RUN == 0 && cols % TONE_RUN == 0 && rows > 0 && cols > 0) {
+    return F.s[0] % (uint32_t)TONE_RUN == 0u && x0 % TONE_RUN == 0 && cols % TONE_RUN == 0 && rows > 0 && cols > 0 ? (uint32_t)TONE_RUN : 0u;
+}
+void launch_tone(const FrameArgs& A, const ToneArgs& T, hipStream_t st, const int32_t* rect)
+{
+    const Frame& F = A.F;
+    int32_t ly0 = F.win_rows > 0 ? F.win_row0 : 0, rows = launch_rows(F, F.s_rows);
+    int32_t x0 = F.win_cols > 0 ? F.win_col0 : 0, cols = (int32_t)launch_cols(F, F.s[0]);
+    if (tone_run_px(A)) {
+        if (rect) {  // within the window, columns on whole runs (the caller's arithmetic; clamped all the same)
+            const int32_t rx0 = std::max(rect[0], x0) / TONE_RUN * TONE_RUN, rx1 = std::min(rect[2], x0 + cols);
+            const int32_t ry0 = std::max(rect[1], ly0), ry1 = std::min(rect[3], ly0 + rows);
+            if (rx1 <= rx0 || ry1 <= ry0) return;
+            x0 = rx0, cols = (rx1 - rx0 + TONE_RUN - 1) / TONE_RUN * TONE_RUN, ly0 = ry0, rows = ry1 - ry0;
+        }
         const uint32_t runs = (uint32_t)cols / (uint32_t)TONE_RUN, n = runs * (uint32_t)rows;
         hipLaunchKernelGGL(k_tone_run, dim3((n + 255u) / 256u), dim3(256), 0, st, A, T, ly0, x0, runs, n);
     } else {

@@ -42,6 +42,7 @@ inline int32_t launch_rows(const Frame& F, int32_t rows) { return F.win_rows > 0
 // covered pixel or a background pixel whose constants are still due.  A workgroup outside them would store nothing
 // (every pixel background, every target already holding its constants: the runtime's tile_keep derives that from the
 // scene's screen bound and the elision masks' history) and returns at its first instruction.  TILE_KEEP_ALL: no skip.
+// (The grid stays whole: a grid of the kept tiles alone measured 8.6 % slower per frame)
 struct TileKeep {
     uint32_t x0, y0, x1, y1;
 };
@@ -308,7 +309,11 @@ void launch_light_merged(const FrameArgs& A, const ChannelArgs& C0, const Channe
                          const TileKeep& keep_indirect = TILE_KEEP_ALL);
 void launch_demod(const FrameArgs& A, const DenoiseArgs& D, hipStream_t st);
 void launch_denoise(const FrameArgs& A, const DenoiseArgs& D, int level, hipStream_t st);
-void launch_tone(const FrameArgs& A, const ToneArgs& T, hipStream_t st);
+// rect: the launch restricted to plane columns [rect[0], rect[2]) and local rows [rect[1], rect[3]) of its window
+// (hks_tone_rect; only where tone_run_px(A) != 0: the run kernel takes any aligned rectangle), nullptr: the window
+void launch_tone(const FrameArgs& A, const ToneArgs& T, hipStream_t st, const int32_t* rect = nullptr);
+// the pixels of a row one thread of launch_tone's kernel over A takes (TONE_RUN), 0 where the per-texel kernel runs
+uint32_t tone_run_px(const FrameArgs& A);
 void launch_collapse_leaves(hk_node* nodes, uint32_t n, const uint32_t* node_base, const uint32_t* node_count,
                             uint32_t* scratch, hipStream_t st);
 void launch_fill_leaves(hk_node* blas, uint32_t n_blas, const uint32_t* prim_offset, const hk_primitive* prims,

@@ -340,6 +340,24 @@ struct MaskHistory {
         return ok;
     }
 };
+// What the host knows of a tone slot's texels (tone_buf[k]) without reading them.  k_tone_run's rule (tone_texel): a
+// pixel whose render texels are the zero texels (a background pixel's, bg_elide) gets the clear colour's texel, whatever
+// else the frame holds.  So after a launch with clear colour `clear` over window `key`, whose input planes held the
+// zero texel at every pixel outside `cover`, every texel of the window outside `cover` is that clear-colour texel: the
+// launch stored it there, or left those pixels out because the record before it already said so (hk_tone_sum).
+// known is false until such a launch ran on the slot as it is (reset: the slot was reallocated, or a launch stored texels
+// the host cannot name).
+struct ToneHistory {
+    bool known = false;
+    PxRect cover;
+    float clear[4] = {};   // compared bit for bit
+    int32_t key[4] = {};   // the launch window: local row 0, rows, column 0, columns
+    void reset() { known = false; }
+    bool holds(const float* clear_color, const int32_t* window) const
+    {
+        return known && std::memcmp(clear, clear_color, sizeof(clear)) == 0 && std::memcmp(key, window, sizeof(key)) == 0;
+    }
+};
 }  // namespace
 
 struct hk_ctx {
@@ -443,6 +461,11 @@ struct hk_ctx {
     PxRect grect[2] = {PxRect::all(), PxRect::all()};
     MaskHistory gb_hist, bg_hist[2];
     uint32_t tiles_skipped[3] = {};
+    // Tone pass over the kept rectangle: each tone slot's history, and the last hk_tone_sum's launch (the pixels of its
+    // window it left out, the frame rectangle it ran over; hk_tone_skip_info)
+    ToneHistory tone_hist[2];
+    uint64_t tone_skipped = 0;
+    int32_t tone_rect[4] = {};
     // denoise
     uint4* dn_rgb[4] = {};        // a-trous level inputs, the 3 channels packed (DenoiseArgs::rgb / bi)
     uint2* dn_bi[4] = {};
@@ -640,6 +663,10 @@ void free_targets(hk_ctx* c)
     c->bg_valid[0] = c->bg_valid[1] = c->gb_valid = false;
     c->grect[0] = c->grect[1] = PxRect::all();
     c->tiles_skipped[0] = c->tiles_skipped[1] = c->tiles_skipped[2] = 0;
+    c->tone_hist[0].reset();
+    c->tone_hist[1].reset();
+    c->tone_skipped = 0;
+    c->tone_rect[0] = c->tone_rect[1] = c->tone_rect[2] = c->tone_rect[3] = 0;
     c->upscale_wh[0] = c->upscale_wh[1] = c->taa_wh[0] = c->taa_wh[1] = 0;
     c->present_wh[0] = c->present_wh[1] = 0;
     c->accum_n = 0;
@@ -1029,13 +1056,13 @@ TileKeep tile_keep(const FrameArgs& A, uint32_t width, int32_t row0, int32_t row
     const Frame& F = A.F;
     *skipped = 0;
     if (F.stripe_n >= 2) return TILE_KEEP_ALL;
-    const int64_t ox = F.win_cols > 0 ? F.win_col0 : 0, oy = (int64_t)row0 + (F.win_rows > 0 ? F.win_row0 : 0);
+    const int32_t ox = F.win_cols > 0 ? F.win_col0 : 0, oy = F.win_rows > 0 ? F.win_row0 : 0;
+    const int32_t window[4] = {ox, oy, ox + (int32_t)launch_cols(F, width), oy + launch_rows(F, rows)};
     const int64_t gx = (launch_cols(F, width) + 15u) / 16u, gy = ((uint32_t)launch_rows(F, rows) + 15u) / 16u;
-    auto lo = [](int64_t p, int64_t o, int64_t g) { return std::clamp<int64_t>(p - o, 0, 16 * g) / 16; };
-    auto hi = [](int64_t p, int64_t o, int64_t g) { return (std::clamp<int64_t>(p - o, 0, 16 * g) + 15) / 16; };
-    TileKeep K{(uint32_t)lo(keep.x0, ox, gx), (uint32_t)lo(keep.y0, oy, gy), (uint32_t)hi(keep.x1, ox, gx),
-               (uint32_t)hi(keep.y1, oy, gy)};
-    if (keep.empty() || K.x1 <= K.x0 || K.y1 <= K.y0) K = TileKeep{0u, 0u, 0u, 0u};
+    const int32_t kr[4] = {keep.x0, keep.y0, keep.x1, keep.y1};
+    uint32_t t[4];
+    (void)hks_keep_tiles(kr, window, row0, 16u, t);  // (all zeros when no tile is kept)
+    const TileKeep K{t[0], t[1], t[2], t[3]};
     *skipped = (uint32_t)(gx * gy) - (K.x1 - K.x0) * (K.y1 - K.y0);
     return *skipped ? K : TILE_KEEP_ALL;
 }
@@ -2599,6 +2626,16 @@ int hk_tile_skip_info(const hk_ctx* c, uint32_t skipped[3], int32_t bound[4], in
     return HK_OK;
 }
 
+int hk_tone_skip_info(const hk_ctx* c, uint64_t* skipped_pixels, int32_t rect[4])
+{
+    if (!c) return HK_ERR_INVALID;
+    if (!c->sized) return HK_ERR_STATE;
+    if (skipped_pixels) *skipped_pixels = c->tone_skipped;
+    if (rect)
+        for (int k = 0; k < 4; ++k) rect[k] = c->tone_rect[k];
+    return HK_OK;
+}
+
 int hk_instance_set_counts(const hk_scene_desc* d, const hk_instance_desc* set, uint32_t count,
                            const hk_material* materials, uint32_t counts[9])
 {
@@ -3376,7 +3413,45 @@ int hk_tone_sum(hk_ctx* c, const hk_settings* settings, void* stream)
     T.indirect = settings->indirect_bounces == 0u ? nullptr : (settings->denoise ? c->denoised[2] : c->render[2]);
     T.output = c->tone_buf[c->head];
     HK_TRY(c->sch.ext_wait(st, T.output));
-    timed(c, "tone_mapping", st, [&] { launch_tone(A, T, st); });
+    // Tone pass over the kept rectangle.  `in`: outside it every input plane holds the zero texel, as the light
+    // launches' mask histories say of this render slot (a masked launch leaves the slot's bit in every byte outside
+    // its G-buffer's screen bound, and the bit stands for a zero render texel: bg_elide; the indirect plane only where
+    // the pass reads it).  Not known, and the launch whole: elision or the tile skip off, a light launch without its
+    // mask (host planes, a ratio other than 1), a mask dropped since, interleaved stripes, the per-texel kernel, and
+    // the denoiser's planes (a background pixel's denoised texel is not shown here to be constant).
+    const int32_t ly0 = A.F.win_rows > 0 ? A.F.win_row0 : 0, x0 = A.F.win_cols > 0 ? A.F.win_col0 : 0;
+    const int32_t window[4] = {x0, ly0, x0 + (int32_t)launch_cols(A.F, A.F.s[0]), ly0 + launch_rows(A.F, A.F.s_rows)};
+    const int32_t key[4] = {window[1], window[3] - window[1], window[0], window[2] - window[0]};
+    const uint32_t run = tone_run_px(A);
+    PxRect in = PxRect::all();
+    bool in_known = run != 0u && !settings->denoise && !bg_elision_off(c) && c->on(OPT_BG_TILE_SKIP) && c->stripe_n < 2;
+    for (int k = 0; in_known && k < (T.indirect ? 2 : 1); ++k) {
+        const int bit = 2 + (int)c->sch.rslot;
+        in_known = c->bg_valid[k] && c->bg_hist[k].known[bit];
+        if (in_known) in = k == 0 ? c->bg_hist[k].cover[bit] : in.join(c->bg_hist[k].cover[bit]);
+    }
+    // the launch: the inputs' rectangle joined with the one outside which the slot already holds this clear colour's
+    // texel; the slot's record afterwards: outside `in` the launch stored that texel or found it there
+    ToneHistory& H = c->tone_hist[c->head];
+    const int64_t all_px = (int64_t)(window[2] - window[0]) * (int64_t)(window[3] - window[1]);
+    int32_t rect[4] = {window[0], window[1], window[2], window[3]};
+    bool any = true;
+    if (in_known && H.holds(settings->clear_color, key)) {
+        const PxRect keep = in.join(H.cover);
+        const int32_t kr[4] = {keep.x0, keep.y0, keep.x1, keep.y1};
+        any = hks_tone_rect(kr, window, c->s_row0, run, rect) != 0;
+    }
+    if (in_known) {
+        H.known = true;
+        H.cover = in;
+        std::memcpy(H.clear, settings->clear_color, sizeof(H.clear));
+        std::memcpy(H.key, key, sizeof(H.key));
+    } else {
+        H.reset();
+    }
+    c->tone_skipped = (uint64_t)(all_px - (any ? (int64_t)(rect[2] - rect[0]) * (int64_t)(rect[3] - rect[1]) : 0));
+    for (int k = 0; k < 4; ++k) c->tone_rect[k] = any ? rect[k] + ((k & 1) ? c->s_row0 : 0) : 0;
+    if (any) timed(c, "tone_mapping", st, [&] { launch_tone(A, T, st, c->tone_skipped ? rect : nullptr); });
     if (async) HK_TRY(c->sch.tail_end());
     HK_HIP(c, hipGetLastError());
     return HK_OK;

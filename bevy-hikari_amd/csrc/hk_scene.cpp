@@ -629,4 +629,43 @@ int hks_screen_bounds(const double aabb[6], const hk_view* view, uint32_t width,
     return 1;
 }
 
+// Each edge of keep relative to the window's origin, clamped to the grid's extent (whole tiles: the last tile may reach
+// past the window) and divided down (first tile) or up (one past the last).
+int hks_keep_tiles(const int32_t keep[4], const int32_t window[4], int32_t row0, uint32_t tile, uint32_t tiles[4])
+{
+    if (!keep || !window || !tiles || tile == 0) return 0;
+    tiles[0] = tiles[1] = tiles[2] = tiles[3] = 0;
+    if (window[2] <= window[0] || window[3] <= window[1]) return 0;
+    if (keep[2] <= keep[0] || keep[3] <= keep[1]) return 0;
+    const int64_t t = (int64_t)tile, ox = window[0], oy = (int64_t)row0 + window[1];
+    const int64_t gx = ((int64_t)window[2] - window[0] + t - 1) / t, gy = ((int64_t)window[3] - window[1] + t - 1) / t;
+    auto lo = [t](int64_t p, int64_t o, int64_t g) { return std::clamp<int64_t>(p - o, 0, t * g) / t; };
+    auto hi = [t](int64_t p, int64_t o, int64_t g) { return (std::clamp<int64_t>(p - o, 0, t * g) + t - 1) / t; };
+    const int64_t x0 = lo(keep[0], ox, gx), y0 = lo(keep[1], oy, gy), x1 = hi(keep[2], ox, gx), y1 = hi(keep[3], oy, gy);
+    if (x1 <= x0 || y1 <= y0) return 0;
+    tiles[0] = (uint32_t)x0, tiles[1] = (uint32_t)y0, tiles[2] = (uint32_t)x1, tiles[3] = (uint32_t)y1;
+    return 1;
+}
+
+// Frame rows to plane rows (less row0), the intersection with the window, then the columns outward to whole runs: the
+// window's own column edges are multiples of `run` (the caller's condition for the run kernel), so the rounded edges
+// stay inside it.  64-bit throughout: PxRect::all()-like edges (INT32_MAX) must not wrap.
+int hks_tone_rect(const int32_t keep[4], const int32_t window[4], int32_t row0, uint32_t run, int32_t launch[4])
+{
+    if (!keep || !window || !launch || run == 0) return 0;
+    launch[0] = launch[1] = launch[2] = launch[3] = 0;
+    const int64_t r = (int64_t)run;
+    if (window[0] < 0 || window[1] < 0 || window[2] <= window[0] || window[3] <= window[1]) return 0;
+    if (window[0] % r != 0 || window[2] % r != 0) return 0;
+    if (keep[2] <= keep[0] || keep[3] <= keep[1]) return 0;
+    const int64_t x0 = std::max<int64_t>(keep[0], window[0]), x1 = std::min<int64_t>(keep[2], window[2]);
+    const int64_t y0 = std::max<int64_t>((int64_t)keep[1] - row0, window[1]), y1 = std::min<int64_t>((int64_t)keep[3] - row0, window[3]);
+    if (x1 <= x0 || y1 <= y0) return 0;
+    launch[0] = (int32_t)(x0 / r * r);
+    launch[1] = (int32_t)y0;
+    launch[2] = (int32_t)((x1 + r - 1) / r * r);
+    launch[3] = (int32_t)y1;
+    return 1;
+}
+
 }  // extern "C"

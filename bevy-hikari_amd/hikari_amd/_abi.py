@@ -274,6 +274,9 @@ def lib() -> C.CDLL:
         "hks_instance_bounds": (i32, [vp, vp, u32, C.POINTER(C.c_double)]),
         "hks_screen_bounds": (i32, [C.POINTER(C.c_double), C.POINTER(hk_view), u32, u32, u32, C.POINTER(i32)]),
         "hk_tile_skip_info": (i32, [vp, C.POINTER(u32), C.POINTER(i32), C.POINTER(i32)]),
+        "hk_tone_skip_info": (i32, [vp, C.POINTER(C.c_uint64), C.POINTER(i32)]),
+        "hks_tone_rect": (i32, [C.POINTER(i32), C.POINTER(i32), i32, u32, C.POINTER(i32)]),
+        "hks_keep_tiles": (i32, [C.POINTER(i32), C.POINTER(i32), i32, u32, C.POINTER(u32)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -293,7 +296,7 @@ EXPORTED_SYMBOLS = [
     "hk_load_reservoirs", "hk_reset_counters", "hk_read_counters", "hk_enable_kernel_timing", "hk_kernel_timing", "hk_set_kernel_timing_interval",
     "hk_trace", "hk_selftest_f16", "hk_selftest_div", "hk_selftest_rcp", "hk_selftest_count", "hk_selftest_texture", "hk_selftest_math", "hks_create", "hks_destroy", "hks_last_error", "hks_add_mesh", "hks_add_material",
     "hks_add_instance", "hks_build", "hks_get_desc", "hk_scene_shared_transform", "hks_shared_transform",
-    "hks_instance_bounds", "hks_screen_bounds", "hk_tile_skip_info",
+    "hks_instance_bounds", "hks_screen_bounds", "hk_tile_skip_info", "hk_tone_skip_info", "hks_tone_rect", "hks_keep_tiles",
     "hk_add_meshes", "hk_add_meshes_counts", "hk_add_meshes_counts_error", "hk_scene_capacity",
     "hk_set_meshes", "hk_set_meshes_counts", "hk_set_meshes_counts_error",
 ]

@@ -447,6 +447,14 @@ class HikariRenderer:
         return {"gbuffer": skipped[0], "direct": skipped[1], "indirect": skipped[2],
                 "bound": tuple(bound) if bounded.value else None}
 
+    def tone_skip_info(self) -> dict:
+        """The last tone_sum's launch (hk_tone_skip_info): the pixels of its window it left out because they already
+        held the clear colour's texel, and the frame rectangle (x0, y0, x1, y1) it ran over, None when it launched
+        nothing."""
+        skipped, rect = C.c_uint64(), (C.c_int32 * 4)()
+        _check(self.ctx, self._L.hk_tone_skip_info(self.ctx, C.byref(skipped), rect), "hk_tone_skip_info")
+        return {"skipped": int(skipped.value), "rect": tuple(rect) if any(rect) else None}
+
     def scene_array(self, array: int, dtype, count: int) -> np.ndarray:
         """Device copy of group-2 scene array `array` (hk_scene_desc order) as `count` records."""
         out = np.empty(count, dtype)

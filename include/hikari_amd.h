@@ -242,7 +242,9 @@ void hk_settings_default(hk_settings* out);
  *   bg_tile_skip (1)         workgroups of k_gbuffer and of the light passes whose 16x16 tile lies outside the scene's
  *                            screen bound (hikari_scene.h hks_screen_bounds, from the instances' world box), and whose
  *                            targets already hold a background pixel's constants (the bg_elision masks' history),
- *                            return at their first instruction; 0: every workgroup runs (hk_tile_skip_info)
+ *                            return at their first instruction, and hk_tone_sum runs over the pixel rectangle that
+ *                            can hold anything but the clear colour; 0: every workgroup runs (hk_tile_skip_info,
+ *                            hk_tone_skip_info)
  * hk_set_option returns HK_ERR_INVALID for an unknown key, a value outside the key's range, or a fractional value
  * for any key but the pixel-count thresholds (*_px). */
 int hk_set_option(hk_ctx* ctx, const char* key, double value);
@@ -453,6 +455,17 @@ int hk_scene_shared_transform(const hk_ctx* ctx, int32_t* shared);
  * of the current G-buffer's screen bound, *bounded = 1; the whole frame and 0 while there is none (host planes, the
  * eye inside the scene's box, after hk_update_meshes).  Any out pointer may be NULL.  HK_ERR_STATE before hk_resize. */
 int hk_tile_skip_info(const hk_ctx* ctx, uint32_t skipped[3], int32_t bound[4], int32_t* bounded);
+/* The last hk_tone_sum's launch under the same option: it runs over the pixel rectangle that can hold anything but the
+ * clear colour's texel (the join of the rectangles outside which the frame's render planes hold a background pixel's
+ * zero texels, as the light launches' elision masks say, and the one outside which the output slot already holds that
+ * clear colour's texel from its own earlier launches), its columns outward to the kernel's pixel runs
+ * (hikari_scene.h hks_tone_rect).  *skipped_pixels: the pixels of its window it left out; 0 where it ran over the whole
+ * window (the option or bg_elision off, no screen bound, a slot or a render plane the host cannot vouch for: the first
+ * launches after hk_resize*, another clear colour, another window, a ratio other than 1, host G-buffer planes; the
+ * denoiser on; interleaved stripes; an odd plane width).  rect: the frame rectangle [x0, y0, x1, y1) it ran over, all
+ * zeros when nothing was launched (every texel already held the clear colour).  Either out pointer may be NULL.
+ * HK_ERR_STATE before hk_resize. */
+int hk_tone_skip_info(const hk_ctx* ctx, uint64_t* skipped_pixels, int32_t rect[4]);
 /* The host arithmetic hk_set_instances sizes its allocations and launches with (needs no device or context): the
  * nine counts after `set` replaces the instances of the host-built `uploaded` scene: the instances, 3n - 2 TLAS
  * nodes, the emitters (255 * emissive[3] * |emissive.rgb| > 0 in float, so a NaN does not emit; `materials`, if

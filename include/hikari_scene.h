@@ -61,6 +61,20 @@ int hks_instance_bounds(const float* models, const float* local_aabbs, uint32_t 
  * bg_tile_skip. */
 int hks_screen_bounds(const double aabb[6], const hk_view* view, uint32_t width, uint32_t height, uint32_t guard,
                       int32_t rect[4]);
+/* The tone pass over a kept rectangle (hk_tone_sum, hk_tone_skip_info).  keep: a pixel rectangle [x0, y0, x1, y1) in frame
+ * coordinates; window: the launch's window [col0, row0, col1, row1) in the coordinates of a plane whose row 0 is frame
+ * row `row0` and whose columns are the frame's; run: the pixels of a row one thread takes (the window's column edges
+ * must be multiples of it).  launch: keep within the window, in plane coordinates, its columns rounded outward to whole
+ * runs.  Returns 1, or 0 with launch all zeros when nothing is to be launched (an empty keep or intersection) or an
+ * argument is unusable (a null pointer, run == 0, an empty or unaligned window). */
+int hks_tone_rect(const int32_t keep[4], const int32_t window[4], int32_t row0, uint32_t run, int32_t launch[4]);
+/* The tiles of a launch's own grid that meet a kept rectangle (the background tile skip, hk_tile_skip_info).  keep and
+ * window as for hks_tone_rect; the grid's tile (0, 0) starts at the window's first column and row and the grid has
+ * ceil(columns / tile) x ceil(rows / tile) tiles of tile x tile pixels.  tiles: [tx0, ty0, tx1, ty1), the tiles holding a
+ * pixel of keep (the runtime's TileKeep: a workgroup outside them returns at once; a launch over them alone would have
+ * (tx1 - tx0) x (ty1 - ty0) workgroups at tile offset (tx0, ty0)).  Returns 1, or 0 with tiles all zeros when no tile is kept or an argument is unusable (a null
+ * pointer, tile == 0, an empty window). */
+int hks_keep_tiles(const int32_t keep[4], const int32_t window[4], int32_t row0, uint32_t tile, uint32_t tiles[4]);
 
 #ifdef __cplusplus
 }
