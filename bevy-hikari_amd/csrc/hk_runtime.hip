@@ -15,8 +15,6 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <map>
-#include <set>
 #include <string>
 #include <vector>
 
@@ -389,9 +387,9 @@ struct hk_ctx {
         uint32_t used = 0;     // instances of the current set that carry it (hk_set_instances can leave it none)
     };
     std::vector<MeshSlice> meshes;
-    // hk_set_instances: element capacities of the arrays it resizes (3, 4, 5, 7, 8; tlas_wide and walk_nodes[1]
-    // follow cap[5], prev_models follows cap[4]) and of collapse_scratch, and the materials' emissive as uploaded or
-    // last replaced (4 floats each: the host's emitter count)
+    // element capacities of the scene arrays (reserve_scene grows them, and with them the buffers FOLLOWERS names:
+    // tlas_wide and walk_nodes[1] follow cap[5], prev_models follows cap[4]) and of collapse_scratch, and the
+    // materials' emissive as uploaded or last replaced (4 floats each: the host's emitter count)
     size_t cap[9] = {};
     size_t collapse_cap = 0;
     std::vector<float> emissive;
@@ -1255,13 +1253,48 @@ static bool scene_stack_need(const hk_scene_desc* d, uint32_t* need, uint32_t* b
     return true;
 }
 
+// the nine arrays of a host scene and their counts, in array order
+static std::array<const hk_array*, 9> desc_arrays(const hk_scene_desc* d)
+{
+    return {&d->vertices, &d->primitives, &d->asset_nodes, &d->alias_table, &d->instances,
+            &d->instance_nodes, &d->materials, &d->emissive_nodes, &d->emissives};
+}
+static std::array<uint32_t, 9> desc_counts(const hk_scene_desc* d)
+{
+    std::array<uint32_t, 9> n;
+    for (int i = 0; i < 9; ++i) n[i] = desc_arrays(d)[i]->count;
+    return n;
+}
+
 static bool scene_desc_ok(const hk_scene_desc* d)
 {
-    const hk_array* arr[9] = {&d->vertices, &d->primitives, &d->asset_nodes, &d->alias_table, &d->instances,
-                              &d->instance_nodes, &d->materials, &d->emissive_nodes, &d->emissives};
-    for (int i = 0; i < 9; ++i)
-        if (arr[i]->count && !arr[i]->data) return false;
+    for (const hk_array* a : desc_arrays(d))
+        if (a->count && !a->data) return false;
     return true;
+}
+
+// the emissive of each material record, 4 floats each: what the host's emitter count reads (material_emits)
+static std::vector<float> emissive_of(const hk_material* materials, uint32_t n)
+{
+    std::vector<float> e(4 * (size_t)n);
+    for (uint32_t k = 0; k < n; ++k) std::memcpy(&e[4 * (size_t)k], materials[k].emissive, 16);
+    return e;
+}
+
+// The registry of mesh slices (hk_ctx::meshes): where slice x stands in it (reg.size(): nowhere), and the deepest BLAS
+// among the slices an instance carries
+static size_t find_slice(const std::vector<hk_ctx::MeshSlice>& reg, const hk_mesh_index& x)
+{
+    size_t k = 0;
+    while (k < reg.size() && std::memcmp(&reg[k].index, &x, sizeof(x)) != 0) ++k;
+    return k;
+}
+static uint32_t used_depth(const std::vector<hk_ctx::MeshSlice>& reg)
+{
+    uint32_t depth = 0;
+    for (const hk_ctx::MeshSlice& s : reg)
+        if (s.used) depth = std::max(depth, s.depth);
+    return depth;
 }
 
 // A mesh slice of a host-built scene as hk_update_meshes and hk_set_instances keep it: the vertices its primitives
@@ -1281,14 +1314,27 @@ static hk_ctx::MeshSlice host_mesh_slice(const hk_scene_desc* d, const hk_mesh_i
     return s;
 }
 
+// The registry of a host-built scene: the distinct slices its instances carry, in the order of their first use, each
+// with the instances that carry it.  false: an instance's node range is outside the asset nodes.
+static bool host_registry(const hk_scene_desc* d, std::vector<hk_ctx::MeshSlice>* reg)
+{
+    const hk_instance* inst = (const hk_instance*)d->instances.data;
+    reg->clear();
+    for (uint32_t k = 0; k < d->instances.count; ++k) {
+        const hk_mesh_index& m = inst[k].mesh;
+        if ((size_t)m.node[0] + m.node[1] > d->asset_nodes.count) return false;
+        const size_t at = find_slice(*reg, m);
+        if (at == reg->size()) reg->push_back(host_mesh_slice(d, m));
+        (*reg)[at].used++;
+    }
+    return true;
+}
+
 int hk_scene_stage_bytes(const hk_scene_desc* d, int plan, uint32_t* bytes, uint32_t* limit)
 {
     if (!d || (plan != PLAN_LIGHT && plan != PLAN_GBUFFER)) return HK_ERR_INVALID;
-    const uint32_t count[9] = {d->vertices.count,  d->primitives.count,     d->asset_nodes.count,
-                               d->alias_table.count, d->instances.count,    d->instance_nodes.count,
-                               d->materials.count, d->emissive_nodes.count, d->emissives.count};
     uint32_t b[SCENE_ARRAYS];
-    scene_array_bytes(count, b);
+    scene_array_bytes(desc_counts(d).data(), b);
     if (bytes) *bytes = stage_bytes(b, plan);
     if (limit) *limit = LDS_SCENE_MAX;
     return HK_OK;
@@ -1317,21 +1363,88 @@ int hk_scene_gbuffer_stack(const hk_scene_desc* d, uint32_t* need, uint32_t* lds
     return HK_OK;
 }
 
+// The buffers that are sized by a scene array's capacity beside the array itself: bytes per element of cap[array], and
+// the byte a new one is filled with (FOLLOWER_AUX, the three rows of blas_aux at stride cap[2]: U32_MAX behind the
+// registered nodes).  follower_slot: where the context keeps follower k.
+struct Follower {
+    int array;
+    size_t bytes;
+    int fill;
+};
+constexpr Follower FOLLOWERS[] = {{2, WIDE_NODE_BYTES, 0}, {2, sizeof(hk_node), 0}, {2, 12, 0xFF},
+                                  {5, WIDE_NODE_BYTES, 0}, {5, sizeof(hk_node), 0}, {4, 64, 0}};
+constexpr int N_FOLLOWERS = sizeof(FOLLOWERS) / sizeof(FOLLOWERS[0]), FOLLOWER_AUX = 2;
+static void** follower_slot(hk_ctx* c, int k)
+{
+    void** slot[N_FOLLOWERS] = {(void**)&c->blas_wide, (void**)&c->walk_nodes[0], (void**)&c->blas_aux,
+                                (void**)&c->tlas_wide, (void**)&c->walk_nodes[1], (void**)&c->prev_models};
+    return slot[k];
+}
+
+// device-only derivatives of the asset nodes, over the whole array of n_blas nodes: leaf boxes, the G-buffer wide layout
+// and the light walks' copy, leaf-collapsed (k_collapse_decide); the array itself stays as it is (hk_read_scene_array,
+// the wide layout and the instance rebuild read it)
+static void refresh_blas_derivatives(hk_ctx* c, hipStream_t st, uint32_t n_blas)
+{
+    launch_fill_leaves((hk_node*)c->buf[2], n_blas, c->blas_aux, (const hk_primitive*)c->buf[1], nullptr, 0, nullptr, 0,
+                       st);
+    launch_build_wide((const hk_node*)c->buf[2], n_blas, c->blas_aux + c->aux_stride, c->blas_aux + 2 * c->aux_stride,
+                      c->blas_wide, st);
+    (void)hipMemcpyAsync(c->walk_nodes[0], c->buf[2], (size_t)n_blas * sizeof(hk_node), hipMemcpyDeviceToDevice, st);
+    if (c->on(OPT_LEAF_COLLAPSE))
+        launch_collapse_leaves(c->walk_nodes[0], n_blas, c->blas_aux + c->aux_stride, c->blas_aux + 2 * c->aux_stride,
+                               c->collapse_scratch, st);
+}
+// the same of the TLAS, over the current instances and instance nodes
+static void refresh_tlas_derivatives(hk_ctx* c, hipStream_t st)
+{
+    const uint32_t n_tlas = c->count[5];
+    launch_fill_leaves(nullptr, 0, nullptr, nullptr, (hk_node*)c->buf[5], n_tlas, (const hk_instance*)c->buf[4],
+                       c->count[4], st);
+    launch_build_wide((const hk_node*)c->buf[5], n_tlas, nullptr, nullptr, c->tlas_wide, st);
+    (void)hipMemcpyAsync(c->walk_nodes[1], c->buf[5], (size_t)n_tlas * sizeof(hk_node), hipMemcpyDeviceToDevice, st);
+    if (c->on(OPT_LEAF_COLLAPSE))
+        launch_collapse_leaves(c->walk_nodes[1], n_tlas, nullptr, nullptr, c->collapse_scratch, st);
+}
+
+// The rows of the per-node mesh tables (blas_aux: primitive offset, node base, node count) over the node ranges of
+// `list`, in list order, on `st`: one copy per row and run of slices whose node ranges follow one another.  rows: the
+// host side of the copies, which the caller keeps past the call's wait.
+static int write_mesh_rows(hk_ctx* c, const hk_mesh_index* list, size_t n, hipStream_t st, std::vector<uint32_t>* rows)
+{
+    size_t total = 0;
+    for (size_t k = 0; k < n; ++k) total += list[k].node[1];
+    rows->resize(3 * total);
+    for (size_t k = 0, at = 0; k < n; at += list[k++].node[1]) {
+        const uint32_t value[3] = {list[k].primitive, list[k].node[0], list[k].node[1]};
+        for (size_t r = 0; r < 3; ++r) std::fill_n(rows->begin() + r * total + at, list[k].node[1], value[r]);
+    }
+    for (size_t k = 0, at = 0; k < n;) {
+        size_t end = k, len = 0;
+        do len += list[end++].node[1];
+        while (end < n && list[end].node[0] == list[end - 1].node[0] + list[end - 1].node[1]);
+        for (size_t r = 0; r < 3 && len; ++r)
+            HK_HIP(c, hipMemcpyAsync(c->blas_aux + r * c->aux_stride + list[k].node[0], rows->data() + r * total + at,
+                                     len * 4, hipMemcpyHostToDevice, st));
+        at += len;
+        k = end;
+    }
+    return HK_OK;
+}
+
 int hk_scene_upload(hk_ctx* c, const hk_scene_desc* d)
 {
     if (!c || !d) return HK_ERR_INVALID;
     (void)hipSetDevice(c->device);
     HK_TRY(c->sch.gb_serialize(true));
-    const hk_array* arr[9] = {&d->vertices, &d->primitives, &d->asset_nodes, &d->alias_table, &d->instances,
-                              &d->instance_nodes, &d->materials, &d->emissive_nodes, &d->emissives};
+    const std::array<const hk_array*, 9> arr = desc_arrays(d);
     const size_t* elem = SCENE_ELEM;
     if (d->instances.count == 0 || d->materials.count == 0)
         return fail(c, HK_ERR_INVALID, "scene needs at least one instance and one material");
     c->gen++;
     c->shared_transform = false;
     c->scene_box_valid = false;
-    for (int i = 0; i < 9; ++i)
-        if (arr[i]->count && !arr[i]->data) return fail(c, HK_ERR_INVALID, "scene array with count but no data");
+    if (!scene_desc_ok(d)) return fail(c, HK_ERR_INVALID, "scene array with count but no data");
     HK_HIP(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < 3; ++i) {
         release(c->spare[i]);
@@ -1346,18 +1459,17 @@ int hk_scene_upload(hk_ctx* c, const hk_scene_desc* d)
         c->count[i] = arr[i]->count;
         c->cap[i] = arr[i]->count ? arr[i]->count : 1;
     }
-    c->emissive.resize(4 * (size_t)d->materials.count);
-    for (uint32_t k = 0; k < d->materials.count; ++k)
-        std::memcpy(&c->emissive[4 * (size_t)k], ((const hk_material*)d->materials.data)[k].emissive, 16);
-    // leaf boxes of the device node copies (see k_fill_blas_leaves) and the wide layout of the
-    // G-buffer traversal: BLAS node -> primitive offset / node range of the mesh that owns it,
-    // from the instances' mesh indices
+    c->emissive = emissive_of((const hk_material*)d->materials.data, d->materials.count);
+    // the instanced meshes: each distinct slice once, with the vertices its primitives index and its BLAS depth
+    // (gb_blas_depth is the maximum of these)
+    if (!host_registry(d, &c->meshes)) return fail(c, HK_ERR_INVALID, "instance mesh node range outside asset nodes");
+    // BLAS node -> primitive offset / node range of the mesh that owns it (k_fill_blas_leaves, k_build_wide), from the
+    // instances' mesh indices: in instance order, so that the last instance wins where host-built slices overlap
     const uint32_t n_blas = d->asset_nodes.count, n_tlas = d->instance_nodes.count;
     std::vector<uint32_t> prim_offset(n_blas, HK_U32_MAX), node_base(n_blas, HK_U32_MAX), node_count(n_blas, 0);
     const hk_instance* inst = (const hk_instance*)d->instances.data;
     for (uint32_t k = 0; k < d->instances.count; ++k) {
         const hk_mesh_index& m = inst[k].mesh;
-        if ((size_t)m.node[0] + m.node[1] > n_blas) return fail(c, HK_ERR_INVALID, "instance mesh node range outside asset nodes");
         for (uint32_t j = 0; j < m.node[1]; ++j) {
             prim_offset[m.node[0] + j] = m.primitive;
             node_base[m.node[0] + j] = m.node[0];
@@ -1365,62 +1477,29 @@ int hk_scene_upload(hk_ctx* c, const hk_scene_desc* d)
         }
     }
     (void)scene_stack_need(d, &c->gb_stack_need, &c->gb_blas_depth);  // (node ranges checked above)
-    // the instanced meshes, for hk_update_meshes: each distinct slice once, with the vertices its primitives index
-    // and its BLAS depth (gb_blas_depth is the maximum of these)
-    c->meshes.clear();
-    std::map<std::array<uint32_t, 4>, size_t> seen;
-    for (uint32_t k = 0; k < d->instances.count; ++k) {
-        const hk_mesh_index& m = inst[k].mesh;
-        const auto at = seen.emplace(std::array<uint32_t, 4>{m.vertex, m.primitive, m.node[0], m.node[1]}, c->meshes.size());
-        if (at.second) c->meshes.push_back(host_mesh_slice(d, m));
-        c->meshes[at.first->second].used++;
-    }
     release(c->dyn_scratch);
     c->dyn_bytes = 0;
     release(c->mesh_scratch);
     c->mesh_bytes = 0;
-    release(c->blas_aux);
-    uint32_t*& d_aux = c->blas_aux;
-    const size_t stride = c->aux_stride = c->cap[2];
-    HK_HIP(c, hipMalloc(&d_aux, stride * 12));
-    if (n_blas) {
-        HK_HIP(c, hipMemcpy(d_aux, prim_offset.data(), (size_t)n_blas * 4, hipMemcpyHostToDevice));
-        HK_HIP(c, hipMemcpy(d_aux + stride, node_base.data(), (size_t)n_blas * 4, hipMemcpyHostToDevice));
-        HK_HIP(c, hipMemcpy(d_aux + 2 * stride, node_count.data(), (size_t)n_blas * 4, hipMemcpyHostToDevice));
+    // (the wide layouts and the walk-node copies are 64 and 32 bytes per node: whole 16-byte chunks for stage_scene
+    // without rounding)
+    for (int k = 0; k < N_FOLLOWERS; ++k) {
+        release(*follower_slot(c, k));
+        HK_HIP(c, hipMalloc(follower_slot(c, k), c->cap[FOLLOWERS[k].array] * FOLLOWERS[k].bytes));
     }
-    launch_fill_leaves((hk_node*)c->buf[2], n_blas, d_aux, (const hk_primitive*)c->buf[1], (hk_node*)c->buf[5],
-                       n_tlas, (const hk_instance*)c->buf[4], c->count[4], c->stream);
-    HK_HIP(c, hipGetLastError());
-    release(c->blas_wide);
-    release(c->tlas_wide);
-    release(c->walk_nodes[0]);
-    release(c->walk_nodes[1]);
     release(c->collapse_scratch);
-    // (the wide layouts and the walk-node copies below are 64 and 32 bytes per node: whole 16-byte chunks for
-    // stage_scene without rounding)
-    HK_HIP(c, hipMalloc(&c->blas_wide, (size_t)(n_blas ? n_blas : 1) * WIDE_NODE_BYTES));
-    HK_HIP(c, hipMalloc(&c->tlas_wide, (size_t)(n_tlas ? n_tlas : 1) * WIDE_NODE_BYTES));
-    launch_build_wide((const hk_node*)c->buf[2], n_blas, d_aux + stride, d_aux + 2 * stride, c->blas_wide, c->stream);
-    launch_build_wide((const hk_node*)c->buf[5], n_tlas, nullptr, nullptr, c->tlas_wide, c->stream);
-    // the light walks' node copies, leaf-collapsed (k_collapse_decide); the arrays above stay as
-    // uploaded (hk_read_scene_array, the wide layout and hk_update_instances read them)
-    HK_HIP(c, hipMalloc(&c->walk_nodes[0], (size_t)(n_blas ? n_blas : 1) * sizeof(hk_node)));
-    HK_HIP(c, hipMalloc(&c->walk_nodes[1], (size_t)(n_tlas ? n_tlas : 1) * sizeof(hk_node)));
     c->collapse_cap = std::max<uint32_t>(1u, std::max(n_blas, n_tlas));
     HK_HIP(c, hipMalloc(&c->collapse_scratch, c->collapse_cap * 4));
-    HK_HIP(c, hipMemcpyAsync(c->walk_nodes[0], c->buf[2], (size_t)n_blas * sizeof(hk_node), hipMemcpyDeviceToDevice,
-                             c->stream));
-    HK_HIP(c, hipMemcpyAsync(c->walk_nodes[1], c->buf[5], (size_t)n_tlas * sizeof(hk_node), hipMemcpyDeviceToDevice,
-                             c->stream));
-    if (c->on(OPT_LEAF_COLLAPSE)) {
-        launch_collapse_leaves(c->walk_nodes[0], n_blas, d_aux + stride, d_aux + 2 * stride, c->collapse_scratch,
-                               c->stream);
-        launch_collapse_leaves(c->walk_nodes[1], n_tlas, nullptr, nullptr, c->collapse_scratch, c->stream);
+    const size_t stride = c->aux_stride = c->cap[2];
+    if (n_blas) {
+        HK_HIP(c, hipMemcpy(c->blas_aux, prim_offset.data(), (size_t)n_blas * 4, hipMemcpyHostToDevice));
+        HK_HIP(c, hipMemcpy(c->blas_aux + stride, node_base.data(), (size_t)n_blas * 4, hipMemcpyHostToDevice));
+        HK_HIP(c, hipMemcpy(c->blas_aux + 2 * stride, node_count.data(), (size_t)n_blas * 4, hipMemcpyHostToDevice));
     }
+    refresh_blas_derivatives(c, c->stream, n_blas);
+    refresh_tlas_derivatives(c, c->stream);
     HK_HIP(c, hipGetLastError());
     // previous models = the uploaded ones (GlobalTransformQueue([matrix; 2]) for a new entity)
-    release(c->prev_models);
-    HK_HIP(c, hipMalloc(&c->prev_models, (size_t)d->instances.count * 64));
     HK_HIP(c, hipMemcpy2DAsync(c->prev_models, 64, (const char*)c->buf[4] + offsetof(hk_instance, model),
                                sizeof(hk_instance), 64, d->instances.count, hipMemcpyDeviceToDevice, c->stream));
     c->models_dirty = false;
@@ -1549,11 +1628,6 @@ static int plan_instance_set(const uint32_t* count, const std::vector<hk_ctx::Me
         *why = "too many instances";
         return HK_ERR_INVALID;
     }
-    std::map<std::array<uint32_t, 4>, uint32_t> at;
-    for (size_t k = 0; k < known.size(); ++k) {
-        const hk_mesh_index& m = known[k].index;
-        at.emplace(std::array<uint32_t, 4>{m.vertex, m.primitive, m.node[0], m.node[1]}, (uint32_t)k);
-    }
     out->set = set;
     out->slice.resize(n);
     out->fresh.clear();
@@ -1565,13 +1639,13 @@ static int plan_instance_set(const uint32_t* count, const std::vector<hk_ctx::Me
             *why = who + "material index out of range";
             return HK_ERR_INVALID;
         }
-        const std::array<uint32_t, 4> key{d.mesh.vertex, d.mesh.primitive, d.mesh.node[0], d.mesh.node[1]};
-        auto it = at.find(key);
-        if (it == at.end() && closed) {
+        size_t at = find_slice(known, d.mesh);
+        if (at == known.size()) at += find_slice(out->fresh, d.mesh);
+        if (at == known.size() + out->fresh.size() && closed) {
             *why = who + "its mesh is not in the new list";
             return HK_ERR_INVALID;
         }
-        if (it == at.end()) {
+        if (at == known.size() + out->fresh.size()) {
             hk_ctx::MeshSlice f;
             std::string text;
             const int rc = check_new_slice(d.mesh, count, known, out->fresh, rd, &f, &text);
@@ -1579,10 +1653,9 @@ static int plan_instance_set(const uint32_t* count, const std::vector<hk_ctx::Me
                 *why = who + "mesh slice refused: " + text;
                 return rc;
             }
-            it = at.emplace(key, (uint32_t)(known.size() + out->fresh.size())).first;
             out->fresh.push_back(f);
         }
-        out->slice[i] = it->second;
+        out->slice[i] = (uint32_t)at;
         if (material_emits(emissive + 4 * (size_t)d.material)) {
             n_em++;
             n_alias += (d.mesh.node[1] + 2u) / 3u;
@@ -1601,60 +1674,145 @@ static int plan_instance_set(const uint32_t* count, const std::vector<hk_ctx::Me
     return HK_OK;
 }
 
-// device-only derivatives of the asset nodes, over the whole array of n_blas nodes: leaf boxes, the G-buffer wide layout
-// and the light walks' copy with its leaf collapse (as hk_scene_upload derives them)
-static void refresh_blas_derivatives(hk_ctx* c, hipStream_t st, uint32_t n_blas)
+// Device buffers that are freed when the scope that holds them ends
+struct Buffers {
+    std::vector<void*> p;
+    ~Buffers()
+    {
+        for (void* q : p) (void)hipFree(q);
+    }
+};
+
+// Room for the counts after a call (hikari_amd.h "Capacity" of hk_set_instances, hk_add_meshes and hk_set_meshes), on
+// `st` ahead of the kernels that write the arrays.  grow: the arrays (bits) that may be allocated anew, each only when
+// its count passes its capacity, and then at max(count, 1.5 x capacity), with the buffers that follow it
+// (FOLLOWERS); collapse_scratch by the same rule, mesh_scratch and dyn_scratch to the bytes asked for.  keep: the
+// arrays (bits) whose contents move into a new buffer; of the others a new buffer is zeroed whole and one that stays
+// gets staged_alloc_bytes' zeroed tail behind its new count, their records being rewritten by the caller's kernels.
+// spares: arrays 0-2 are written out of place (hk_set_meshes): each gets its spare, allocated anew only where it is
+// smaller than the capacity asked for, and zeroed behind the new count; the array it was becomes the spare
+// (c->spare[i] afterwards: where the kernels read the old contents).
+// First every allocation, with the context untouched: a failure frees them and leaves the context as it was.  Then
+// the pointers, so that nothing allocated is lost on a failed enqueue, then the fills and copies.  The buffers that
+// were replaced go to `old`, which the caller holds past the call's wait: work in flight, and a gather of the
+// previous models as they were (prev_models), may still read them.
+static int reserve_scene(hk_ctx* c, const char* who, const uint32_t* counts, uint32_t grow, uint32_t keep, bool spares,
+                         size_t mesh_need, size_t dyn_need, hipStream_t st, Buffers* old)
 {
-    launch_fill_leaves((hk_node*)c->buf[2], n_blas, c->blas_aux, (const hk_primitive*)c->buf[1], nullptr, 0, nullptr, 0,
-                       st);
-    launch_build_wide((const hk_node*)c->buf[2], n_blas, c->blas_aux + c->aux_stride, c->blas_aux + 2 * c->aux_stride,
-                      c->blas_wide, st);
-    (void)hipMemcpyAsync(c->walk_nodes[0], c->buf[2], (size_t)n_blas * sizeof(hk_node), hipMemcpyDeviceToDevice, st);
-    if (c->on(OPT_LEAF_COLLAPSE))
-        launch_collapse_leaves(c->walk_nodes[0], n_blas, c->blas_aux + c->aux_stride, c->blas_aux + 2 * c->aux_stride,
-                               c->collapse_scratch, st);
+    Buffers fresh;
+    bool ok = true;
+    auto grown = [](size_t need, size_t cap) { return std::max(need, cap + cap / 2); };
+    auto alloc = [&](size_t bytes) -> void* {
+        void* nb = nullptr;
+        ok = ok && hipMalloc(&nb, bytes) == hipSuccess;
+        if (ok) fresh.p.push_back(nb);
+        return nb;
+    };
+    size_t cap[9];
+    void *nbuf[9] = {}, *nfol[N_FOLLOWERS] = {};
+    for (int i = 0; i < 9; ++i) {
+        cap[i] = c->cap[i];
+        if (!(grow >> i & 1u)) continue;
+        if (counts[i] > cap[i]) cap[i] = grown(counts[i], cap[i]);
+        const bool spare = spares && i < 3;
+        if (spare && c->spare_cap[i] >= cap[i]) cap[i] = c->spare_cap[i];
+        else if (spare || cap[i] != c->cap[i]) nbuf[i] = alloc(staged_alloc_bytes(cap[i], SCENE_ELEM[i]));
+    }
+    for (int k = 0; k < N_FOLLOWERS; ++k) {
+        const Follower& f = FOLLOWERS[k];
+        if (cap[f.array] != c->cap[f.array]) nfol[k] = alloc(cap[f.array] * f.bytes);
+    }
+    const size_t collapse_need = std::max<size_t>(1, std::max(counts[2], counts[5]));
+    const size_t collapse_cap = collapse_need > c->collapse_cap ? grown(collapse_need, c->collapse_cap) : c->collapse_cap;
+    void* n_collapse = collapse_cap != c->collapse_cap ? alloc(collapse_cap * 4) : nullptr;
+    void* n_mesh = c->mesh_bytes < mesh_need ? alloc(mesh_need) : nullptr;
+    void* n_dyn = c->dyn_bytes < dyn_need ? alloc(dyn_need) : nullptr;
+    if (!ok) return fail(c, HK_ERR_HIP, std::string(who) + ": out of device memory");
+    fresh.p.clear();  // (all of them go into the context below)
+    auto put = [&](void** slot, void* nb) {
+        if (*slot) old->p.push_back(*slot);
+        *slot = nb;
+    };
+    const void *buf_was[9], *fol_was[N_FOLLOWERS];
+    for (int i = 0; i < 9; ++i) {
+        buf_was[i] = c->buf[i];
+        if (spares && i < 3 && (grow >> i & 1u)) {
+            if (nbuf[i]) {
+                put(&c->spare[i], nbuf[i]);
+                c->spare_cap[i] = cap[i];
+            }
+            std::swap(c->buf[i], c->spare[i]);
+            std::swap(c->cap[i], c->spare_cap[i]);
+        } else if (nbuf[i]) {
+            put(&c->buf[i], nbuf[i]);
+            c->cap[i] = cap[i];
+        }
+    }
+    for (int k = 0; k < N_FOLLOWERS; ++k) {
+        fol_was[k] = *follower_slot(c, k);
+        if (nfol[k]) put(follower_slot(c, k), nfol[k]);
+    }
+    const size_t stride_was = c->aux_stride;
+    c->aux_stride = c->cap[2];
+    if (n_collapse) {
+        put((void**)&c->collapse_scratch, n_collapse);
+        c->collapse_cap = collapse_cap;
+    }
+    if (n_mesh) {
+        put(&c->mesh_scratch, n_mesh);
+        c->mesh_bytes = mesh_need;
+    }
+    if (n_dyn) {
+        put(&c->dyn_scratch, n_dyn);
+        c->dyn_bytes = dyn_need;
+    }
+    for (int i = 0; i < 9; ++i) {
+        if (!(grow >> i & 1u)) continue;
+        const bool kept = keep >> i & 1u;
+        const size_t have = (size_t)c->count[i] * SCENE_ELEM[i];
+        // staged_alloc_bytes' tail behind the new count reads zero (an empty array keeps one zeroed element): of a
+        // buffer that is new to the array, all that is behind the count
+        const bool swapped = nbuf[i] || (spares && i < 3);
+        const size_t end = staged_alloc_bytes(swapped ? c->cap[i] : counts[i], SCENE_ELEM[i]);
+        const size_t at = nbuf[i] ? 0 : kept ? end : (size_t)counts[i] * SCENE_ELEM[i];
+        if (end > at) HK_HIP(c, hipMemsetAsync((char*)c->buf[i] + at, 0, end - at, st));
+        if (nbuf[i] && kept && have) HK_HIP(c, hipMemcpyAsync(nbuf[i], buf_was[i], have, hipMemcpyDeviceToDevice, st));
+    }
+    for (int k = 0; k < N_FOLLOWERS; ++k) {
+        const Follower& f = FOLLOWERS[k];
+        if (!nfol[k]) continue;
+        HK_HIP(c, hipMemsetAsync(nfol[k], f.fill, c->cap[f.array] * f.bytes, st));
+        const size_t have = keep >> f.array & 1u ? c->count[f.array] : 0;
+        if (!have) continue;
+        if (k != FOLLOWER_AUX) HK_HIP(c, hipMemcpyAsync(nfol[k], fol_was[k], have * f.bytes, hipMemcpyDeviceToDevice, st));
+        for (size_t r = 0; r < 3 && k == FOLLOWER_AUX; ++r)  // the per-node mesh tables, re-laid at the new stride
+            HK_HIP(c, hipMemcpyAsync((uint32_t*)nfol[k] + r * c->aux_stride, (const uint32_t*)fol_was[k] + r * stride_was,
+                                     have * 4, hipMemcpyDeviceToDevice, st));
+    }
+    return HK_OK;
 }
 
-// Room for the counts of a new set (hikari_amd.h hk_set_instances "Capacity"): an array whose count passes its
-// capacity is allocated anew, zeroed, at max(count, 1.5 x capacity); its records are all rewritten by the rebuild.
-// *old_prev: the previous models of the set before, where they moved (the gather reads them; the caller frees).
-static int reserve_set(hk_ctx* c, const uint32_t* counts, float** old_prev)
+// A scratch block carved into parts of the given bytes, each rounded up to 256: the bytes they take together, and the
+// parts' pointers in *scratch, which is allocated anew (to exactly that) where it holds fewer than that
+static size_t carve_bytes(const size_t* bytes, int n)
 {
-    auto grown = [](size_t need, size_t cap) { return std::max(need, cap + cap / 2); };
-    auto fresh = [&](void** p, size_t bytes) {
-        void* nb = nullptr;
-        if (hipMalloc(&nb, bytes) != hipSuccess) return false;
-        if (hipMemset(nb, 0, bytes) != hipSuccess) {
-            (void)hipFree(nb);
-            return false;
-        }
-        if (*p) (void)hipFree(*p);
-        *p = nb;
-        return true;
-    };
-    for (int i : {3, 4, 5, 7, 8}) {
-        if (counts[i] <= c->cap[i]) continue;
-        const size_t cap = grown(counts[i], c->cap[i]);
-        bool ok = true;
-        if (i == 5)
-            ok = fresh((void**)&c->tlas_wide, cap * WIDE_NODE_BYTES) && fresh((void**)&c->walk_nodes[1], cap * sizeof(hk_node));
-        if (i == 4) {
-            void* np = nullptr;
-            ok = fresh(&np, cap * 64);
-            if (ok) {
-                *old_prev = c->prev_models;
-                c->prev_models = (float*)np;
-            }
-        }
-        if (!ok || !fresh(&c->buf[i], staged_alloc_bytes(cap, SCENE_ELEM[i])))
-            return fail(c, HK_ERR_HIP, "hk_set_instances: out of device memory");
-        c->cap[i] = cap;
+    size_t total = 0;
+    for (int k = 0; k < n; ++k) total += (bytes[k] + 255) & ~(size_t)255;
+    return total;
+}
+static int carve(hk_ctx* c, void** scratch, size_t* have, const size_t* bytes, int n, char** part)
+{
+    const size_t total = carve_bytes(bytes, n);
+    if (*have < total) {
+        release(*scratch);
+        *have = 0;
+        HK_HIP(c, hipMalloc(scratch, total));
+        *have = total;
     }
-    const size_t need = std::max<size_t>(1, std::max(c->count[2], counts[5]));
-    if (need > c->collapse_cap) {
-        const size_t cap = grown(need, c->collapse_cap);
-        if (!fresh((void**)&c->collapse_scratch, cap * 4)) return fail(c, HK_ERR_HIP, "hk_set_instances: out of device memory");
-        c->collapse_cap = cap;
+    char* p = (char*)*scratch;
+    for (int k = 0; k < n; ++k) {
+        part[k] = p;
+        p += carve_bytes(bytes + k, 1);
     }
     return HK_OK;
 }
@@ -1667,70 +1825,48 @@ static int rebuild_instances(hk_ctx* c, const float* models, const float* local_
 {
     HK_TRY(c->sch.gb_join(st));
     HK_TRY(c->sch.gb_serialize(false));
+    const uint32_t* counts = set ? set->counts : c->count;
+    const uint32_t n = count, m = counts[8], n_alias = counts[3];
+    const uint32_t nm = n > m ? n : m;
+    const size_t ns = set ? n : 0;  // (scratch of a set change only)
+    const size_t sz[] = {(size_t)n * 64, (size_t)n * 24, (size_t)(n_alias ? n_alias : 1) * 4,
+                         (size_t)(n_alias ? n_alias : 1) * 16, (size_t)nm * 24, (size_t)nm * 8, (size_t)nm * 24,
+                         (size_t)3 * n * 4, 16, ns * sizeof(InstanceDesc), ns * 64, ns * 8};
+    constexpr int PARTS = sizeof(sz) / sizeof(sz[0]);
+    // what reserve_scene replaced, freed on every way out: the gather reads the previous models of the set before
+    // where they were
+    Buffers old;
+    const float* prev_before = c->prev_models;
+    const uint32_t n_before = c->count[4];
+    std::vector<uint32_t> rows;  // (write_mesh_rows' host side, alive past the wait)
+    if (set)  // (first, so that a failed allocation leaves the context as it was)
+        HK_TRY(reserve_scene(c, "hk_set_instances", counts, 1u << 3 | 1u << 4 | 1u << 5 | 1u << 7 | 1u << 8, 0, false, 0,
+                             carve_bytes(sz, PARTS), st, &old));
     c->gen++;
     c->shared_transform = false;  // (the general walks, should this call fail half-way)
     c->scene_box_valid = false;   // (likewise: no tile skip)
-    struct Moved {  // the previous models of the set before, where reserve_set moved them: freed on every way out
-        float* p = nullptr;
-        ~Moved() { release(p); }
-    } old_prev;
-    const uint32_t n_before = c->count[4];
     if (set) {
-        HK_TRY(reserve_set(c, set->counts, &old_prev.p));
         if (!set->fresh.empty()) {  // register the new slices: their rows of the per-node mesh tables, then the derivatives
+            std::vector<hk_mesh_index> list;
             for (const hk_ctx::MeshSlice& f : set->fresh) {
-                const hk_mesh_index& x = f.index;
-                const uint32_t value[3] = {x.primitive, x.node[0], x.node[1]};
-                std::vector<uint32_t> row(x.node[1]);
-                for (int k = 0; k < 3; ++k) {
-                    std::fill(row.begin(), row.end(), value[k]);
-                    HK_HIP(c, hipMemcpy(c->blas_aux + k * c->aux_stride + x.node[0], row.data(), row.size() * 4,
-                                        hipMemcpyHostToDevice));
-                }
+                list.push_back(f.index);
                 c->meshes.push_back(f);
             }
+            HK_TRY(write_mesh_rows(c, list.data(), list.size(), st, &rows));
             refresh_blas_derivatives(c, st, c->count[2]);
         }
         for (hk_ctx::MeshSlice& s : c->meshes) s.used = 0;
         for (uint32_t k : set->slice) c->meshes[k].used++;
-        c->gb_blas_depth = 0;
-        for (const hk_ctx::MeshSlice& s : c->meshes)
-            if (s.used) c->gb_blas_depth = std::max(c->gb_blas_depth, s.depth);
-        for (int i : {3, 4, 5, 7, 8}) {
-            c->count[i] = set->counts[i];
-            // staged_alloc_bytes' zeroed tail behind the new count (an empty array keeps one zeroed element)
-            const size_t at = (size_t)c->count[i] * SCENE_ELEM[i], end = staged_alloc_bytes(c->count[i], SCENE_ELEM[i]);
-            if (end > at) HK_HIP(c, hipMemsetAsync((char*)c->buf[i] + at, 0, end - at, st));
-        }
+        c->gb_blas_depth = used_depth(c->meshes);
+        for (int i : {3, 4, 5, 7, 8}) c->count[i] = counts[i];
         if (set->materials) {
-            for (uint32_t k = 0; k < c->count[6]; ++k) std::memcpy(&c->emissive[4 * (size_t)k], set->materials[k].emissive, 16);
+            c->emissive = emissive_of(set->materials, c->count[6]);
             HK_HIP(c, hipMemcpyAsync(c->buf[6], set->materials, (size_t)c->count[6] * sizeof(hk_material),
                                      hipMemcpyHostToDevice, st));
         }
     }
-    const uint32_t n = count, m = c->count[8], n_alias = c->count[3];
-    const uint32_t nm = n > m ? n : m;
-    const size_t ns = set ? n : 0;  // (scratch of a set change only)
-    auto align = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t sz[] = {align((size_t)n * 64), align((size_t)n * 24), align((size_t)(n_alias ? n_alias : 1) * 4),
-                         align((size_t)(n_alias ? n_alias : 1) * 16), align((size_t)nm * 24), align((size_t)nm * 8),
-                         align((size_t)nm * 24), align((size_t)3 * n * 4), align(16),
-                         align(ns * sizeof(InstanceDesc)), align(ns * 64), align(ns * 8)};
-    constexpr int PARTS = sizeof(sz) / sizeof(sz[0]);
-    size_t total = 0;
-    for (size_t b : sz) total += b;
-    if (c->dyn_bytes < total) {
-        release(c->dyn_scratch);
-        c->dyn_bytes = 0;
-        HK_HIP(c, hipMalloc(&c->dyn_scratch, total));
-        c->dyn_bytes = total;
-    }
-    char* p = (char*)c->dyn_scratch;
     char* part[PARTS];
-    for (int k = 0; k < PARTS; ++k) {
-        part[k] = p;
-        p += sz[k];
-    }
+    HK_TRY(carve(c, &c->dyn_scratch, &c->dyn_bytes, sz, PARTS, part));
     HK_HIP(c, hipMemcpyAsync(part[0], models, (size_t)n * 64, hipMemcpyHostToDevice, st));
     HK_HIP(c, hipMemcpyAsync(part[1], local_aabbs, (size_t)n * 24, hipMemcpyHostToDevice, st));
     HK_HIP(c, hipMemsetAsync(part[8], 0, 16, st));
@@ -1757,7 +1893,7 @@ static int rebuild_instances(hk_ctx* c, const float* models, const float* local_
     D.flags = (uint32_t*)part[8];
     SetArgs S;
     S.set = (const InstanceDesc*)part[9];
-    S.prev_models = old_prev.p ? old_prev.p : c->prev_models;
+    S.prev_models = prev_before;
     S.n_prev = n_before;
     S.new_prev = (float*)part[10];
     S.emitter = (uint2*)part[11];
@@ -1768,14 +1904,7 @@ static int rebuild_instances(hk_ctx* c, const float* models, const float* local_
         } else {
             launch_dynamic_update(D, st);
         }
-        // device-only derivatives of the TLAS: leaf boxes and the G-buffer wide layout
-        launch_fill_leaves(nullptr, 0, nullptr, nullptr, (hk_node*)c->buf[5], c->count[5], (const hk_instance*)c->buf[4],
-                           n, st);
-        launch_build_wide((const hk_node*)c->buf[5], c->count[5], nullptr, nullptr, c->tlas_wide, st);
-        (void)hipMemcpyAsync(c->walk_nodes[1], c->buf[5], (size_t)c->count[5] * sizeof(hk_node), hipMemcpyDeviceToDevice,
-                             st);
-        if (c->on(OPT_LEAF_COLLAPSE))
-            launch_collapse_leaves(c->walk_nodes[1], c->count[5], nullptr, nullptr, c->collapse_scratch, st);
+        refresh_tlas_derivatives(c, st);
     });
     HK_HIP(c, hipGetLastError());
     uint32_t flags[4] = {0, 0, 0, 0};
@@ -1785,9 +1914,7 @@ static int rebuild_instances(hk_ctx* c, const float* models, const float* local_
     HK_HIP(c, hipStreamSynchronize(st));
     if (ml) {  // the deepest instanced BLAS now: a mesh that became shallower lowers the bound
         for (size_t k = 0; k < levels.size(); ++k) c->meshes[ml->slice[k]].depth = levels[k];
-        c->gb_blas_depth = 0;
-        for (const hk_ctx::MeshSlice& s : c->meshes)
-            if (s.used) c->gb_blas_depth = std::max(c->gb_blas_depth, s.depth);
+        c->gb_blas_depth = used_depth(c->meshes);
     }
     if (ml || set) c->gb_stack_need = flags[1] + c->gb_blas_depth;
     if (set && (flags[2] != m || flags[3] != n_alias))
@@ -1807,14 +1934,20 @@ static int rebuild_instances(hk_ctx* c, const float* models, const float* local_
     return HK_OK;
 }
 
+// the TLAS and the light BVH are 3n - 2 nodes over their n leaves, as the device builds them
+static int scene_rebuildable(hk_ctx* c)
+{
+    if (c->count[5] != 3u * c->count[4] - 2u || (c->count[8] && c->count[7] != 3u * c->count[8] - 2u))
+        return fail(c, HK_ERR_STATE, "scene BVHs are not bvh-0.7.1 flattened (3n - 2 nodes); cannot rebuild");
+    return HK_OK;
+}
+
 // the checks hk_update_instances and hk_update_meshes share; HK_OK: the scene can be rebuilt with `count` instances
 static int update_args_ok(hk_ctx* c, uint32_t count, const char* who)
 {
     if (!c->has_scene) return fail(c, HK_ERR_STATE, "no scene uploaded (hk_scene_upload)");
     if (count != c->count[4]) return fail(c, HK_ERR_INVALID, std::string(who) + " needs every instance, in upload order");
-    if (c->count[5] != 3u * count - 2u || (c->count[8] && c->count[7] != 3u * c->count[8] - 2u))
-        return fail(c, HK_ERR_STATE, "scene BVHs are not bvh-0.7.1 flattened (3n - 2 nodes); cannot rebuild");
-    return HK_OK;
+    return scene_rebuildable(c);
 }
 
 int hk_update_instances(hk_ctx* c, const float* models, const float* local_aabbs, uint32_t count, void* stream)
@@ -1825,14 +1958,120 @@ int hk_update_instances(hk_ctx* c, const float* models, const float* local_aabbs
     return rebuild_instances(c, models, local_aabbs, count, pick(c, stream), nullptr);
 }
 
+// Meshes on their way to a build (hk_update_meshes, hk_add_meshes and the new entries of hk_set_meshes): the tables in
+// list order and by size, where each mesh's indices lie, and the bytes of scratch they, the attribute and index streams
+// and the builds' shape boxes, indices, segments and levels take (sz: one entry per part; the last is the caller's
+// own, `extra` bytes).
+struct MeshStaging {
+    std::vector<MeshUpdate> tab, by_size;
+    std::vector<MeshSource> sources;
+    uint32_t n_lds = 0, n_vertices = 0, n_shapes = 0, n_indices = 0;
+    static constexpr int PARTS = 12;
+    size_t sz[PARTS] = {};
+    size_t total = 0;
+};
+
+// meshes[k] goes to slices[k] with tris[k] triangles.  A deformed mesh (hk_update_meshes) has no uvs and no indices,
+// and may have no normals: MeshUpdate::has_normals says so, and its part of the normal stream is left unwritten.
+static void plan_mesh_staging(const std::vector<const hk_mesh_desc*>& meshes, const hk_mesh_index* slices,
+                              const uint32_t* tris, uint64_t n_vertices, uint64_t n_shapes, uint64_t n_indices,
+                              size_t extra, MeshStaging* S)
+{
+    const uint32_t n = (uint32_t)meshes.size();
+    S->tab.resize(n);
+    S->sources.resize(n);
+    S->n_vertices = (uint32_t)n_vertices;
+    S->n_shapes = (uint32_t)n_shapes;
+    S->n_indices = (uint32_t)n_indices;
+    uint32_t v0 = 0, s0 = 0, i0 = 0;
+    bool uvs = false;
+    for (uint32_t k = 0; k < n; ++k) {
+        const hk_mesh_index& x = slices[k];
+        const hk_mesh_desc& m = *meshes[k];
+        S->tab[k] = MeshUpdate{x.vertex, m.vertex_count, x.primitive, tris[k], x.node[0], v0, s0, k, m.normals ? 1u : 0u};
+        S->sources[k] = MeshSource{m.indices ? i0 : MESH_NO_INDICES, m.topology == HKS_TRIANGLE_STRIP ? 1u : 0u};
+        v0 += m.vertex_count;
+        s0 += tris[k];
+        if (m.indices) i0 += m.index_count;
+        uvs = uvs || m.uvs;
+        S->n_lds += tris[k] <= mesh_lds_shapes() ? 1u : 0u;
+    }
+    for (int big = 0; big < 2; ++big)
+        for (const MeshUpdate& m : S->tab)
+            if ((m.shapes > mesh_lds_shapes()) == (big == 1)) S->by_size.push_back(m);
+    const size_t nv = S->n_vertices, ns = S->n_shapes;
+    const size_t sz[MeshStaging::PARTS] = {(size_t)n * sizeof(MeshUpdate), (size_t)n * sizeof(MeshUpdate),
+                                           (size_t)n * sizeof(MeshSource), nv * 12, nv * 12, uvs ? nv * 8 : 0,
+                                           (size_t)(S->n_indices ? S->n_indices : 1) * 4, ns * 24, ns * 8, ns * 24,
+                                           (size_t)n * 4, extra};
+    std::memcpy(S->sz, sz, sizeof(sz));
+    S->total = carve_bytes(sz, MeshStaging::PARTS);
+}
+
+// The tables and streams copied into c->mesh_scratch on `st`, and the launch arguments over them, the destinations
+// c->buf[0..2].  *extra: the caller's part.
+static int enqueue_mesh_staging(hk_ctx* c, const std::vector<const hk_mesh_desc*>& meshes, const MeshStaging& S,
+                                hipStream_t st, MeshAddArgs* A, char** extra)
+{
+    char* part[MeshStaging::PARTS];
+    HK_TRY(carve(c, &c->mesh_scratch, &c->mesh_bytes, S.sz, MeshStaging::PARTS, part));
+    const size_t n = meshes.size();
+    if (n) {
+        HK_HIP(c, hipMemcpyAsync(part[0], S.tab.data(), n * sizeof(MeshUpdate), hipMemcpyHostToDevice, st));
+        HK_HIP(c, hipMemcpyAsync(part[1], S.by_size.data(), n * sizeof(MeshUpdate), hipMemcpyHostToDevice, st));
+        HK_HIP(c, hipMemcpyAsync(part[2], S.sources.data(), n * sizeof(MeshSource), hipMemcpyHostToDevice, st));
+    }
+    for (size_t k = 0; k < n; ++k) {
+        const hk_mesh_desc& m = *meshes[k];
+        const size_t v0 = S.tab[k].vertex0, nv = m.vertex_count;
+        const struct {
+            int part;
+            const float* from;
+            size_t bytes;
+        } streams[] = {{3, m.positions, 12}, {4, m.normals, 12}, {5, m.uvs, 8}};
+        for (const auto& a : streams)
+            if (nv && a.from)
+                HK_HIP(c, hipMemcpyAsync(part[a.part] + v0 * a.bytes, a.from, nv * a.bytes, hipMemcpyHostToDevice, st));
+        if (m.indices)
+            HK_HIP(c, hipMemcpyAsync(part[6] + (size_t)S.sources[k].index0 * 4, m.indices, (size_t)m.index_count * 4,
+                                     hipMemcpyHostToDevice, st));
+    }
+    MeshUpdateArgs& M = A->M;
+    M.table = (const MeshUpdate*)part[0];
+    M.table_by_size = (const MeshUpdate*)part[1];
+    M.n_meshes = (uint32_t)n;
+    M.n_lds = S.n_lds;
+    M.n_vertices = S.n_vertices;
+    M.n_shapes = S.n_shapes;
+    M.positions = (const float*)part[3];
+    M.normals = (const float*)part[4];
+    M.vertices = (hk_vertex*)c->buf[0];
+    M.primitives = (hk_primitive*)c->buf[1];
+    M.blas = (hk_node*)c->buf[2];
+    M.buckets = 6;  // bvh 0.7.1 NUM_BUCKETS (hks_build default)
+    M.shapes = part[7];
+    M.idx = (uint32_t*)part[8];
+    M.segments = part[9];
+    M.levels = (uint32_t*)part[10];
+    A->sources = (const MeshSource*)part[2];
+    A->uvs = (const float*)part[5];
+    A->indices = (const uint32_t*)part[6];
+    if (extra) *extra = part[11];
+    return HK_OK;
+}
+
 int hk_update_meshes(hk_ctx* c, const hk_mesh_update* meshes, uint32_t mesh_count, const float* models,
                      const float* local_aabbs, uint32_t count, void* stream)
 {
     if (!c) return HK_ERR_INVALID;
     if (!meshes || !models || !local_aabbs) return fail(c, HK_ERR_INVALID, "hk_update_meshes: null pointer");
     HK_TRY(update_args_ok(c, count, "hk_update_meshes"));
-    // every listed mesh against what upload recorded (no device work before the list is accepted whole)
-    std::vector<MeshUpdate> tab(mesh_count);
+    // every listed mesh against what upload recorded (no device work before the list is accepted whole): a staged mesh
+    // without uvs and indices
+    std::vector<hk_mesh_desc> descs(mesh_count);
+    std::vector<const hk_mesh_desc*> list(mesh_count);
+    std::vector<hk_mesh_index> slices(mesh_count);
+    std::vector<uint32_t> tris(mesh_count);
     MeshLevels ml;
     ml.slice.resize(mesh_count);
     uint32_t n_vertices = 0, n_shapes = 0;
@@ -1840,9 +2079,7 @@ int hk_update_meshes(hk_ctx* c, const hk_mesh_update* meshes, uint32_t mesh_coun
         const hk_mesh_update& u = meshes[k];
         const std::string who = "hk_update_meshes: mesh " + std::to_string(k);
         if (!u.positions) return fail(c, HK_ERR_INVALID, who + " has no positions");
-        size_t at = c->meshes.size();
-        for (size_t j = 0; j < c->meshes.size(); ++j)
-            if (std::memcmp(&c->meshes[j].index, &u.mesh, sizeof(u.mesh)) == 0) at = j;
+        const size_t at = find_slice(c->meshes, u.mesh);
         if (at == c->meshes.size()) return fail(c, HK_ERR_INVALID, who + " is not an instanced mesh of the uploaded scene");
         for (uint32_t j = 0; j < k; ++j)
             if (ml.slice[j] == at) return fail(c, HK_ERR_INVALID, who + " is listed twice");
@@ -1857,74 +2094,31 @@ int hk_update_meshes(hk_ctx* c, const hk_mesh_update* meshes, uint32_t mesh_coun
             return fail(c, HK_ERR_INVALID, who + ": vertex_count does not cover the vertex indices of its primitives");
         if (u.vertex_count > room)
             return fail(c, HK_ERR_INVALID, who + ": vertex_count reaches past its vertex slice");
-        const uint32_t tris = (u.mesh.node[1] + 2u) / 3u;
-        if ((size_t)n_vertices + u.vertex_count > 0x40000000u || (size_t)n_shapes + tris > 0x40000000u)
+        tris[k] = (u.mesh.node[1] + 2u) / 3u;
+        if ((size_t)n_vertices + u.vertex_count > 0x40000000u || (size_t)n_shapes + tris[k] > 0x40000000u)
             return fail(c, HK_ERR_INVALID, "hk_update_meshes: too many vertices or primitives in one call");
-        tab[k] = MeshUpdate{u.mesh.vertex, u.vertex_count, u.mesh.primitive, tris, u.mesh.node[0],
-                            n_vertices,    n_shapes,       k,                u.normals ? 1u : 0u};
+        descs[k] = hk_mesh_desc{u.positions, u.normals, nullptr, u.vertex_count, nullptr, 0u, HKS_TRIANGLE_LIST};
+        list[k] = &descs[k];
+        slices[k] = u.mesh;
         ml.slice[k] = (uint32_t)at;
         n_vertices += u.vertex_count;
-        n_shapes += tris;
+        n_shapes += tris[k];
     }
     (void)hipSetDevice(c->device);
     hipStream_t st = pick(c, stream);
     if (mesh_count == 0) return rebuild_instances(c, models, local_aabbs, count, st, nullptr);
     HK_TRY(c->sch.gb_join(st));
     HK_TRY(c->sch.gb_serialize(false));
-    std::vector<MeshUpdate> by_size;
-    for (int big = 0; big < 2; ++big)
-        for (const MeshUpdate& m : tab)
-            if ((m.shapes > mesh_lds_shapes()) == (big == 1)) by_size.push_back(m);
-    uint32_t n_lds = 0;
-    for (const MeshUpdate& m : tab) n_lds += m.shapes <= mesh_lds_shapes() ? 1u : 0u;
-    auto align = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t sz[] = {align((size_t)mesh_count * sizeof(MeshUpdate)), align((size_t)mesh_count * sizeof(MeshUpdate)),
-                         align((size_t)n_vertices * 12),  align((size_t)n_vertices * 12),
-                         align((size_t)n_shapes * 24),    align((size_t)n_shapes * 8),
-                         align((size_t)n_shapes * 24),    align((size_t)mesh_count * 4)};
-    size_t total = 0;
-    for (size_t b : sz) total += b;
-    if (c->mesh_bytes < total) {
-        release(c->mesh_scratch);
-        HK_HIP(c, hipMalloc(&c->mesh_scratch, total));
-        c->mesh_bytes = total;
-    }
-    char* part[8];
-    char* p = (char*)c->mesh_scratch;
-    for (int k = 0; k < 8; ++k) {
-        part[k] = p;
-        p += sz[k];
-    }
-    HK_HIP(c, hipMemcpyAsync(part[0], tab.data(), tab.size() * sizeof(MeshUpdate), hipMemcpyHostToDevice, st));
-    HK_HIP(c, hipMemcpyAsync(part[1], by_size.data(), by_size.size() * sizeof(MeshUpdate), hipMemcpyHostToDevice, st));
-    for (uint32_t k = 0; k < mesh_count; ++k) {
-        const size_t at = (size_t)tab[k].vertex0 * 12, bytes = (size_t)tab[k].vertex_count * 12;
-        HK_HIP(c, hipMemcpyAsync(part[2] + at, meshes[k].positions, bytes, hipMemcpyHostToDevice, st));
-        if (meshes[k].normals) HK_HIP(c, hipMemcpyAsync(part[3] + at, meshes[k].normals, bytes, hipMemcpyHostToDevice, st));
-    }
-    MeshUpdateArgs M;
-    M.table = (const MeshUpdate*)part[0];
-    M.table_by_size = (const MeshUpdate*)part[1];
-    M.n_meshes = mesh_count;
-    M.n_lds = n_lds;
-    M.n_vertices = n_vertices;
-    M.n_shapes = n_shapes;
-    M.positions = (const float*)part[2];
-    M.normals = (const float*)part[3];
-    M.vertices = (hk_vertex*)c->buf[0];
-    M.primitives = (hk_primitive*)c->buf[1];
-    M.blas = (hk_node*)c->buf[2];
-    M.buckets = 6;  // bvh 0.7.1 NUM_BUCKETS (hks_build default)
-    M.shapes = part[4];
-    M.idx = (uint32_t*)part[5];
-    M.segments = part[6];
-    M.levels = (uint32_t*)part[7];
+    MeshStaging stage;
+    plan_mesh_staging(list, slices.data(), tris.data(), n_vertices, n_shapes, 0, 0, &stage);
+    MeshAddArgs A;
+    HK_TRY(enqueue_mesh_staging(c, list, stage, st, &A, nullptr));
     timed(c, "update_meshes", st, [&] {
-        launch_mesh_update(M, st);
+        launch_mesh_update(A.M, st);
         refresh_blas_derivatives(c, st, c->count[2]);
     });
     HK_HIP(c, hipGetLastError());
-    ml.device = (const uint32_t*)part[7];
+    ml.device = A.M.levels;
     return rebuild_instances(c, models, local_aabbs, count, st, &ml);
 }
 
@@ -1932,8 +2126,7 @@ int hk_update_meshes(hk_ctx* c, const hk_mesh_update* meshes, uint32_t mesh_coun
 // the previous indices name the set before, each once
 static int set_args_ok(hk_ctx* c, const hk_instance_desc* set, uint32_t count, const char* who)
 {
-    if (c->count[5] != 3u * c->count[4] - 2u || (c->count[8] && c->count[7] != 3u * c->count[8] - 2u))
-        return fail(c, HK_ERR_STATE, "scene BVHs are not bvh-0.7.1 flattened (3n - 2 nodes); cannot rebuild");
+    HK_TRY(scene_rebuildable(c));
     std::vector<bool> taken(c->count[4], false);
     for (uint32_t i = 0; i < count; ++i) {
         const uint32_t p = set[i].previous;
@@ -1954,14 +2147,10 @@ int hk_set_instances(hk_ctx* c, const hk_instance_desc* set, const float* models
     if (!c->has_scene) return fail(c, HK_ERR_STATE, "no scene uploaded (hk_scene_upload)");
     HK_TRY(set_args_ok(c, set, count, "hk_set_instances"));
     (void)hipSetDevice(c->device);
-    std::vector<float> emissive;
-    if (materials) {
-        emissive.resize(4 * (size_t)c->count[6]);
-        for (uint32_t k = 0; k < c->count[6]; ++k) std::memcpy(&emissive[4 * (size_t)k], materials[k].emissive, 16);
-    }
+    const std::vector<float> emissive = materials ? emissive_of(materials, c->count[6]) : c->emissive;
     SetChange change;
     std::string why;
-    const int rc = plan_instance_set(c->count, c->meshes, materials ? emissive.data() : c->emissive.data(), set, count,
+    const int rc = plan_instance_set(c->count, c->meshes, emissive.data(), set, count,
                                      SliceReader{nullptr, c}, &change, &why);
     if (rc != HK_OK) return fail(c, rc, "hk_set_instances: " + why);
     change.materials = materials;
@@ -2055,128 +2244,29 @@ static int plan_add_meshes(const uint32_t* before, const hk_mesh_desc* meshes, u
     return HK_OK;
 }
 
-// the message of the calling thread's last hk_add_meshes_counts, which has no context to keep it (empty: it succeeded)
-static thread_local std::string counts_error;
+// the message of the calling thread's last hk_add_meshes_counts / hk_set_meshes_counts, which have no context to keep
+// it (empty: it succeeded), one string each; counts_refusal: a refusal of `call` kept in its string
+static thread_local std::string counts_error, set_counts_error;
 const char* hk_add_meshes_counts_error(void) { return counts_error.c_str(); }
+const char* hk_set_meshes_counts_error(void) { return set_counts_error.c_str(); }
+static int counts_refusal(std::string& kept, const char* call, const std::string& text)
+{
+    kept = std::string(call) + ": " + text;
+    return HK_ERR_INVALID;
+}
 
 int hk_add_meshes_counts(const uint32_t before[9], const hk_mesh_desc* meshes, uint32_t mesh_count,
                          hk_mesh_index* slices, uint32_t after[9])
 {
     counts_error.clear();
-    auto no = [&](const std::string& text) {
-        counts_error = "hk_add_meshes: " + text;
-        return HK_ERR_INVALID;
-    };
-    if (!before) return no("null counts");
-    if (!slices) return no("null slices");
+    if (!before) return counts_refusal(counts_error, "hk_add_meshes", "null counts");
+    if (!slices) return counts_refusal(counts_error, "hk_add_meshes", "null slices");
     MeshAddPlan plan;
     std::string why;
-    const int rc = plan_add_meshes(before, meshes, mesh_count, &plan, &why);
-    if (rc != HK_OK) return no(why);
+    if (plan_add_meshes(before, meshes, mesh_count, &plan, &why) != HK_OK)
+        return counts_refusal(counts_error, "hk_add_meshes", why);
     std::memcpy(slices, plan.slices.data(), plan.slices.size() * sizeof(hk_mesh_index));
     if (after) std::memcpy(after, plan.after, sizeof(plan.after));
-    return HK_OK;
-}
-
-// The new meshes of hk_add_meshes and hk_set_meshes on their way to the device: the tables in list order and by size,
-// where each mesh's indices lie, and the scratch they, the attribute and index streams and the builds' shape boxes,
-// indices, segments and levels take (sz: one entry per part; the last is the caller's own, `extra` bytes).
-struct MeshStaging {
-    std::vector<MeshUpdate> tab, by_size;
-    std::vector<MeshSource> sources;
-    uint32_t n_lds = 0, n_vertices = 0, n_shapes = 0, n_indices = 0;
-    static constexpr int PARTS = 12;
-    size_t sz[PARTS] = {};
-    size_t total = 0;
-};
-
-// meshes[k] goes to slices[k] with tris[k] triangles
-static void plan_mesh_staging(const std::vector<const hk_mesh_desc*>& meshes, const hk_mesh_index* slices,
-                              const uint32_t* tris, uint64_t n_vertices, uint64_t n_shapes, uint64_t n_indices,
-                              size_t extra, MeshStaging* S)
-{
-    const uint32_t n = (uint32_t)meshes.size();
-    S->tab.resize(n);
-    S->sources.resize(n);
-    S->n_vertices = (uint32_t)n_vertices;
-    S->n_shapes = (uint32_t)n_shapes;
-    S->n_indices = (uint32_t)n_indices;
-    uint32_t v0 = 0, s0 = 0, i0 = 0;
-    for (uint32_t k = 0; k < n; ++k) {
-        const hk_mesh_index& x = slices[k];
-        const hk_mesh_desc& m = *meshes[k];
-        S->tab[k] = MeshUpdate{x.vertex, m.vertex_count, x.primitive, tris[k], x.node[0], v0, s0, k, 1u};
-        S->sources[k] = MeshSource{m.indices ? i0 : MESH_NO_INDICES, m.topology == HKS_TRIANGLE_STRIP ? 1u : 0u};
-        v0 += m.vertex_count;
-        s0 += tris[k];
-        if (m.indices) i0 += m.index_count;
-        S->n_lds += tris[k] <= mesh_lds_shapes() ? 1u : 0u;
-    }
-    for (int big = 0; big < 2; ++big)
-        for (const MeshUpdate& m : S->tab)
-            if ((m.shapes > mesh_lds_shapes()) == (big == 1)) S->by_size.push_back(m);
-    auto align = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t nv = S->n_vertices, ns = S->n_shapes;
-    const size_t sz[MeshStaging::PARTS] = {
-        align((size_t)n * sizeof(MeshUpdate)), align((size_t)n * sizeof(MeshUpdate)), align((size_t)n * sizeof(MeshSource)),
-        align(nv * 12), align(nv * 12), align(nv * 8), align((size_t)(S->n_indices ? S->n_indices : 1) * 4),
-        align(ns * 24), align(ns * 8), align(ns * 24), align((size_t)n * 4), align(extra)};
-    S->total = 0;
-    for (int k = 0; k < MeshStaging::PARTS; ++k) S->total += (S->sz[k] = sz[k]);
-}
-
-// The tables and streams copied into c->mesh_scratch (at least S.total bytes) on `st`, and the launch arguments over
-// them, the destinations c->buf[0..2].  *extra: the caller's part.
-static int enqueue_mesh_staging(hk_ctx* c, const std::vector<const hk_mesh_desc*>& meshes, const MeshStaging& S,
-                                hipStream_t st, MeshAddArgs* A, char** extra)
-{
-    char* part[MeshStaging::PARTS];
-    {
-        char* p = (char*)c->mesh_scratch;
-        for (int k = 0; k < MeshStaging::PARTS; ++k) {
-            part[k] = p;
-            p += S.sz[k];
-        }
-    }
-    const size_t n = meshes.size();
-    if (n) {
-        HK_HIP(c, hipMemcpyAsync(part[0], S.tab.data(), n * sizeof(MeshUpdate), hipMemcpyHostToDevice, st));
-        HK_HIP(c, hipMemcpyAsync(part[1], S.by_size.data(), n * sizeof(MeshUpdate), hipMemcpyHostToDevice, st));
-        HK_HIP(c, hipMemcpyAsync(part[2], S.sources.data(), n * sizeof(MeshSource), hipMemcpyHostToDevice, st));
-    }
-    for (size_t k = 0; k < n; ++k) {
-        const hk_mesh_desc& m = *meshes[k];
-        const size_t v0 = S.tab[k].vertex0, nv = m.vertex_count;
-        if (nv) {
-            HK_HIP(c, hipMemcpyAsync(part[3] + v0 * 12, m.positions, nv * 12, hipMemcpyHostToDevice, st));
-            HK_HIP(c, hipMemcpyAsync(part[4] + v0 * 12, m.normals, nv * 12, hipMemcpyHostToDevice, st));
-            HK_HIP(c, hipMemcpyAsync(part[5] + v0 * 8, m.uvs, nv * 8, hipMemcpyHostToDevice, st));
-        }
-        if (m.indices)
-            HK_HIP(c, hipMemcpyAsync(part[6] + (size_t)S.sources[k].index0 * 4, m.indices, (size_t)m.index_count * 4,
-                                     hipMemcpyHostToDevice, st));
-    }
-    MeshUpdateArgs& M = A->M;
-    M.table = (const MeshUpdate*)part[0];
-    M.table_by_size = (const MeshUpdate*)part[1];
-    M.n_meshes = (uint32_t)n;
-    M.n_lds = S.n_lds;
-    M.n_vertices = S.n_vertices;
-    M.n_shapes = S.n_shapes;
-    M.positions = (const float*)part[3];
-    M.normals = (const float*)part[4];
-    M.vertices = (hk_vertex*)c->buf[0];
-    M.primitives = (hk_primitive*)c->buf[1];
-    M.blas = (hk_node*)c->buf[2];
-    M.buckets = 6;  // bvh 0.7.1 NUM_BUCKETS (hks_build default)
-    M.shapes = part[7];
-    M.idx = (uint32_t*)part[8];
-    M.segments = part[9];
-    M.levels = (uint32_t*)part[10];
-    A->sources = (const MeshSource*)part[2];
-    A->uvs = (const float*)part[5];
-    A->indices = (const uint32_t*)part[6];
-    if (extra) *extra = part[11];
     return HK_OK;
 }
 
@@ -2199,105 +2289,14 @@ int hk_add_meshes(hk_ctx* c, const hk_mesh_desc* meshes, uint32_t mesh_count, hk
     for (uint32_t k = 0; k < mesh_count; ++k) list[k] = meshes + k;
     MeshStaging stage;
     plan_mesh_staging(list, plan.slices.data(), plan.tris.data(), plan.n_vertices, plan.n_shapes, plan.n_indices, 0, &stage);
-    const size_t total = stage.total;
-    // Room (hikari_amd.h hk_add_meshes "Capacity").  First every allocation the call needs, with the context untouched:
-    // a failure here frees them and leaves the context as it was.  Then the grown arrays take their contents, copied on
-    // the stream, and a zeroed tail; the buffers they leave are freed after the call's one wait, or on the way out.
-    struct Buffers {
-        std::vector<void*> p;
-        ~Buffers()
-        {
-            for (void* q : p) (void)hipFree(q);
-        }
-    } fresh, old;
-    auto grown = [](size_t need, size_t cap) { return std::max(need, cap + cap / 2); };
-    auto alloc = [&](size_t bytes) -> void* {
-        void* nb = nullptr;
-        if (hipMalloc(&nb, bytes) != hipSuccess) return nullptr;
-        fresh.p.push_back(nb);
-        return nb;
-    };
-    size_t cap[3];
-    void* nbuf[3] = {};
-    bool ok = true;
-    for (int i = 0; i < 3; ++i) {
-        cap[i] = plan.after[i] > c->cap[i] ? grown(plan.after[i], c->cap[i]) : c->cap[i];
-        if (cap[i] != c->cap[i]) ok = ok && (nbuf[i] = alloc(staged_alloc_bytes(cap[i], SCENE_ELEM[i])));
-    }
-    void *n_wide = nullptr, *n_walk = nullptr, *n_aux = nullptr, *n_collapse = nullptr, *n_scratch = nullptr;
-    if (cap[2] != c->cap[2])
-        ok = ok && (n_wide = alloc(cap[2] * WIDE_NODE_BYTES)) && (n_walk = alloc(cap[2] * sizeof(hk_node))) &&
-             (n_aux = alloc(cap[2] * 12));
-    size_t collapse_cap = c->collapse_cap;
-    {
-        const size_t need = std::max<size_t>(1, std::max(plan.after[2], c->count[5]));
-        if (need > collapse_cap) {
-            collapse_cap = grown(need, collapse_cap);
-            ok = ok && (n_collapse = alloc(collapse_cap * 4));
-        }
-    }
-    if (c->mesh_bytes < total) ok = ok && (n_scratch = alloc(total));
-    if (!ok) return fail(c, HK_ERR_HIP, "hk_add_meshes: out of device memory");
-    fresh.p.clear();  // (all of them go into the context below)
-    // (the pointers first, so that nothing allocated is lost on a failed enqueue)
-    void** slot[] = {&c->buf[0], &c->buf[1], &c->buf[2], (void**)&c->blas_wide, (void**)&c->walk_nodes[0]};
-    void* repl[] = {nbuf[0], nbuf[1], nbuf[2], n_wide, n_walk};
-    void* was[5];
-    for (int k = 0; k < 5; ++k) {
-        was[k] = *slot[k];
-        if (!repl[k]) continue;
-        old.p.push_back(*slot[k]);
-        *slot[k] = repl[k];
-    }
-    uint32_t* aux_was = c->blas_aux;
-    const size_t stride_was = c->aux_stride, have = c->count[2];
-    if (n_aux) {
-        old.p.push_back(c->blas_aux);
-        c->blas_aux = (uint32_t*)n_aux;
-        c->aux_stride = cap[2];
-    }
-    if (n_collapse) {
-        old.p.push_back(c->collapse_scratch);
-        c->collapse_scratch = (uint32_t*)n_collapse;
-        c->collapse_cap = collapse_cap;
-    }
-    if (n_scratch) {
-        old.p.push_back(c->mesh_scratch);
-        c->mesh_scratch = n_scratch;
-        c->mesh_bytes = total;
-    }
-    for (int i = 0; i < 3; ++i) c->cap[i] = cap[i];
-    {
-        const size_t elem[5] = {SCENE_ELEM[0], SCENE_ELEM[1], SCENE_ELEM[2], WIDE_NODE_BYTES, sizeof(hk_node)};
-        const int of[5] = {0, 1, 2, 2, 2};
-        for (int k = 0; k < 5; ++k) {
-            if (!repl[k]) continue;
-            const size_t keep = (size_t)c->count[of[k]] * elem[k];
-            const size_t bytes = k < 3 ? staged_alloc_bytes(cap[of[k]], elem[k]) : cap[2] * elem[k];
-            if (keep) HK_HIP(c, hipMemcpyAsync(repl[k], was[k], keep, hipMemcpyDeviceToDevice, st));
-            if (bytes > keep) HK_HIP(c, hipMemsetAsync((char*)repl[k] + keep, 0, bytes - keep, st));
-        }
-    }
-    if (n_aux) {  // the per-node mesh tables, re-laid at the new stride: unregistered nodes read U32_MAX
-        HK_HIP(c, hipMemsetAsync(n_aux, 0xFF, cap[2] * 12, st));
-        for (size_t k = 0; k < 3 && have; ++k)
-            HK_HIP(c, hipMemcpyAsync((uint32_t*)n_aux + k * cap[2], aux_was + k * stride_was, have * 4,
-                                     hipMemcpyDeviceToDevice, st));
-    }
+    // Room (hikari_amd.h hk_add_meshes "Capacity"): the grown arrays take their contents; the buffers they leave are
+    // freed after the call's one wait, or on the way out
+    Buffers old;
+    HK_TRY(reserve_scene(c, "hk_add_meshes", plan.after, 7u, 7u, false, stage.total, 0, st, &old));
     MeshAddArgs A;
     HK_TRY(enqueue_mesh_staging(c, list, stage, st, &A, nullptr));
-    // the new meshes' rows of the per-node mesh tables: primitive offset, node base, node count
-    const uint32_t n_before = c->count[2], n_new = plan.after[2] - n_before;
-    std::vector<uint32_t> rows[3];
-    for (std::vector<uint32_t>& r : rows) r.reserve(n_new);
-    for (const hk_mesh_index& x : plan.slices) {
-        rows[0].insert(rows[0].end(), x.node[1], x.primitive);
-        rows[1].insert(rows[1].end(), x.node[1], x.node[0]);
-        rows[2].insert(rows[2].end(), x.node[1], x.node[1]);
-    }
-    for (size_t k = 0; k < 3; ++k)
-        HK_HIP(c, hipMemcpyAsync(c->blas_aux + k * c->aux_stride + n_before, rows[k].data(), (size_t)n_new * 4,
-                                 hipMemcpyHostToDevice, st));
+    std::vector<uint32_t> rows;  // the new meshes' rows of the per-node mesh tables
+    HK_TRY(write_mesh_rows(c, plan.slices.data(), plan.slices.size(), st, &rows));
     timed(c, "add_meshes", st, [&] {
         launch_mesh_add(A, st);
         refresh_blas_derivatives(c, st, plan.after[2]);  // over the whole array, as hk_update_meshes
@@ -2376,9 +2375,8 @@ static int plan_set_meshes(const uint32_t* before, const std::vector<hk_ctx::Mes
             for (const Kept& o : kept)
                 if (std::memcmp(&o.x, &x, sizeof(x)) == 0) return no(who + "the slice is kept twice");
             if (known) {
-                const hk_ctx::MeshSlice* s = nullptr;
-                for (const hk_ctx::MeshSlice& o : *known)
-                    if (std::memcmp(&o.index, &x, sizeof(x)) == 0) s = &o;
+                const size_t at = find_slice(*known, x);
+                const hk_ctx::MeshSlice* s = at < known->size() ? &(*known)[at] : nullptr;
                 hk_ctx::MeshSlice f;
                 if (!s) {
                     std::string text;
@@ -2432,24 +2430,16 @@ static int plan_set_meshes(const uint32_t* before, const std::vector<hk_ctx::Mes
     return HK_OK;
 }
 
-// (as counts_error, for hk_set_meshes_counts)
-static thread_local std::string set_counts_error;
-const char* hk_set_meshes_counts_error(void) { return set_counts_error.c_str(); }
-
 int hk_set_meshes_counts(const uint32_t before[9], const hk_mesh_entry* list, uint32_t mesh_count, hk_mesh_index* slices,
                          uint32_t after[9])
 {
     set_counts_error.clear();
-    auto no = [&](const std::string& text) {
-        set_counts_error = "hk_set_meshes: " + text;
-        return HK_ERR_INVALID;
-    };
-    if (!before) return no("null counts");
-    if (!slices) return no("null slices");
+    if (!before) return counts_refusal(set_counts_error, "hk_set_meshes", "null counts");
+    if (!slices) return counts_refusal(set_counts_error, "hk_set_meshes", "null slices");
     MeshSetPlan plan;
     std::string why;
-    const int rc = plan_set_meshes(before, nullptr, nullptr, list, mesh_count, &plan, &why);
-    if (rc != HK_OK) return no(why);
+    if (plan_set_meshes(before, nullptr, nullptr, list, mesh_count, &plan, &why) != HK_OK)
+        return counts_refusal(set_counts_error, "hk_set_meshes", why);
     std::memcpy(slices, plan.slices.data(), plan.slices.size() * sizeof(hk_mesh_index));
     if (after) std::memcpy(after, plan.after, sizeof(plan.after));
     return HK_OK;
@@ -2472,14 +2462,9 @@ int hk_set_meshes(hk_ctx* c, const hk_mesh_entry* list, uint32_t mesh_count, hk_
     int rc = plan_set_meshes(c->count, &c->meshes, &rd, list, mesh_count, &plan, &why);
     if (rc != HK_OK) return fail(c, rc, "hk_set_meshes: " + why);
     HK_TRY(set_args_ok(c, set, count, "hk_set_meshes"));
-    std::vector<float> emissive;
-    if (materials) {
-        emissive.resize(4 * (size_t)c->count[6]);
-        for (uint32_t k = 0; k < c->count[6]; ++k) std::memcpy(&emissive[4 * (size_t)k], materials[k].emissive, 16);
-    }
+    const std::vector<float> emissive = materials ? emissive_of(materials, c->count[6]) : c->emissive;
     SetChange change;
-    rc = plan_instance_set(plan.after, plan.registry, materials ? emissive.data() : c->emissive.data(), set, count, rd,
-                           &change, &why, true);
+    rc = plan_instance_set(plan.after, plan.registry, emissive.data(), set, count, rd, &change, &why, true);
     if (rc != HK_OK) return fail(c, rc, "hk_set_meshes: " + why);
     change.materials = materials;
     hipStream_t st = pick(c, stream);
@@ -2489,75 +2474,11 @@ int hk_set_meshes(hk_ctx* c, const hk_mesh_entry* list, uint32_t mesh_count, hk_
     MeshStaging stage;
     plan_mesh_staging(plan.sources, plan.source_slices.data(), plan.tris.data(), plan.n_vertices, plan.n_shapes,
                       plan.n_indices, (size_t)mesh_count * sizeof(MeshMove), &stage);
-    // Room (hikari_amd.h hk_set_meshes "Capacity"), every allocation first as in hk_add_meshes.  The move is out of
-    // place: arrays 0-2 are written into their spares, which are then the arrays, and the arrays the spares.  A spare
-    // smaller than the capacity the call needs is allocated anew; the derivatives, which are rewritten whole, only
-    // where the node capacity grows.
-    struct Buffers {
-        std::vector<void*> p;
-        ~Buffers()
-        {
-            for (void* q : p) (void)hipFree(q);
-        }
-    } fresh, old;
-    auto grown = [](size_t need, size_t cap) { return std::max(need, cap + cap / 2); };
-    auto alloc = [&](size_t bytes) -> void* {
-        void* nb = nullptr;
-        if (hipMalloc(&nb, bytes) != hipSuccess) return nullptr;
-        fresh.p.push_back(nb);
-        return nb;
-    };
-    size_t cap[3];
-    void* nspare[3] = {};
-    bool ok = true;
-    for (int i = 0; i < 3; ++i) {
-        cap[i] = plan.after[i] > c->cap[i] ? grown(plan.after[i], c->cap[i]) : c->cap[i];
-        if (c->spare_cap[i] < cap[i]) ok = ok && (nspare[i] = alloc(staged_alloc_bytes(cap[i], SCENE_ELEM[i])));
-        else cap[i] = c->spare_cap[i];
-    }
-    void *n_wide = nullptr, *n_walk = nullptr, *n_aux = nullptr, *n_collapse = nullptr, *n_scratch = nullptr;
-    if (cap[2] != c->cap[2])
-        ok = ok && (n_wide = alloc(cap[2] * WIDE_NODE_BYTES)) && (n_walk = alloc(cap[2] * sizeof(hk_node))) &&
-             (n_aux = alloc(cap[2] * 12));
-    size_t collapse_cap = c->collapse_cap;
-    {
-        const size_t need = std::max<size_t>(1, std::max(plan.after[2], std::max(c->count[5], change.counts[5])));
-        if (need > collapse_cap) {
-            collapse_cap = grown(need, collapse_cap);
-            ok = ok && (n_collapse = alloc(collapse_cap * 4));
-        }
-    }
-    if (c->mesh_bytes < stage.total) ok = ok && (n_scratch = alloc(stage.total));
-    if (!ok) return fail(c, HK_ERR_HIP, "hk_set_meshes: out of device memory");
-    fresh.p.clear();  // (all of them go into the context below)
-    const void* from[3];
-    for (int i = 0; i < 3; ++i) {
-        if (nspare[i]) {
-            if (c->spare[i]) old.p.push_back(c->spare[i]);
-            c->spare[i] = nspare[i];
-            c->spare_cap[i] = cap[i];
-        }
-        from[i] = c->buf[i];
-        std::swap(c->buf[i], c->spare[i]);
-        std::swap(c->cap[i], c->spare_cap[i]);
-    }
-    void** slot[] = {(void**)&c->blas_wide, (void**)&c->walk_nodes[0], (void**)&c->blas_aux, (void**)&c->collapse_scratch,
-                     &c->mesh_scratch};
-    void* repl[] = {n_wide, n_walk, n_aux, n_collapse, n_scratch};
-    for (int k = 0; k < 5; ++k) {
-        if (!repl[k]) continue;
-        old.p.push_back(*slot[k]);
-        *slot[k] = repl[k];
-    }
-    c->aux_stride = c->cap[2];
-    if (n_collapse) c->collapse_cap = collapse_cap;
-    if (n_scratch) c->mesh_bytes = stage.total;
-    for (int i = 0; i < 3; ++i) {  // the tail behind the new count, zeroed
-        const size_t at = (size_t)plan.after[i] * SCENE_ELEM[i], end = staged_alloc_bytes(c->cap[i], SCENE_ELEM[i]);
-        if (end > at) HK_HIP(c, hipMemsetAsync((char*)c->buf[i] + at, 0, end - at, st));
-    }
-    if (n_wide) HK_HIP(c, hipMemsetAsync(n_wide, 0, c->cap[2] * WIDE_NODE_BYTES, st));
-    if (n_walk) HK_HIP(c, hipMemsetAsync(n_walk, 0, c->cap[2] * sizeof(hk_node), st));
+    // Room (hikari_amd.h hk_set_meshes "Capacity").  The move is out of place: arrays 0-2 are written into their spares,
+    // which are then the arrays, and the arrays the spares.  The derivatives, which are rewritten whole, are allocated
+    // anew only where the node capacity grows.
+    Buffers old;
+    HK_TRY(reserve_scene(c, "hk_set_meshes", plan.after, 7u, 0u, true, stage.total, 0, st, &old));
     HK_HIP(c, hipMemsetAsync(c->blas_aux, 0xFF, c->aux_stride * 12, st));  // (behind the count: U32_MAX, as at upload)
     MeshAddArgs A;
     char* table = nullptr;
@@ -2570,7 +2491,7 @@ int hk_set_meshes(hk_ctx* c, const hk_mesh_entry* list, uint32_t mesh_count, hk_
     V.n_prims = plan.after[1];
     V.n_nodes = plan.after[2];
     for (int i = 0; i < 3; ++i) {
-        V.src[i] = from[i];
+        V.src[i] = c->spare[i];  // (the array as it was)
         V.dst[i] = c->buf[i];
     }
     V.aux = c->blas_aux;
@@ -2640,23 +2561,14 @@ int hk_instance_set_counts(const hk_scene_desc* d, const hk_instance_desc* set, 
                            const hk_material* materials, uint32_t counts[9])
 {
     if (!d || !set || !counts || !scene_desc_ok(d)) return HK_ERR_INVALID;
-    const uint32_t before[9] = {d->vertices.count,  d->primitives.count,     d->asset_nodes.count,
-                                d->alias_table.count, d->instances.count,    d->instance_nodes.count,
-                                d->materials.count, d->emissive_nodes.count, d->emissives.count};
     std::vector<hk_ctx::MeshSlice> known;
-    std::set<std::array<uint32_t, 4>> seen;
-    const hk_instance* inst = (const hk_instance*)d->instances.data;
-    for (uint32_t k = 0; k < d->instances.count; ++k) {
-        const hk_mesh_index& m = inst[k].mesh;
-        if ((size_t)m.node[0] + m.node[1] > d->asset_nodes.count) return HK_ERR_INVALID;
-        if (seen.insert({m.vertex, m.primitive, m.node[0], m.node[1]}).second) known.push_back(host_mesh_slice(d, m));
-    }
-    std::vector<float> emissive(4 * (size_t)d->materials.count);
-    const hk_material* mats = materials ? materials : (const hk_material*)d->materials.data;
-    for (uint32_t k = 0; k < d->materials.count; ++k) std::memcpy(&emissive[4 * (size_t)k], mats[k].emissive, 16);
+    if (!host_registry(d, &known)) return HK_ERR_INVALID;
+    const std::vector<float> emissive =
+        emissive_of(materials ? materials : (const hk_material*)d->materials.data, d->materials.count);
     SetChange change;
     std::string why;
-    const int rc = plan_instance_set(before, known, emissive.data(), set, count, SliceReader{d, nullptr}, &change, &why);
+    const int rc = plan_instance_set(desc_counts(d).data(), known, emissive.data(), set, count, SliceReader{d, nullptr},
+                                     &change, &why);
     if (rc != HK_OK) return rc;
     std::memcpy(counts, change.counts, sizeof(change.counts));
     return HK_OK;
@@ -2666,10 +2578,7 @@ int hk_read_scene_array(hk_ctx* c, int array, void* dst, size_t bytes)
 {
     if (!c || !dst || array < 0 || array > 8) return HK_ERR_INVALID;
     if (!c->has_scene) return fail(c, HK_ERR_STATE, "no scene uploaded (hk_scene_upload)");
-    const size_t elem[9] = {sizeof(hk_vertex), sizeof(hk_primitive), sizeof(hk_node), sizeof(hk_alias_entry),
-                            sizeof(hk_instance), sizeof(hk_node), sizeof(hk_material), sizeof(hk_node),
-                            sizeof(hk_emissive)};
-    const size_t have = (size_t)c->count[array] * elem[array];
+    const size_t have = (size_t)c->count[array] * SCENE_ELEM[array];
     if (bytes < have) return fail(c, HK_ERR_INVALID, "destination too small");
     (void)hipSetDevice(c->device);
     HK_HIP(c, hipStreamSynchronize(c->stream));

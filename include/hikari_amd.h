@@ -323,8 +323,9 @@ int hk_update_meshes(hk_ctx* ctx, const hk_mesh_update* meshes, uint32_t mesh_co
  * far.
  *   Capacity: the five arrays, the TLAS derivatives, the previous models and the scratch keep a capacity beside
  * their count; a call allocates only for a count above its capacity, and then max(count, 1.5 x capacity); nothing
- * shrinks before hk_scene_upload or hk_destroy.  A set without an emitter is legal (empty alias table, light BVH and
- * emissives).  An EMPTY set is not: hk_scene_upload refuses an empty scene too.
+ * shrinks before hk_scene_upload or hk_destroy.  Every allocation the call needs is made before anything changes: on
+ * HK_ERR_HIP "out of device memory" the context is as it was.  A set without an emitter is legal (empty alias table,
+ * light BVH and emissives).  An EMPTY set is not: hk_scene_upload refuses an empty scene too.
  *   HK_ERR_INVALID with a message, decided before any device work, the context unchanged and usable: a null set,
  * models or local_aabbs; count == 0; a material index >= the material count; a slice that fails the checks above; a
  * previous that is neither HK_INSTANCE_NEW nor below the count before, or used twice.  HK_ERR_STATE without a scene

@@ -304,6 +304,29 @@ def test_a_steady_toggle_allocates_nothing():
     r.close()
 
 
+def test_a_set_past_the_capacity_grows_by_half_and_stays():
+    """spawn_copies 4 -> 6 takes arrays 3, 4, 5, 7 and 8 past the capacity the upload gave them: each grows to
+    max(count, capacity + capacity // 2) and the others keep theirs; the way back and a second way forward fit."""
+    name = "there_and_back"
+    c = ic.case(name)
+    r = renderer(c.scenes[0])
+    before = r.scene_capacity()
+    assert before == [max(1, n) for n in ic.desc_counts(c.scenes[0].desc)]
+    _set(r, name, 1)
+    counts, after = r.scene_counts(), r.scene_capacity()
+    for i in (3, 4, 5, 7, 8):
+        assert counts[i] > before[i], (i, counts, before)  # (the case: every one of them has to grow)
+        assert after[i] == max(counts[i], before[i] + before[i] // 2), (i, counts, before, after)
+    for i in (0, 1, 2, 6):
+        assert after[i] == before[i], (i, before, after)
+    _set(r, name, 2)
+    assert r.scene_capacity() == after
+    _set(r, name, 1)
+    assert r.scene_capacity() == after
+    assert_set_matches_host(r, ic.built(name, 1))
+    r.close()
+
+
 def test_plugin_forwards_set_instances():
     from hikari_amd import HikariPlugin
     name = "emitter_on"
