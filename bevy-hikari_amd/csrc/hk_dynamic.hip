@@ -1,5 +1,6 @@
 // hk_dynamic.hip — dynamic instances, deforming meshes, changed instance sets
-// (DESIGN §0 f8), appended meshes and new mesh lists on the device.
+// (DESIGN §0 f8), appended meshes, new mesh lists and skinned meshes on
+// the device.
 //
 // The reference re-runs `prepare_instances` on the CPU whenever a transform changes
 // (instance.rs:284-437: instance records with world AABBs and inverse-transpose models, the
@@ -15,6 +16,7 @@
 // exactly 3k - 2 nodes, so each segment knows its output range without the rest of the tree.
 #include "hk_device.h"
 #include "hk_launch.h"
+#include "../../include/hk_skin.h"
 
 namespace hk {
 
@@ -548,6 +550,98 @@ __global__ __launch_bounds__(256) void k_build_mesh_bvh(const MeshUpdate* tab, c
                    seg + 2u * (size_t)m.shape0, levels + m.slot);
 }
 
+// ---- skinned meshes (include/hk_skin.h: Bevy 0.9's skinning.wgsl as recalled, its order pinned there;
+// the host side is hk_scene.cpp hks_skin_vertices over the same header).  One thread per vertex of the posed meshes,
+// found by k_update_mesh_geometry's table search: the bind pose and the rig from the context's resident streams
+// (consecutive lanes read consecutive addresses: 12-byte positions and normals, one 8-byte load of the four u16 indices,
+// one 16-byte load of the weights), the four joint matrices as four 16-byte loads each from the uploaded palettes, and
+// the posed position and normal stored into the staged streams at the vertex's place in list order, where
+// k_update_mesh_geometry and the BLAS build read them as if the host had sent them.  Every index was checked against
+// the skin's joint_count on the host (hk_set_mesh_skins), and the pose's joint_count is the skin's (hk_skin_meshes).
+__global__ __launch_bounds__(256) void k_skin_vertices(const MeshUpdate* tab, const SkinSource* sources,
+                                                       uint32_t n_meshes, uint32_t n_vertices,
+                                                       const float* bind_positions, const float* bind_normals,
+                                                       const uint2* joint_indices, const float4* joint_weights,
+                                                       const float4* palettes, float* positions, float* normals)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_vertices) return;
+    const uint32_t k = mesh_of(tab, n_meshes, i, false);
+    const MeshUpdate& m = tab[k];
+    const uint32_t v = i - m.vertex0;
+    if (v >= m.vertex_count) return;
+    const SkinSource s = sources[k];
+    const size_t at = (size_t)s.skin0 + v;
+    const uint2 ix = joint_indices[at];
+    const float4 wt = joint_weights[at];
+    const uint32_t joint[4] = {ix.x & 0xFFFFu, ix.x >> 16, ix.y & 0xFFFFu, ix.y >> 16};
+    const float w[4] = {wt.x, wt.y, wt.z, wt.w};
+    float J[4][16];
+    for (int j = 0; j < 4; ++j) {
+        const float4* col = palettes + 4u * ((size_t)s.joint0 + joint[j]);
+        for (int c = 0; c < 4; ++c) {
+            const float4 q = col[c];
+            J[j][4 * c] = q.x, J[j][4 * c + 1] = q.y, J[j][4 * c + 2] = q.z, J[j][4 * c + 3] = q.w;
+        }
+    }
+    float M[12], p[3], o[3];
+    hk_skin_matrix(J[0], J[1], J[2], J[3], w, M);
+    for (int a = 0; a < 3; ++a) p[a] = bind_positions[3u * at + a];
+    hk_skin_position(M, p, o);
+    for (int a = 0; a < 3; ++a) positions[3u * (size_t)i + a] = o[a];
+    if (m.has_normals) {
+        for (int a = 0; a < 3; ++a) p[a] = bind_normals[3u * at + a];
+        hk_skin_normal(M, p, o);
+        for (int a = 0; a < 3; ++a) normals[3u * (size_t)i + a] = o[a];
+    }
+}
+// One workgroup per posed mesh: the box of its staged (posed) positions by hk_skin.h's bounds rule, stated without an
+// order: each bound's value by fminf / fmaxf (exact in any order; a NaN loses, as in the host's fold), and a bound of 0
+// with the sign of the last vertex in vertex order whose component is a zero (coop_split's keyed atomicMax; the index
+// is below 2^30, hk_skin_meshes' bound).  Then the Bevy Aabb (centre, half extents) over the rows of local_aabbs whose
+// instance record carries this mesh's slice: one thread per instance, strided.  The records are those before the
+// rebuild; k_update_instances leaves their mesh slices as they are.
+__global__ __launch_bounds__(256) void k_skin_bounds(const MeshUpdate* tab, const SkinSource* sources,
+                                                     const float* positions, const hk_instance* inst, uint32_t n_inst,
+                                                     float* local_aabbs)
+{
+    __shared__ CoopShared sh;
+    const MeshUpdate m = tab[blockIdx.x];
+    const hk_mesh_index mesh = sources[blockIdx.x].mesh;
+    const float* p = positions + 3u * (size_t)m.vertex0;
+    const float inf = __uint_as_float(0x7F800000u);
+    float b[6] = {inf, inf, inf, -inf, -inf, -inf};
+    const int op[6] = {0, 0, 0, 1, 1, 1};
+    for (uint32_t v = threadIdx.x; v < m.vertex_count; v += 256u)
+        for (int k = 0; k < 3; ++k) {
+            const float x = p[3u * (size_t)v + k];
+            b[k] = fminf(b[k], x), b[3 + k] = fmaxf(b[3 + k], x);
+        }
+    block_reduce<6>(b, op, sh);
+    for (int j = 0; j < 6; ++j) {  // (b[] is the same in every thread: the branch is block-uniform)
+        if (b[j] != 0.0f) continue;
+        if (threadIdx.x == 0) sh.u[0] = 0u;
+        __syncthreads();
+        uint32_t key = 0u;  // (index + 1) * 2 + sign bit of the thread's last zero
+        for (uint32_t v = threadIdx.x; v < m.vertex_count; v += 256u) {
+            const float x = p[3u * (size_t)v + j % 3];
+            if (x == 0.0f) key = ((v + 1u) << 1) | (__float_as_uint(x) >> 31);
+        }
+        if (key) atomicMax(&sh.u[0], key);
+        __syncthreads();
+        b[j] = (sh.u[0] & 1u) ? -0.0f : 0.0f;
+        __syncthreads();
+    }
+    float aabb[6];
+    hk_skin_aabb(b, b + 3, aabb);
+    for (uint32_t i = threadIdx.x; i < n_inst; i += 256u) {
+        const hk_mesh_index& x = inst[i].mesh;
+        if (x.vertex == mesh.vertex && x.primitive == mesh.primitive && x.node[0] == mesh.node[0] &&
+            x.node[1] == mesh.node[1])
+            for (int k = 0; k < 6; ++k) local_aabbs[6u * (size_t)i + k] = aabb[k];
+    }
+}
+
 // ---- appended meshes (mesh.rs:77-166 prepare_mesh_assets on AssetEvent::Created, mod.rs:379-467 GpuMesh::try_from;
 // hk_scene.cpp hks_add_mesh + hks_build "concatenate").  One thread per vertex of the new meshes: the
 // whole hk_vertex (position, u | normal, v) from the three staged attribute streams, as two 16-byte stores.  Then one
@@ -1035,6 +1129,18 @@ void launch_mesh_move(const MeshMoveArgs& V, hipStream_t st)
     hipLaunchKernelGGL(k_move_mesh_slices, dim3((uint32_t)((chunks + 255u) / 256u)), dim3(256), 0, st, V.table, V.n_meshes,
                        V.n_vertices, V.n_prims, V.n_nodes, (const uint4*)V.src[0], (const uint4*)V.src[1],
                        (const uint4*)V.src[2], (uint4*)V.dst[0], (uint4*)V.dst[1], (uint4*)V.dst[2], V.aux, V.stride);
+}
+void launch_skin_vertices(const SkinArgs& K, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_skin_vertices, dim3((K.n_vertices + 255u) / 256u), dim3(256), 0, st, K.table, K.sources,
+                       K.n_meshes, K.n_vertices, K.bind_positions, K.bind_normals, K.joint_indices, K.joint_weights,
+                       K.palettes, K.positions, K.normals);
+}
+void launch_skin_bounds(const SkinArgs& K, const hk_instance* instances, uint32_t n_instances, float* local_aabbs,
+                        hipStream_t st)
+{
+    hipLaunchKernelGGL(k_skin_bounds, dim3(K.n_meshes), dim3(256), 0, st, K.table, K.sources, (const float*)K.positions,
+                       instances, n_instances, local_aabbs);
 }
 uint32_t mesh_lds_shapes() { return BVH_LDS_SHAPES; }
 

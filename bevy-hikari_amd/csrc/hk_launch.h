@@ -215,6 +215,33 @@ struct MeshUpdateArgs {
 void launch_mesh_update(const MeshUpdateArgs& M, hipStream_t st);
 uint32_t mesh_lds_shapes();
 
+// Skinned meshes (hk_skin_meshes, hk_dynamic.hip): beside each posed mesh's MeshUpdate record (vertex0:
+// its place in the staged position / normal streams, which k_skin_vertices writes and launch_mesh_update then reads),
+// where its bind pose lies in the context's resident skin streams and its palette in the uploaded ones.
+struct SkinSource {
+    uint32_t skin0;      // its first vertex in the resident streams
+    uint32_t joint0;     // its first matrix in the uploaded palettes
+    hk_mesh_index mesh;  // its slice, as its instances' records carry it (k_skin_bounds)
+};
+struct SkinArgs {
+    const MeshUpdate* table;        // n_meshes records in list order
+    const SkinSource* sources;      // beside them
+    uint32_t n_meshes, n_vertices;  // n_vertices: the sum over the list
+    const float* bind_positions;    // resident: x 3
+    const float* bind_normals;      // resident: x 3 (read where MeshUpdate::has_normals)
+    const uint2* joint_indices;     // resident: four u16 per vertex, one 8-byte load
+    const float4* joint_weights;    // resident: one 16-byte load per vertex
+    const float4* palettes;         // the uploaded joint matrices, four float4 columns each
+    float* positions;               // the staged streams, n_vertices x 3
+    float* normals;
+};
+// one thread per vertex of the posed meshes: the posed position and normal into the staged streams (one launch)
+void launch_skin_vertices(const SkinArgs& K, hipStream_t st);
+// one workgroup per posed mesh: its Bevy Aabb from the staged positions (include/hk_skin.h's bounds rule), written over
+// the rows of local_aabbs (n_instances x 6) whose instance record carries the mesh's slice (one launch)
+void launch_skin_bounds(const SkinArgs& K, const hk_instance* instances, uint32_t n_instances, float* local_aabbs,
+                        hipStream_t st);
+
 // Appended meshes (hk_add_meshes, hk_dynamic.hip): beside each mesh's MeshUpdate record (its destination slices past
 // the arrays' ends, vertex0 / shape0 its place in the staged streams; has_normals is not read), where its indices lie
 // and how its triangles read them.

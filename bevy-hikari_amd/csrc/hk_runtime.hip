@@ -15,6 +15,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -401,6 +402,17 @@ struct hk_ctx {
     // buf[i]; spare_cap: its elements
     void* spare[3] = {};
     size_t spare_cap[3] = {};
+    // hk_set_mesh_skins: the registered skins (slice, vertices, joints, where its vertices lie in the streams) and one
+    // device block carved into the four resident streams at skin_cap vertices each (bind positions x 12, bind normals
+    // x 12, joint indices x 8, joint weights x 16); skin_cap stays where a smaller set follows a larger one
+    struct Skin {
+        hk_mesh_index index;
+        uint32_t vertex_count, joint_count, vertex0;
+        bool has_normals;
+    };
+    std::vector<Skin> skins;
+    void* skin_block = nullptr;
+    size_t skin_cap = 0;
     // GlobalTransformQueue[1] of every instance (transform.rs:32-44): the models as of the previous
     // k_gbuffer, read by its motion vectors; refreshed after a k_gbuffer that followed an update
     float* prev_models = nullptr;
@@ -1165,6 +1177,7 @@ void hk_destroy(hk_ctx* c)
     release(c->dyn_scratch);
     release(c->blas_aux);
     release(c->mesh_scratch);
+    release(c->skin_block);
     release(c->prev_models);
     release(c->tex_desc);
     release(c->texels);
@@ -1460,6 +1473,7 @@ int hk_scene_upload(hk_ctx* c, const hk_scene_desc* d)
         c->cap[i] = arr[i]->count ? arr[i]->count : 1;
     }
     c->emissive = emissive_of((const hk_material*)d->materials.data, d->materials.count);
+    c->skins.clear();  // (the slices are another scene's; the streams keep their capacity)
     // the instanced meshes: each distinct slice once, with the vertices its primitives index and its BLAS depth
     // (gb_blas_depth is the maximum of these)
     if (!host_registry(d, &c->meshes)) return fail(c, HK_ERR_INVALID, "instance mesh node range outside asset nodes");
@@ -1819,9 +1833,11 @@ static int carve(hk_ctx* c, void** scratch, size_t* have, const size_t* bytes, i
 
 // The instance rebuild on `st` (after the mesh rebuild of hk_update_meshes, if any) and its one wait: the one body of
 // hk_update_instances, hk_update_meshes and hk_set_instances.  set: the new instance set that replaces the current one
-// (null: the current set with new models).
+// (null: the current set with new models).  mesh_work (hk_skin_meshes): what the caller enqueues on `st` between the
+// uploads and the instance kernels, given the device copy of local_aabbs, whose rows it may overwrite.
 static int rebuild_instances(hk_ctx* c, const float* models, const float* local_aabbs, uint32_t count, hipStream_t st,
-                             const MeshLevels* ml, const SetChange* set = nullptr)
+                             const MeshLevels* ml, const SetChange* set = nullptr,
+                             const std::function<void(float*)>* mesh_work = nullptr)
 {
     HK_TRY(c->sch.gb_join(st));
     HK_TRY(c->sch.gb_serialize(false));
@@ -1871,6 +1887,7 @@ static int rebuild_instances(hk_ctx* c, const float* models, const float* local_
     HK_HIP(c, hipMemcpyAsync(part[1], local_aabbs, (size_t)n * 24, hipMemcpyHostToDevice, st));
     HK_HIP(c, hipMemsetAsync(part[8], 0, 16, st));
     if (set) HK_HIP(c, hipMemcpyAsync(part[9], set->set, (size_t)n * sizeof(InstanceDesc), hipMemcpyHostToDevice, st));
+    if (mesh_work) (*mesh_work)((float*)part[1]);
     DynamicArgs D;
     D.instances = (hk_instance*)c->buf[4];
     D.n_instances = n;
@@ -2060,6 +2077,26 @@ static int enqueue_mesh_staging(hk_ctx* c, const std::vector<const hk_mesh_desc*
     return HK_OK;
 }
 
+// The checks of a mesh whose vertices are rewritten in place (hk_update_meshes, hk_set_mesh_skins, hk_skin_meshes), `who`
+// in front of the message, for the known slice c->meshes[at]: a BLAS the device can rebuild, and a vertex_count that
+// covers the stored indices and stays inside the slice.
+static int mesh_rewritable(hk_ctx* c, const std::string& who, size_t at, uint32_t vertex_count)
+{
+    const hk_ctx::MeshSlice& s = c->meshes[at];
+    const hk_mesh_index& mesh = s.index;
+    if (s.vertex_need == HK_U32_MAX)
+        return fail(c, HK_ERR_INVALID, who + ": its BLAS is not 3k - 2 nodes over k primitives of the scene; cannot rebuild");
+    // the vertex slice ends where the array or the next instanced mesh's vertices begin
+    uint32_t room = c->count[0] - mesh.vertex;
+    for (const hk_ctx::MeshSlice& o : c->meshes)
+        if (o.index.vertex > mesh.vertex) room = std::min(room, o.index.vertex - mesh.vertex);
+    if (vertex_count < s.vertex_need)
+        return fail(c, HK_ERR_INVALID, who + ": vertex_count does not cover the vertex indices of its primitives");
+    if (vertex_count > room)
+        return fail(c, HK_ERR_INVALID, who + ": vertex_count reaches past its vertex slice");
+    return HK_OK;
+}
+
 int hk_update_meshes(hk_ctx* c, const hk_mesh_update* meshes, uint32_t mesh_count, const float* models,
                      const float* local_aabbs, uint32_t count, void* stream)
 {
@@ -2083,17 +2120,7 @@ int hk_update_meshes(hk_ctx* c, const hk_mesh_update* meshes, uint32_t mesh_coun
         if (at == c->meshes.size()) return fail(c, HK_ERR_INVALID, who + " is not an instanced mesh of the uploaded scene");
         for (uint32_t j = 0; j < k; ++j)
             if (ml.slice[j] == at) return fail(c, HK_ERR_INVALID, who + " is listed twice");
-        const hk_ctx::MeshSlice& s = c->meshes[at];
-        if (s.vertex_need == HK_U32_MAX)
-            return fail(c, HK_ERR_INVALID, who + ": its BLAS is not 3k - 2 nodes over k primitives of the scene; cannot rebuild");
-        // the vertex slice ends where the array or the next instanced mesh's vertices begin
-        uint32_t room = c->count[0] - u.mesh.vertex;
-        for (const hk_ctx::MeshSlice& o : c->meshes)
-            if (o.index.vertex > u.mesh.vertex) room = std::min(room, o.index.vertex - u.mesh.vertex);
-        if (u.vertex_count < s.vertex_need)
-            return fail(c, HK_ERR_INVALID, who + ": vertex_count does not cover the vertex indices of its primitives");
-        if (u.vertex_count > room)
-            return fail(c, HK_ERR_INVALID, who + ": vertex_count reaches past its vertex slice");
+        HK_TRY(mesh_rewritable(c, who, at, u.vertex_count));
         tris[k] = (u.mesh.node[1] + 2u) / 3u;
         if ((size_t)n_vertices + u.vertex_count > 0x40000000u || (size_t)n_shapes + tris[k] > 0x40000000u)
             return fail(c, HK_ERR_INVALID, "hk_update_meshes: too many vertices or primitives in one call");
@@ -2120,6 +2147,179 @@ int hk_update_meshes(hk_ctx* c, const hk_mesh_update* meshes, uint32_t mesh_coun
     HK_HIP(c, hipGetLastError());
     ml.device = A.M.levels;
     return rebuild_instances(c, models, local_aabbs, count, st, &ml);
+}
+
+// The four resident skin streams in one block at `cap` vertices each (hk_ctx::skin_block), every stream 256-aligned
+struct SkinStreams {
+    float* positions;
+    float* normals;
+    uint2* indices;
+    float4* weights;
+    size_t bytes;
+};
+static SkinStreams skin_streams(void* block, size_t cap)
+{
+    const size_t sz[4] = {cap * 12, cap * 12, cap * 8, cap * 16};
+    char* p = (char*)block;
+    SkinStreams s;
+    s.positions = (float*)p;
+    s.normals = (float*)(p + carve_bytes(sz, 1));
+    s.indices = (uint2*)(p + carve_bytes(sz, 2));
+    s.weights = (float4*)(p + carve_bytes(sz, 3));
+    s.bytes = carve_bytes(sz, 4);
+    return s;
+}
+static size_t find_skin(const std::vector<hk_ctx::Skin>& skins, const hk_mesh_index& x)
+{
+    size_t k = 0;
+    while (k < skins.size() && std::memcmp(&skins[k].index, &x, sizeof(x)) != 0) ++k;
+    return k;
+}
+
+int hk_set_mesh_skins(hk_ctx* c, const hk_mesh_skin* skins, uint32_t n, void* stream)
+{
+    if (!c) return HK_ERR_INVALID;
+    if (!c->has_scene) return fail(c, HK_ERR_STATE, "no scene uploaded (hk_scene_upload)");
+    if (n && !skins) return fail(c, HK_ERR_INVALID, "hk_set_mesh_skins: null pointer");
+    // the whole list on the host first: a refusal leaves the set before as it was
+    std::vector<hk_ctx::Skin> set(n);
+    uint64_t total = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+        const hk_mesh_skin& s = skins[k];
+        const std::string who = "hk_set_mesh_skins: skin " + std::to_string(k);
+        if (!s.positions || !s.joint_indices || !s.joint_weights)
+            return fail(c, HK_ERR_INVALID, who + " has a null pointer (positions, joint_indices, joint_weights)");
+        const size_t at = find_slice(c->meshes, s.mesh);
+        if (at == c->meshes.size()) return fail(c, HK_ERR_INVALID, who + " is not a known mesh slice of the scene");
+        for (uint32_t j = 0; j < k; ++j)
+            if (std::memcmp(&set[j].index, &s.mesh, sizeof(s.mesh)) == 0)
+                return fail(c, HK_ERR_INVALID, who + " is listed twice");
+        HK_TRY(mesh_rewritable(c, who, at, s.vertex_count));
+        if (s.joint_count == 0 || s.joint_count > 65536u)
+            return fail(c, HK_ERR_INVALID, who + ": joint_count is outside 1 .. 65536");
+        for (size_t i = 0; i < 4 * (size_t)s.vertex_count; ++i)
+            if (s.joint_indices[i] >= s.joint_count)
+                return fail(c, HK_ERR_INVALID, who + ": vertex " + std::to_string(i / 4) + " has a joint index " +
+                                                   std::to_string(s.joint_indices[i]) + " >= joint_count");
+        if (total + s.vertex_count > 0x40000000u) return fail(c, HK_ERR_INVALID, "hk_set_mesh_skins: too many vertices");
+        set[k] = hk_ctx::Skin{s.mesh, s.vertex_count, s.joint_count, (uint32_t)total, s.normals != nullptr};
+        total += s.vertex_count;
+    }
+    (void)hipSetDevice(c->device);
+    hipStream_t st = pick(c, stream);
+    if (total > c->skin_cap) {  // (the new block first: out of memory leaves the set before in place)
+        void* block = nullptr;
+        HK_HIP(c, hipMalloc(&block, skin_streams((void*)0, (size_t)total).bytes));
+        HK_HIP(c, hipStreamSynchronize(st));
+        release(c->skin_block);
+        c->skin_block = block;
+        c->skin_cap = (size_t)total;
+    }
+    c->skins.clear();  // (the streams are overwritten from here on)
+    const SkinStreams S = skin_streams(c->skin_block, c->skin_cap);
+    for (uint32_t k = 0; k < n; ++k) {
+        const hk_mesh_skin& s = skins[k];
+        const size_t v0 = set[k].vertex0, nv = s.vertex_count;
+        if (!nv) continue;
+        HK_HIP(c, hipMemcpyAsync(S.positions + 3 * v0, s.positions, nv * 12, hipMemcpyHostToDevice, st));
+        if (s.normals) HK_HIP(c, hipMemcpyAsync(S.normals + 3 * v0, s.normals, nv * 12, hipMemcpyHostToDevice, st));
+        HK_HIP(c, hipMemcpyAsync(S.indices + v0, s.joint_indices, nv * 8, hipMemcpyHostToDevice, st));
+        HK_HIP(c, hipMemcpyAsync(S.weights + v0, s.joint_weights, nv * 16, hipMemcpyHostToDevice, st));
+    }
+    HK_HIP(c, hipStreamSynchronize(st));
+    c->skins = std::move(set);
+    return HK_OK;
+}
+
+int hk_skin_meshes(hk_ctx* c, const hk_skin_pose* poses, uint32_t n, const float* models, const float* local_aabbs,
+                   uint32_t count, void* stream)
+{
+    if (!c) return HK_ERR_INVALID;
+    if (!models || !local_aabbs || (n && !poses)) return fail(c, HK_ERR_INVALID, "hk_skin_meshes: null pointer");
+    HK_TRY(update_args_ok(c, count, "hk_skin_meshes"));
+    // every pose against the registered skins and the registry, before any device work: each a staged mesh with no
+    // host streams (k_skin_vertices fills its part of them)
+    std::vector<hk_mesh_desc> descs(n);
+    std::vector<const hk_mesh_desc*> list(n);
+    std::vector<hk_mesh_index> slices(n);
+    std::vector<uint32_t> tris(n);
+    std::vector<size_t> skin_of(n);
+    std::vector<SkinSource> sources(n);
+    MeshLevels ml;
+    ml.slice.resize(n);
+    uint64_t n_vertices = 0, n_shapes = 0, n_joints = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+        const hk_skin_pose& p = poses[k];
+        const std::string who = "hk_skin_meshes: pose " + std::to_string(k);
+        if (!p.joints) return fail(c, HK_ERR_INVALID, who + " has a null pointer (joints)");
+        const size_t sk = find_skin(c->skins, p.mesh);
+        if (sk == c->skins.size())
+            return fail(c, HK_ERR_INVALID, who + " names a mesh with no registered skin (hk_set_mesh_skins)");
+        for (uint32_t j = 0; j < k; ++j)
+            if (skin_of[j] == sk) return fail(c, HK_ERR_INVALID, who + " poses a mesh twice");
+        const hk_ctx::Skin& s = c->skins[sk];
+        if (p.joint_count != s.joint_count)
+            return fail(c, HK_ERR_INVALID, who + ": joint_count " + std::to_string(p.joint_count) +
+                                               " differs from the registered skin's " + std::to_string(s.joint_count));
+        const size_t at = find_slice(c->meshes, s.index);
+        if (at == c->meshes.size()) return fail(c, HK_ERR_INVALID, who + " is not a known mesh slice of the scene");
+        HK_TRY(mesh_rewritable(c, who, at, s.vertex_count));
+        tris[k] = (s.index.node[1] + 2u) / 3u;
+        if (n_vertices + s.vertex_count > 0x40000000u || n_shapes + tris[k] > 0x40000000u)
+            return fail(c, HK_ERR_INVALID, "hk_skin_meshes: too many vertices or primitives in one call");
+        descs[k] = hk_mesh_desc{nullptr, nullptr, nullptr, s.vertex_count, nullptr, 0u, HKS_TRIANGLE_LIST};
+        list[k] = &descs[k];
+        slices[k] = s.index;
+        skin_of[k] = sk;
+        sources[k] = SkinSource{s.vertex0, (uint32_t)n_joints, s.index};
+        ml.slice[k] = (uint32_t)at;
+        n_vertices += s.vertex_count;
+        n_shapes += tris[k];
+        n_joints += s.joint_count;
+    }
+    (void)hipSetDevice(c->device);
+    hipStream_t st = pick(c, stream);
+    if (n == 0) return rebuild_instances(c, models, local_aabbs, count, st, nullptr);
+    HK_TRY(c->sch.gb_join(st));
+    HK_TRY(c->sch.gb_serialize(false));
+    // the caller's part of the staging: the palettes one after another, then the SkinSource table
+    const size_t palette_bytes = ((size_t)n_joints * 64 + 255) & ~(size_t)255;
+    MeshStaging stage;
+    plan_mesh_staging(list, slices.data(), tris.data(), n_vertices, n_shapes, 0,
+                      palette_bytes + (size_t)n * sizeof(SkinSource), &stage);
+    for (std::vector<MeshUpdate>* t : {&stage.tab, &stage.by_size})
+        for (MeshUpdate& m : *t) m.has_normals = c->skins[skin_of[m.slot]].has_normals ? 1u : 0u;
+    MeshAddArgs A;
+    char* extra = nullptr;
+    HK_TRY(enqueue_mesh_staging(c, list, stage, st, &A, &extra));
+    for (uint32_t k = 0; k < n; ++k)
+        HK_HIP(c, hipMemcpyAsync(extra + (size_t)sources[k].joint0 * 64, poses[k].joints, (size_t)poses[k].joint_count * 64,
+                                 hipMemcpyHostToDevice, st));
+    HK_HIP(c, hipMemcpyAsync(extra + palette_bytes, sources.data(), (size_t)n * sizeof(SkinSource), hipMemcpyHostToDevice, st));
+    const SkinStreams S = skin_streams(c->skin_block, c->skin_cap);
+    SkinArgs K;
+    K.table = A.M.table;
+    K.sources = (const SkinSource*)(extra + palette_bytes);
+    K.n_meshes = n;
+    K.n_vertices = (uint32_t)n_vertices;
+    K.bind_positions = S.positions;
+    K.bind_normals = S.normals;
+    K.joint_indices = S.indices;
+    K.joint_weights = S.weights;
+    K.palettes = (const float4*)extra;
+    K.positions = const_cast<float*>(A.M.positions);
+    K.normals = const_cast<float*>(A.M.normals);
+    // after rebuild_instances' uploads, so that the posed boxes land on the device copy of local_aabbs
+    const std::function<void(float*)> work = [&](float* device_aabbs) {
+        timed(c, "skin_meshes", st, [&] {
+            launch_skin_vertices(K, st);
+            launch_mesh_update(A.M, st);
+            refresh_blas_derivatives(c, st, c->count[2]);
+            launch_skin_bounds(K, (const hk_instance*)c->buf[4], count, device_aabbs, st);
+        });
+    };
+    ml.device = A.M.levels;
+    return rebuild_instances(c, models, local_aabbs, count, st, &ml, nullptr, &work);
 }
 
 // the checks hk_set_instances and hk_set_meshes share before the set is planned: the scene's BVHs can be rebuilt, and
@@ -2509,6 +2709,7 @@ int hk_set_meshes(hk_ctx* c, const hk_mesh_entry* list, uint32_t mesh_count, hk_
     for (uint32_t k = 0; k < n_sources; ++k) plan.registry[plan.source_entry[k]].depth = levels[k];
     for (int i = 0; i < 3; ++i) c->count[i] = plan.after[i];
     c->meshes = plan.registry;
+    c->skins.clear();  // (the slices moved: hk_set_mesh_skins registers the new ones)
     std::memcpy(slices, plan.slices.data(), plan.slices.size() * sizeof(hk_mesh_index));
     return rebuild_instances(c, models, local_aabbs, count, st, nullptr, &change);
 }

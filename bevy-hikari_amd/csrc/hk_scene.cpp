@@ -9,6 +9,7 @@
 //   prepare_instances            instance.rs:245-444 (AABB, TLAS, emissives, light BVH)
 //   bvh 0.7.1 BVH::build + flatten_custom (third-party, restated from its published algorithm)
 #include "../../include/hikari_scene.h"
+#include "../../include/hk_skin.h"
 
 #include <algorithm>
 #include <cmath>
@@ -666,6 +667,40 @@ int hks_tone_rect(const int32_t keep[4], const int32_t window[4], int32_t row0, 
     launch[2] = (int32_t)((x1 + r - 1) / r * r);
     launch[3] = (int32_t)y1;
     return 1;
+}
+
+// Linear blend skinning by include/hk_skin.h's rule, vertex by vertex, and the posed mesh's Aabb by hks_add_mesh's own
+// fold (Aabb::grow in vertex order) and hks_build's centre and half extents.  Everything is checked before the first
+// store.
+int hks_skin_vertices(const float* positions, const float* normals, const uint16_t* joint_indices,
+                      const float* joint_weights, uint32_t vertex_count, const float* joints, uint32_t joint_count,
+                      float* out_positions, float* out_normals, float out_aabb[6])
+{
+    if (!positions || !joint_indices || !joint_weights || !joints || !out_positions) return HK_ERR_INVALID;
+    if ((normals == nullptr) != (out_normals == nullptr) || joint_count == 0) return HK_ERR_INVALID;
+    for (size_t i = 0; i < 4 * (size_t)vertex_count; ++i)
+        if (joint_indices[i] >= joint_count) return HK_ERR_INVALID;
+    Aabb box = Aabb::empty();
+    for (uint32_t v = 0; v < vertex_count; ++v) {
+        const uint16_t* ix = joint_indices + 4 * (size_t)v;
+        float M[12], p[3];
+        hk_skin_matrix(joints + 16 * (size_t)ix[0], joints + 16 * (size_t)ix[1], joints + 16 * (size_t)ix[2],
+                       joints + 16 * (size_t)ix[3], joint_weights + 4 * (size_t)v, M);
+        hk_skin_position(M, positions + 3 * (size_t)v, p);
+        if (normals) {
+            float n[3];
+            hk_skin_normal(M, normals + 3 * (size_t)v, n);
+            for (int k = 0; k < 3; ++k) out_normals[3 * (size_t)v + k] = n[k];
+        }
+        for (int k = 0; k < 3; ++k) out_positions[3 * (size_t)v + k] = p[k];
+        box.grow(v3(p[0], p[1], p[2]));
+    }
+    if (out_aabb) {
+        const V3 center = box.center(), half = (box.max - box.min) * 0.5f;
+        const float a[6] = {center.x, center.y, center.z, half.x, half.y, half.z};
+        std::memcpy(out_aabb, a, sizeof(a));
+    }
+    return HK_OK;
 }
 
 }  // extern "C"

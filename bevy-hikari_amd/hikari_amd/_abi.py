@@ -83,6 +83,18 @@ class hk_mesh_entry(C.Structure):
     _fields_ = [("source", C.POINTER(hk_mesh_desc)), ("keep", hk_mesh_index), ("vertex_count", C.c_uint32)]
 
 
+class hk_mesh_skin(C.Structure):
+    """include/hikari_amd.h hk_mesh_skin (one mesh's bind pose and rig for hk_set_mesh_skins)."""
+    _fields_ = [("mesh", hk_mesh_index), ("vertex_count", C.c_uint32), ("positions", C.c_void_p),
+                ("normals", C.c_void_p), ("joint_indices", C.c_void_p), ("joint_weights", C.c_void_p),
+                ("joint_count", C.c_uint32)]
+
+
+class hk_skin_pose(C.Structure):
+    """include/hikari_amd.h hk_skin_pose (one mesh's joint palette for hk_skin_meshes)."""
+    _fields_ = [("mesh", hk_mesh_index), ("joints", C.c_void_p), ("joint_count", C.c_uint32)]
+
+
 HK_INSTANCE_NEW = 0xFFFFFFFF
 
 
@@ -238,6 +250,8 @@ def lib() -> C.CDLL:
         "hk_set_meshes_counts": (i32, [C.POINTER(u32), C.POINTER(hk_mesh_entry), u32, C.POINTER(hk_mesh_index),
                                        C.POINTER(u32)]),
         "hk_set_meshes_counts_error": (C.c_char_p, []),
+        "hk_set_mesh_skins": (i32, [vp, C.POINTER(hk_mesh_skin), u32, vp]),
+        "hk_skin_meshes": (i32, [vp, C.POINTER(hk_skin_pose), u32, vp, vp, u32, vp]),
         "hk_scene_shared_transform": (i32, [vp, C.POINTER(i32)]),
         "hk_instance_set_counts": (i32, [C.POINTER(hk_scene_desc), C.POINTER(hk_instance_desc), u32, vp, C.POINTER(u32)]),
         "hk_read_scene_array": (i32, [vp, i32, vp, C.c_size_t]),
@@ -277,6 +291,7 @@ def lib() -> C.CDLL:
         "hk_tone_skip_info": (i32, [vp, C.POINTER(C.c_uint64), C.POINTER(i32)]),
         "hks_tone_rect": (i32, [C.POINTER(i32), C.POINTER(i32), i32, u32, C.POINTER(i32)]),
         "hks_keep_tiles": (i32, [C.POINTER(i32), C.POINTER(i32), i32, u32, C.POINTER(u32)]),
+        "hks_skin_vertices": (i32, [vp, vp, vp, vp, u32, vp, u32, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -299,6 +314,7 @@ EXPORTED_SYMBOLS = [
     "hks_instance_bounds", "hks_screen_bounds", "hk_tile_skip_info", "hk_tone_skip_info", "hks_tone_rect", "hks_keep_tiles",
     "hk_add_meshes", "hk_add_meshes_counts", "hk_add_meshes_counts_error", "hk_scene_capacity",
     "hk_set_meshes", "hk_set_meshes_counts", "hk_set_meshes_counts_error",
+    "hk_set_mesh_skins", "hk_skin_meshes", "hks_skin_vertices",
 ]
 
 

@@ -367,6 +367,58 @@ class HikariRenderer:
         _check(self.ctx, self._L.hk_update_meshes(self.ctx, ups, len(mesh_ids), m.ctypes.data, a.ctypes.data, len(m),
                                                   _stream(stream)), "hk_update_meshes")
 
+    def set_mesh_skins(self, scene: Scene, mesh_ids, keep_normals=(), stream=None) -> None:
+        """Register the skins of `scene.meshes[i]` for each i in `mesh_ids` (hk_set_mesh_skins): the mesh's positions and
+        normals as the bind pose and its `skin` (joint indices, weights, joint count) are copied to the device, where
+        skin_meshes reads them.  The call replaces the whole set (an empty list drops it).  keep_normals: mesh ids
+        registered without normals, whose uploaded normals a pose leaves alone."""
+        arr = (_abi.hk_mesh_skin * max(1, len(mesh_ids)))()
+        keep = []
+        for s, i in zip(arr, mesh_ids):
+            mesh = scene.meshes[i]
+            if mesh.skin is None:
+                raise ValueError(f"mesh {i} has no skin")
+            p = np.ascontiguousarray(mesh.positions, np.float32).reshape(-1, 3)
+            n = None if mesh.normals is None or i in keep_normals else \
+                np.ascontiguousarray(mesh.normals, np.float32).reshape(-1, 3)
+            ix = np.ascontiguousarray(mesh.skin.joint_indices, np.uint16).reshape(-1, 4)
+            w = np.ascontiguousarray(mesh.skin.joint_weights, np.float32).reshape(-1, 4)
+            if not (len(ix) == len(w) == len(p)) or (n is not None and len(n) != len(p)):
+                raise ValueError("positions, normals, joint_indices and joint_weights differ in length")
+            keep += [p, n, ix, w]
+            v, pr, n0, nc = scene.mesh_index(i)
+            s.mesh = _abi.hk_mesh_index(v, pr, (C.c_uint32 * 2)(n0, nc))
+            s.vertex_count = len(p)
+            s.positions = p.ctypes.data
+            s.normals = None if n is None else n.ctypes.data
+            s.joint_indices = ix.ctypes.data
+            s.joint_weights = w.ctypes.data
+            s.joint_count = int(mesh.skin.joint_count)
+        _check(self.ctx, self._L.hk_set_mesh_skins(self.ctx, arr, len(mesh_ids), _stream(stream)), "hk_set_mesh_skins")
+
+    def skin_meshes(self, scene: Scene, poses: dict, models=None, local_aabbs=None, stream=None) -> None:
+        """Pose skinned meshes on the GPU (hk_skin_meshes): poses = {mesh id: (joint_count, 16) column-major joint
+        matrices} for meshes registered by set_mesh_skins; the GPU skins their vertices, rebuilds their primitives and
+        BLAS and then everything update_instances rebuilds, with the posed meshes' boxes derived on the device.
+        `scene` gives the slices (scene.mesh_index) and, by default, models and local_aabbs (instance_models() /
+        instance_local_aabbs(); the rows of a posed mesh's instances are ignored)."""
+        m = np.ascontiguousarray(scene.instance_models() if models is None else models, np.float32).reshape(-1, 16)
+        a = np.ascontiguousarray(scene.instance_local_aabbs() if local_aabbs is None else local_aabbs,
+                                 np.float32).reshape(-1, 6)
+        if len(m) != len(a):
+            raise ValueError("models and local_aabbs differ in length")
+        arr = (_abi.hk_skin_pose * max(1, len(poses)))()
+        keep = []
+        for p, (i, joints) in zip(arr, poses.items()):
+            j = np.ascontiguousarray(joints, np.float32).reshape(-1, 16)
+            keep.append(j)
+            v, pr, n0, nc = scene.mesh_index(i)
+            p.mesh = _abi.hk_mesh_index(v, pr, (C.c_uint32 * 2)(n0, nc))
+            p.joints = j.ctypes.data
+            p.joint_count = len(j)
+        _check(self.ctx, self._L.hk_skin_meshes(self.ctx, arr, len(poses), m.ctypes.data, a.ctypes.data, len(m),
+                                                _stream(stream)), "hk_skin_meshes")
+
     def set_instances(self, scene: Scene, previous=None, materials: bool = False, stream=None, models=None,
                       local_aabbs=None) -> None:
         """A new instance set for the uploaded scene (hk_set_instances): entities spawned, despawned, hidden or given
@@ -699,6 +751,14 @@ class HikariPlugin:
     def update_meshes(self, scene: Scene, mesh_ids, models=None, local_aabbs=None, stream=None) -> None:
         """`prepare_mesh_assets` for modified meshes of unchanged topology (HikariRenderer.update_meshes)."""
         self.renderer.update_meshes(scene, mesh_ids, models, local_aabbs, stream)
+
+    def set_mesh_skins(self, scene: Scene, mesh_ids, keep_normals=(), stream=None) -> None:
+        """HikariRenderer.set_mesh_skins: the `SkinnedMesh` entities' bind poses and rigs, resident on the device."""
+        self.renderer.set_mesh_skins(scene, mesh_ids, keep_normals, stream)
+
+    def skin_meshes(self, scene: Scene, poses: dict, models=None, local_aabbs=None, stream=None) -> None:
+        """HikariRenderer.skin_meshes: this frame's joint palettes (`SkinnedMeshJoints` x inverse bind poses)."""
+        self.renderer.skin_meshes(scene, poses, models, local_aabbs, stream)
 
     def add_meshes(self, meshes, stream=None) -> list:
         """HikariRenderer.add_meshes: mesh assets created after the scene was uploaded (AssetEvent::Created)."""

@@ -241,12 +241,49 @@ def frame_inputs(number: int, camera: Camera, lights: _abi.hk_lights, width: int
 
 # ---------------------------------------------------------------- assets
 @dataclass
+class Skin:
+    """A mesh's rig: Bevy's `ATTRIBUTE_JOINT_INDEX` (Uint16x4) and `ATTRIBUTE_JOINT_WEIGHT` (Float32x4) per vertex, and
+    the number of joints its palette has (every index is below it)."""
+
+    joint_indices: np.ndarray  # (n, 4) u16
+    joint_weights: np.ndarray  # (n, 4) f32
+    joint_count: int
+
+
+@dataclass
 class Mesh:
     positions: np.ndarray  # (n, 3) f32
     normals: np.ndarray    # (n, 3) f32
     uvs: np.ndarray        # (n, 2) f32
     indices: Optional[np.ndarray] = None  # u32
     topology: int = 0      # 0 = TriangleList, 1 = TriangleStrip
+    skin: Optional[Skin] = None  # with it, positions and normals are the bind pose
+
+
+def skin_vertices(mesh: Mesh, joints, aabb: bool = False):
+    """The mesh posed on the host (hks_skin_vertices, include/hk_skin.h's rule): a copy of `mesh` whose positions and
+    normals (where it has any) are the skinned bind pose; the skin stays.  joints: (joint_count, 16) column-major
+    matrices (joint global transform x inverse bind pose).  aabb=True: (mesh, aabb) with the posed mesh's Bevy `Aabb`
+    (centre xyz, half extents xyz) as the builder derives it."""
+    if mesh.skin is None:
+        raise ValueError("the mesh has no skin")
+    p = np.ascontiguousarray(mesh.positions, np.float32).reshape(-1, 3)
+    n = None if mesh.normals is None else np.ascontiguousarray(mesh.normals, np.float32).reshape(-1, 3)
+    ix = np.ascontiguousarray(mesh.skin.joint_indices, np.uint16).reshape(-1, 4)
+    w = np.ascontiguousarray(mesh.skin.joint_weights, np.float32).reshape(-1, 4)
+    j = np.ascontiguousarray(joints, np.float32).reshape(-1, 16)
+    if not (len(ix) == len(w) == len(p)) or (n is not None and len(n) != len(p)):
+        raise ValueError("positions, normals, joint_indices and joint_weights differ in length")
+    if len(j) != mesh.skin.joint_count:
+        raise ValueError("joints needs one matrix per joint of the skin")
+    op, on, box = np.empty_like(p), None if n is None else np.empty_like(n), np.empty(6, np.float32)
+    rc = _abi.lib().hks_skin_vertices(p.ctypes.data, None if n is None else n.ctypes.data, ix.ctypes.data, w.ctypes.data,
+                                      len(p), j.ctypes.data, len(j), op.ctypes.data,
+                                      None if on is None else on.ctypes.data, box.ctypes.data)
+    if rc != 0:
+        raise _abi.HikariError(f"hks_skin_vertices refused its arguments ({rc}): a joint index >= joint_count?")
+    posed = Mesh(op, on, mesh.uvs, mesh.indices, mesh.topology, mesh.skin)
+    return (posed, box) if aabb else posed
 
 
 @dataclass
@@ -413,6 +450,22 @@ class Scene:
         before = [sizes(m) for m in self.meshes[:i]]
         return (sum(s[0] for s in before), sum(s[1] for s in before), sum(s[2] for s in before),
                 sizes(self.meshes[i])[2])
+
+    def posed(self, poses: dict, keep_normals: Sequence[int] = ()) -> "Scene":
+        """A copy of the scene whose meshes `poses` names ({mesh id: joints}) are skinned on the host (skin_vertices):
+        the host scene of HikariRenderer.skin_meshes.  keep_normals: mesh ids whose normals stay the bind pose's (a skin
+        registered without normals).  The other meshes, the materials, instances and textures are shared."""
+        s = Scene()
+        s.meshes = list(self.meshes)
+        for i, joints in poses.items():
+            m = self.meshes[i]
+            if i in keep_normals:
+                p = skin_vertices(Mesh(m.positions, None, m.uvs, m.indices, m.topology, m.skin), joints)
+                s.meshes[i] = Mesh(p.positions, m.normals, m.uvs, m.indices, m.topology, m.skin)
+            else:
+                s.meshes[i] = skin_vertices(m, joints)
+        s.materials, s.instances, s.textures = self.materials, self.instances, self.textures
+        return s
 
     def instance_models(self) -> np.ndarray:
         """(n, 16) float32 column-major model matrices of the instances, in upload order."""

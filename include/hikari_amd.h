@@ -440,6 +440,62 @@ int hk_set_meshes(hk_ctx* ctx, const hk_mesh_entry* list, uint32_t mesh_count, h
 int hk_set_meshes_counts(const uint32_t before[9], const hk_mesh_entry* list, uint32_t mesh_count,
                          hk_mesh_index* slices, uint32_t after[9]);
 const char* hk_set_meshes_counts_error(void);
+
+/* Skinned meshes.  The reference does not skin (its README leaves "Skinned animation" unticked); a
+ * Bevy scene does, in the mesh vertex shader (bevy_pbr skinning.wgsl, recalled: include/hk_skin.h states the rule and
+ * pins its evaluation order).  A path tracer needs the posed vertices in its vertex and primitive arrays and a BLAS
+ * over them, so posing is hk_update_meshes with a device source: the bind pose and the rig are resident, a pose costs
+ * the host one joint palette (64 bytes per joint) and one call.
+ *
+ * hk_set_mesh_skins replaces the context's WHOLE skin set (n == 0 drops it): for each listed mesh the bind pose, joint
+ * indices and joint weights are copied into device memory the context owns, as separate streams (12-byte positions and
+ * normals, one 8-byte load of the four indices, one 16-byte load of the weights per vertex).  The streams keep a
+ * capacity beside their size: re-registering as many vertices or fewer allocates nothing.  Every check is made on the
+ * host before any device work, and a refusal leaves the context, its former skin set included, as it was.  It renders
+ * nothing and changes no scene array.  The set is dropped by hk_scene_upload and hk_set_meshes (slices move) and kept
+ * by hk_add_meshes, hk_set_instances and the updates.  Waits for the stream once.
+ * HK_ERR_INVALID with a message: a null list with n != 0, a null positions, joint_indices or joint_weights; `mesh` and
+ * vertex_count failing hk_update_meshes' checks (not a known slice; a BLAS that is not 3k - 2 nodes; vertex_count not
+ * covering the stored vertex indices, or reaching past the vertex slice); joint_count outside 1 .. 65536; a joint
+ * index >= joint_count; a mesh listed twice.  HK_ERR_STATE without a scene. */
+typedef struct hk_mesh_skin {
+    hk_mesh_index mesh;            /* a known slice (instanced, registered, or appended by hk_add_meshes) */
+    uint32_t vertex_count;         /* as hk_mesh_update's */
+    const float* positions;        /* bind pose, vertex_count x 3 */
+    const float* normals;          /* bind pose; NULL: the array's normals stay as they are */
+    const uint16_t* joint_indices; /* vertex_count x 4 */
+    const float* joint_weights;    /* vertex_count x 4 */
+    uint32_t joint_count;          /* every index < joint_count; 1 .. 65536 */
+} hk_mesh_skin;
+int hk_set_mesh_skins(hk_ctx* ctx, const hk_mesh_skin* skins, uint32_t n, void* stream);
+
+/* hk_skin_meshes poses the listed meshes ON THE GPU and rebuilds what depends on them.  joints: joint_count column-major
+ * 4 x 4 matrices (joint global transform x inverse bind pose, Bevy's SkinnedMeshUniform).  One thread per vertex writes
+ * the posed position and normal (hk_skin.h; the normal NOT normalised) where hk_update_meshes stages the host's, and
+ * from there the call IS hk_update_meshes: vertices, primitives, the BLAS by the host builder's exact operations, the
+ * device-only derivatives, the stack bound, then the instance rebuild with models and local_aabbs as in
+ * hk_update_instances.  The library derives each posed mesh's Bevy `Aabb` from the posed vertices itself (as
+ * hks_add_mesh folds a mesh's; hikari_scene.h hks_skin_vertices gives the same six floats) and uses it for every
+ * instance of that mesh: the caller's local_aabbs rows of those instances are ignored (they must still be readable),
+ * the rows of all other instances are used.  After the call all nine arrays are byte for byte what hks_build +
+ * hk_scene_upload give for the scene whose posed meshes hold hks_skin_vertices' output; meshes not posed in this call
+ * keep their bytes (a mesh posed earlier stays posed).  The bound behind bg_tile_skip stays unknown until the next
+ * instance update or upload, as after hk_update_meshes.  Motion vectors keep their rule (current geometry against the
+ * previous models; Bevy 0.9 has no previous-pose input either).  Waits for the stream once.  n == 0 is
+ * hk_update_instances.
+ * HK_ERR_INVALID with a message, the context unchanged and usable: a null pointer (poses with n != 0, a pose's joints,
+ * models, local_aabbs); count other than the instance count; a pose for a mesh with no registered skin; joint_count
+ * other than the skin's; a mesh posed twice; a mesh whose BLAS is not 3k - 2 nodes or whose slice no longer holds
+ * its vertex_count (hk_update_meshes' checks, made again).  HK_ERR_STATE without a scene.  A singular model fails after
+ * the rebuild, as in hk_update_instances. */
+typedef struct hk_skin_pose {
+    hk_mesh_index mesh;
+    const float* joints;
+    uint32_t joint_count;
+} hk_skin_pose;
+int hk_skin_meshes(hk_ctx* ctx, const hk_skin_pose* poses, uint32_t n, const float* models, const float* local_aabbs,
+                   uint32_t count, void* stream);
+
 /* the element capacities beside hk_scene_counts' counts, hk_scene_desc order: what each array holds before a call
  * has to allocate (hk_set_instances: 3, 4, 5, 7, 8; hk_add_meshes: 0, 1, 2; array 6 never grows).  HK_ERR_STATE
  * without a scene. */

@@ -76,6 +76,19 @@ int hks_tone_rect(const int32_t keep[4], const int32_t window[4], int32_t row0, 
  * pointer, tile == 0, an empty window). */
 int hks_keep_tiles(const int32_t keep[4], const int32_t window[4], int32_t row0, uint32_t tile, uint32_t tiles[4]);
 
+/* Linear blend skinning of a mesh's vertices on the host, by the rule of include/hk_skin.h (Bevy 0.9's skinning.wgsl
+ * as recalled, its evaluation order pinned there): the host side of hk_skin_meshes' contract, and what a caller without
+ * a device uses.  positions / normals: the bind pose, vertex_count x 3; joint_indices: vertex_count x 4 (Uint16x4,
+ * Bevy's ATTRIBUTE_JOINT_INDEX); joint_weights: vertex_count x 4, used as given; joints: joint_count column-major 4 x 4
+ * matrices (joint global transform x inverse bind pose).  out_positions / out_normals: vertex_count x 3, the normals not
+ * normalised; normals and out_normals may both be NULL.  out_aabb (may be NULL): the posed mesh's Bevy `Aabb`, centre
+ * xyz then half extents xyz, exactly as hks_add_mesh derives a mesh's from its vertices.  Returns 0, or HK_ERR_INVALID
+ * with nothing written for a null required pointer (positions, joint_indices, joint_weights, joints, out_positions;
+ * normals without out_normals or the reverse), joint_count == 0 or an index >= joint_count. */
+int hks_skin_vertices(const float* positions, const float* normals, const uint16_t* joint_indices,
+                      const float* joint_weights, uint32_t vertex_count, const float* joints, uint32_t joint_count,
+                      float* out_positions, float* out_normals, float out_aabb[6]);
+
 #ifdef __cplusplus
 }
 #endif
