@@ -1,6 +1,6 @@
 // hk_dynamic.hip — dynamic instances, deforming meshes, changed instance sets
-// (DESIGN §0 f8), appended meshes, new mesh lists and skinned meshes on
-// the device.
+// (DESIGN §0 f8), appended meshes, new mesh lists, skinned meshes and the
+// BLAS refit on the device.
 //
 // The reference re-runs `prepare_instances` on the CPU whenever a transform changes
 // (instance.rs:284-437: instance records with world AABBs and inverse-transpose models, the
@@ -17,6 +17,7 @@
 #include "hk_device.h"
 #include "hk_launch.h"
 #include "../../include/hk_skin.h"
+#include "../../include/hk_refit.h"
 
 namespace hk {
 
@@ -548,6 +549,96 @@ __global__ __launch_bounds__(256) void k_build_mesh_bvh(const MeshUpdate* tab, c
     const MeshUpdate m = tab[blockIdx.x];
     build_bvh<LDS>(shapes + m.shape0, m.shapes, buckets, blas + m.node0, idx + 2u * (size_t)m.shape0,
                    seg + 2u * (size_t)m.shape0, levels + m.slot);
+}
+
+// ---- BLAS refit (include/hk_refit.h: the rule, this project's own; the host side is hk_scene.cpp
+// hks_refit_nodes over the same header).  The listed slices keep their topology; every entry node's box becomes the
+// hk_minf / hk_maxf fold of the shape boxes (k_update_mesh_geometry's scratch) of the leaves stored in its range
+// (i, exit).  The fold has no order, so no box is derived from another: every entry node reads leaves only, nothing
+// passes between workgroups inside a launch, and the two launches below are ordered by the stream alone.
+//   k_refit_small  one thread per node of the listed slices.  A leaf returns.  An entry node with
+//                  exit - i <= REFIT_SMALL scans its own range, folds in registers and stores its six words; a larger
+//                  one appends its index to the list of large nodes (one atomicAdd on a counter the stream zeroed
+//                  before; the list is read by the next launch only, in any order).
+//   k_refit_large  one workgroup per listed large node (a fixed grid strides over the list, whose length it reads from
+//                  the counter): a strided scan of the range by the 256 threads, block_reduce, six stores.
+// exit - i is 3p - 1 for a subtree of p primitives, so the spans either side of the threshold are REFIT_SMALL (p = 11)
+// and REFIT_SMALL + 3.  Work: each node is read once per entry node above it, O(n x depth) 4-byte reads out of L2.
+// Every index is bounded by the slice: an exit past the slice is clamped, a payload past the mesh's primitives is
+// skipped, the list takes no more entries than it has room for.  Only min / max of entry nodes are written; the words
+// the scans read (entry_index, exit_index) are written by nobody.
+constexpr uint32_t REFIT_SMALL = 32;
+constexpr uint32_t REFIT_LARGE_GRID = 2048;  // workgroups of k_refit_large at the most (8 per CU)
+// the listed mesh that holds node g of the listed slices laid end to end (mesh k starts at 3 x shape0 - 2k)
+HKD uint32_t refit_mesh_of(const MeshUpdate* tab, uint32_t n, uint32_t g)
+{
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (3u * tab[mid].shape0 - 2u * mid <= g) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+// the shape box of the leaf at node j of mesh m's slice joined into box (nothing for an entry node)
+HKD void refit_scan(const MeshUpdate& m, const hk_node* slice, const BBox* shapes, uint32_t j, float* box)
+{
+    const uint32_t entry = slice[j].entry_index;
+    if (!hk_refit_is_leaf(entry)) return;
+    const uint32_t t = hk_refit_leaf_primitive(entry);
+    if (t >= m.shapes) return;  // (a registered slice's payloads are its own primitives; never taken)
+    const BBox s = shapes[m.shape0 + t];
+    hk_refit_join(box, s.mn, s.mx);
+}
+__global__ __launch_bounds__(256) void k_refit_small(const MeshUpdate* tab, uint32_t n_meshes, uint32_t n_nodes,
+                                                     const BBox* shapes, hk_node* blas, uint32_t* large,
+                                                     uint32_t large_room, uint32_t* n_large)
+{
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= n_nodes) return;
+    const uint32_t k = refit_mesh_of(tab, n_meshes, g);
+    const MeshUpdate m = tab[k];
+    if (m.shapes == 0u) return;  // (refused on the host; never taken)
+    const uint32_t count = 3u * m.shapes - 2u, i = g - (3u * m.shape0 - 2u * k);
+    if (i >= count) return;
+    hk_node* slice = blas + m.node0;
+    if (hk_refit_is_leaf(slice[i].entry_index)) return;
+    const uint32_t exit = slice[i].exit_index, e = exit < count ? exit : count;
+    if (e > i && e - i > REFIT_SMALL) {
+        const uint32_t at = atomicAdd(n_large, 1u);
+        if (at < large_room) large[at] = g;
+        return;
+    }
+    float box[6];
+    hk_refit_empty(box);
+    for (uint32_t j = i + 1u; j < e; ++j) refit_scan(m, slice, shapes, j, box);
+    for (int c = 0; c < 3; ++c) {
+        slice[i].min[c] = box[c];
+        slice[i].max[c] = box[3 + c];
+    }
+}
+__global__ __launch_bounds__(256) void k_refit_large(const MeshUpdate* tab, uint32_t n_meshes, const BBox* shapes,
+                                                     hk_node* blas, const uint32_t* large, uint32_t large_room,
+                                                     const uint32_t* n_large)
+{
+    __shared__ CoopShared sh;
+    const uint32_t listed = *n_large < large_room ? *n_large : large_room;
+    const int op[6] = {0, 0, 0, 1, 1, 1};
+    for (uint32_t w = blockIdx.x; w < listed; w += gridDim.x) {  // (block-uniform)
+        const uint32_t g = large[w];
+        const uint32_t k = refit_mesh_of(tab, n_meshes, g);
+        const MeshUpdate m = tab[k];
+        const uint32_t count = 3u * m.shapes - 2u, i = g - (3u * m.shape0 - 2u * k);
+        if (m.shapes == 0u || i >= count) continue;  // (k_refit_small listed a node of the slice; never taken)
+        hk_node* slice = blas + m.node0;
+        const uint32_t exit = slice[i].exit_index, e = exit < count ? exit : count;
+        float box[6];
+        hk_refit_empty(box);
+        for (uint32_t j = i + 1u + threadIdx.x; j < e; j += 256u) refit_scan(m, slice, shapes, j, box);
+        block_reduce<6>(box, op, sh);
+        if (threadIdx.x < 3u) slice[i].min[threadIdx.x] = box[threadIdx.x];
+        else if (threadIdx.x < 6u) slice[i].max[threadIdx.x - 3u] = box[threadIdx.x];
+    }
 }
 
 // ---- skinned meshes (include/hk_skin.h: Bevy 0.9's skinning.wgsl as recalled, its order pinned there;
@@ -1107,12 +1198,35 @@ static void launch_mesh_builds(const MeshUpdateArgs& M, hipStream_t st)
                            M.table_by_size + M.n_lds, (const BBox*)M.shapes, M.buckets, M.blas, M.idx,
                            (Segment*)M.segments, M.levels);
 }
-void launch_mesh_update(const MeshUpdateArgs& M, hipStream_t st)
+void launch_mesh_geometry(const MeshUpdateArgs& M, hipStream_t st)
 {
     const uint32_t items = M.n_vertices + M.n_shapes;
     hipLaunchKernelGGL(k_update_mesh_geometry, dim3((items + 255u) / 256u), dim3(256), 0, st, M.table, M.n_meshes,
                        M.n_vertices, M.n_shapes, M.positions, M.normals, M.vertices, M.primitives, (BBox*)M.shapes);
+}
+void launch_mesh_update(const MeshUpdateArgs& M, hipStream_t st)
+{
+    launch_mesh_geometry(M, st);
     launch_mesh_builds(M, st);
+}
+void launch_refit_small(const MeshUpdateArgs& M, hipStream_t st)
+{
+    const uint32_t n_nodes = 3u * M.n_shapes - 2u * M.n_meshes;
+    (void)hipMemsetAsync(M.n_large, 0, 4, st);
+    hipLaunchKernelGGL(k_refit_small, dim3((n_nodes + 255u) / 256u), dim3(256), 0, st, M.table, M.n_meshes, n_nodes,
+                       (const BBox*)M.shapes, M.blas, M.large, 2u * M.n_shapes, M.n_large);
+}
+void launch_refit_large(const MeshUpdateArgs& M, hipStream_t st)
+{
+    if (M.large_bound == 0) return;
+    const uint32_t grid = M.large_bound < REFIT_LARGE_GRID ? M.large_bound : REFIT_LARGE_GRID;
+    hipLaunchKernelGGL(k_refit_large, dim3(grid), dim3(256), 0, st, M.table, M.n_meshes, (const BBox*)M.shapes, M.blas,
+                       (const uint32_t*)M.large, 2u * M.n_shapes, (const uint32_t*)M.n_large);
+}
+uint32_t mesh_refit_large_bound(uint32_t shapes)
+{
+    // the widest range below the root's, over shapes - 1 primitives, spans 3 (shapes - 1) - 1
+    return shapes >= 2u && 3u * (shapes - 1u) - 1u > REFIT_SMALL ? 2u * shapes - 2u : 0u;
 }
 void launch_mesh_add(const MeshAddArgs& A, hipStream_t st)
 {

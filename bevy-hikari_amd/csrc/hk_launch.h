@@ -209,11 +209,23 @@ struct MeshUpdateArgs {
     uint32_t* idx;                    // 2 x n_shapes
     void* segments;                   // 2 x n_shapes x 12 B
     uint32_t* levels;                 // n_meshes: split levels of each rebuilt BLAS (G-buffer stack bound)
+    // scratch of a refit, which builds nothing: it lies where idx and levels do
+    uint32_t* large;                  // 2 x n_shapes: the listed slices' large entry nodes (k_refit_small lists them)
+    uint32_t* n_large;                // their number
+    uint32_t large_bound;             // the sum of mesh_refit_large_bound over the list; 0: no slice can hold one
 };
 // vertex and primitive rewrite with the shape boxes (one launch), then the BLAS builds: one workgroup per mesh, one
 // launch per instantiation of the build (LDS-staged / global)
 void launch_mesh_update(const MeshUpdateArgs& M, hipStream_t st);
 uint32_t mesh_lds_shapes();
+// A refit (hk_refit_meshes / hk_skin_meshes_refit) in place of the builds, as three launches: the rewrite
+// alone; one thread per node of the listed slices (the small entry nodes refit, the large ones listed); one workgroup
+// per listed large node (nothing when large_bound is 0).  Only the min / max words of entry nodes are written.
+void launch_mesh_geometry(const MeshUpdateArgs& M, hipStream_t st);
+void launch_refit_small(const MeshUpdateArgs& M, hipStream_t st);
+void launch_refit_large(const MeshUpdateArgs& M, hipStream_t st);
+// how many large entry nodes a slice over `shapes` primitives can hold at the most
+uint32_t mesh_refit_large_bound(uint32_t shapes);
 
 // Skinned meshes (hk_skin_meshes, hk_dynamic.hip): beside each posed mesh's MeshUpdate record (vertex0:
 // its place in the staged position / normal streams, which k_skin_vertices writes and launch_mesh_update then reads),

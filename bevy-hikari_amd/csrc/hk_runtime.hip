@@ -1834,7 +1834,8 @@ static int carve(hk_ctx* c, void** scratch, size_t* have, const size_t* bytes, i
 // The instance rebuild on `st` (after the mesh rebuild of hk_update_meshes, if any) and its one wait: the one body of
 // hk_update_instances, hk_update_meshes and hk_set_instances.  set: the new instance set that replaces the current one
 // (null: the current set with new models).  mesh_work (hk_skin_meshes): what the caller enqueues on `st` between the
-// uploads and the instance kernels, given the device copy of local_aabbs, whose rows it may overwrite.
+// uploads and the instance kernels, given the device copy of local_aabbs, whose rows it may overwrite.  ml with no
+// slices (a refit): meshes changed and no depth did.
 static int rebuild_instances(hk_ctx* c, const float* models, const float* local_aabbs, uint32_t count, hipStream_t st,
                              const MeshLevels* ml, const SetChange* set = nullptr,
                              const std::function<void(float*)>* mesh_work = nullptr)
@@ -1927,7 +1928,8 @@ static int rebuild_instances(hk_ctx* c, const float* models, const float* local_
     uint32_t flags[4] = {0, 0, 0, 0};
     std::vector<uint32_t> levels(ml ? ml->slice.size() : 0);
     HK_HIP(c, hipMemcpyAsync(flags, part[8], 16, hipMemcpyDeviceToHost, st));
-    if (ml) HK_HIP(c, hipMemcpyAsync(levels.data(), ml->device, levels.size() * 4, hipMemcpyDeviceToHost, st));
+    if (!levels.empty())
+        HK_HIP(c, hipMemcpyAsync(levels.data(), ml->device, levels.size() * 4, hipMemcpyDeviceToHost, st));
     HK_HIP(c, hipStreamSynchronize(st));
     if (ml) {  // the deepest instanced BLAS now: a mesh that became shallower lowers the bound
         for (size_t k = 0; k < levels.size(); ++k) c->meshes[ml->slice[k]].depth = levels[k];
@@ -1983,16 +1985,19 @@ struct MeshStaging {
     std::vector<MeshUpdate> tab, by_size;
     std::vector<MeshSource> sources;
     uint32_t n_lds = 0, n_vertices = 0, n_shapes = 0, n_indices = 0;
+    uint32_t large_bound = 0;  // (a refit: MeshUpdateArgs::large_bound)
     static constexpr int PARTS = 12;
     size_t sz[PARTS] = {};
     size_t total = 0;
 };
 
 // meshes[k] goes to slices[k] with tris[k] triangles.  A deformed mesh (hk_update_meshes) has no uvs and no indices,
-// and may have no normals: MeshUpdate::has_normals says so, and its part of the normal stream is left unwritten.
+// and may have no normals: MeshUpdate::has_normals says so, and its part of the normal stream is left unwritten.  refit:
+// the meshes are refit, not built, so the table by size and the segments take no room (the list of large nodes lies
+// where the indices would, its counter where the levels would).
 static void plan_mesh_staging(const std::vector<const hk_mesh_desc*>& meshes, const hk_mesh_index* slices,
                               const uint32_t* tris, uint64_t n_vertices, uint64_t n_shapes, uint64_t n_indices,
-                              size_t extra, MeshStaging* S)
+                              size_t extra, MeshStaging* S, bool refit = false)
 {
     const uint32_t n = (uint32_t)meshes.size();
     S->tab.resize(n);
@@ -2012,15 +2017,16 @@ static void plan_mesh_staging(const std::vector<const hk_mesh_desc*>& meshes, co
         if (m.indices) i0 += m.index_count;
         uvs = uvs || m.uvs;
         S->n_lds += tris[k] <= mesh_lds_shapes() ? 1u : 0u;
+        S->large_bound += mesh_refit_large_bound(tris[k]);
     }
     for (int big = 0; big < 2; ++big)
         for (const MeshUpdate& m : S->tab)
             if ((m.shapes > mesh_lds_shapes()) == (big == 1)) S->by_size.push_back(m);
     const size_t nv = S->n_vertices, ns = S->n_shapes;
-    const size_t sz[MeshStaging::PARTS] = {(size_t)n * sizeof(MeshUpdate), (size_t)n * sizeof(MeshUpdate),
+    const size_t sz[MeshStaging::PARTS] = {(size_t)n * sizeof(MeshUpdate), refit ? 0 : (size_t)n * sizeof(MeshUpdate),
                                            (size_t)n * sizeof(MeshSource), nv * 12, nv * 12, uvs ? nv * 8 : 0,
-                                           (size_t)(S->n_indices ? S->n_indices : 1) * 4, ns * 24, ns * 8, ns * 24,
-                                           (size_t)n * 4, extra};
+                                           (size_t)(S->n_indices ? S->n_indices : 1) * 4, ns * 24, ns * 8,
+                                           refit ? 0 : ns * 24, (size_t)n * 4, extra};
     std::memcpy(S->sz, sz, sizeof(sz));
     S->total = carve_bytes(sz, MeshStaging::PARTS);
 }
@@ -2035,7 +2041,8 @@ static int enqueue_mesh_staging(hk_ctx* c, const std::vector<const hk_mesh_desc*
     const size_t n = meshes.size();
     if (n) {
         HK_HIP(c, hipMemcpyAsync(part[0], S.tab.data(), n * sizeof(MeshUpdate), hipMemcpyHostToDevice, st));
-        HK_HIP(c, hipMemcpyAsync(part[1], S.by_size.data(), n * sizeof(MeshUpdate), hipMemcpyHostToDevice, st));
+        if (S.sz[1])
+            HK_HIP(c, hipMemcpyAsync(part[1], S.by_size.data(), n * sizeof(MeshUpdate), hipMemcpyHostToDevice, st));
         HK_HIP(c, hipMemcpyAsync(part[2], S.sources.data(), n * sizeof(MeshSource), hipMemcpyHostToDevice, st));
     }
     for (size_t k = 0; k < n; ++k) {
@@ -2070,6 +2077,9 @@ static int enqueue_mesh_staging(hk_ctx* c, const std::vector<const hk_mesh_desc*
     M.idx = (uint32_t*)part[8];
     M.segments = part[9];
     M.levels = (uint32_t*)part[10];
+    M.large = (uint32_t*)part[8];
+    M.n_large = (uint32_t*)part[10];
+    M.large_bound = S.large_bound;
     A->sources = (const MeshSource*)part[2];
     A->uvs = (const float*)part[5];
     A->indices = (const uint32_t*)part[6];
@@ -2097,12 +2107,23 @@ static int mesh_rewritable(hk_ctx* c, const std::string& who, size_t at, uint32_
     return HK_OK;
 }
 
-int hk_update_meshes(hk_ctx* c, const hk_mesh_update* meshes, uint32_t mesh_count, const float* models,
-                     const float* local_aabbs, uint32_t count, void* stream)
+// The refit of the listed slices behind the rewrite, in place of launch_mesh_update's builds, each launch
+// timed under its own name
+static void enqueue_mesh_refit(hk_ctx* c, const MeshUpdateArgs& M, hipStream_t st)
+{
+    timed(c, "refit_geometry", st, [&] { launch_mesh_geometry(M, st); });
+    timed(c, "refit_small", st, [&] { launch_refit_small(M, st); });
+    timed(c, "refit_large", st, [&] { launch_refit_large(M, st); });
+    timed(c, "refit_derivatives", st, [&] { refresh_blas_derivatives(c, st, c->count[2]); });
+}
+
+// hk_update_meshes (fn = "hk_update_meshes") and hk_refit_meshes: one body, the BLAS step apart
+static int update_meshes(hk_ctx* c, const std::string& fn, bool refit, const hk_mesh_update* meshes, uint32_t mesh_count,
+                         const float* models, const float* local_aabbs, uint32_t count, void* stream)
 {
     if (!c) return HK_ERR_INVALID;
-    if (!meshes || !models || !local_aabbs) return fail(c, HK_ERR_INVALID, "hk_update_meshes: null pointer");
-    HK_TRY(update_args_ok(c, count, "hk_update_meshes"));
+    if (!meshes || !models || !local_aabbs) return fail(c, HK_ERR_INVALID, fn + ": null pointer");
+    HK_TRY(update_args_ok(c, count, fn.c_str()));
     // every listed mesh against what upload recorded (no device work before the list is accepted whole): a staged mesh
     // without uvs and indices
     std::vector<hk_mesh_desc> descs(mesh_count);
@@ -2114,7 +2135,7 @@ int hk_update_meshes(hk_ctx* c, const hk_mesh_update* meshes, uint32_t mesh_coun
     uint32_t n_vertices = 0, n_shapes = 0;
     for (uint32_t k = 0; k < mesh_count; ++k) {
         const hk_mesh_update& u = meshes[k];
-        const std::string who = "hk_update_meshes: mesh " + std::to_string(k);
+        const std::string who = fn + ": mesh " + std::to_string(k);
         if (!u.positions) return fail(c, HK_ERR_INVALID, who + " has no positions");
         const size_t at = find_slice(c->meshes, u.mesh);
         if (at == c->meshes.size()) return fail(c, HK_ERR_INVALID, who + " is not an instanced mesh of the uploaded scene");
@@ -2123,7 +2144,7 @@ int hk_update_meshes(hk_ctx* c, const hk_mesh_update* meshes, uint32_t mesh_coun
         HK_TRY(mesh_rewritable(c, who, at, u.vertex_count));
         tris[k] = (u.mesh.node[1] + 2u) / 3u;
         if ((size_t)n_vertices + u.vertex_count > 0x40000000u || (size_t)n_shapes + tris[k] > 0x40000000u)
-            return fail(c, HK_ERR_INVALID, "hk_update_meshes: too many vertices or primitives in one call");
+            return fail(c, HK_ERR_INVALID, fn + ": too many vertices or primitives in one call");
         descs[k] = hk_mesh_desc{u.positions, u.normals, nullptr, u.vertex_count, nullptr, 0u, HKS_TRIANGLE_LIST};
         list[k] = &descs[k];
         slices[k] = u.mesh;
@@ -2137,16 +2158,30 @@ int hk_update_meshes(hk_ctx* c, const hk_mesh_update* meshes, uint32_t mesh_coun
     HK_TRY(c->sch.gb_join(st));
     HK_TRY(c->sch.gb_serialize(false));
     MeshStaging stage;
-    plan_mesh_staging(list, slices.data(), tris.data(), n_vertices, n_shapes, 0, 0, &stage);
+    plan_mesh_staging(list, slices.data(), tris.data(), n_vertices, n_shapes, 0, 0, &stage, refit);
     MeshAddArgs A;
     HK_TRY(enqueue_mesh_staging(c, list, stage, st, &A, nullptr));
-    timed(c, "update_meshes", st, [&] {
-        launch_mesh_update(A.M, st);
-        refresh_blas_derivatives(c, st, c->count[2]);
-    });
+    if (refit)
+        enqueue_mesh_refit(c, A.M, st);
+    else
+        timed(c, "update_meshes", st, [&] {
+            launch_mesh_update(A.M, st);
+            refresh_blas_derivatives(c, st, c->count[2]);
+        });
     HK_HIP(c, hipGetLastError());
     ml.device = A.M.levels;
+    if (refit) ml.slice.clear();  // the topology stays, and so does every depth: no levels to read back
     return rebuild_instances(c, models, local_aabbs, count, st, &ml);
+}
+int hk_update_meshes(hk_ctx* c, const hk_mesh_update* meshes, uint32_t mesh_count, const float* models,
+                     const float* local_aabbs, uint32_t count, void* stream)
+{
+    return update_meshes(c, "hk_update_meshes", false, meshes, mesh_count, models, local_aabbs, count, stream);
+}
+int hk_refit_meshes(hk_ctx* c, const hk_mesh_update* meshes, uint32_t mesh_count, const float* models,
+                    const float* local_aabbs, uint32_t count, void* stream)
+{
+    return update_meshes(c, "hk_refit_meshes", true, meshes, mesh_count, models, local_aabbs, count, stream);
 }
 
 // The four resident skin streams in one block at `cap` vertices each (hk_ctx::skin_block), every stream 256-aligned
@@ -2231,12 +2266,13 @@ int hk_set_mesh_skins(hk_ctx* c, const hk_mesh_skin* skins, uint32_t n, void* st
     return HK_OK;
 }
 
-int hk_skin_meshes(hk_ctx* c, const hk_skin_pose* poses, uint32_t n, const float* models, const float* local_aabbs,
-                   uint32_t count, void* stream)
+// hk_skin_meshes (fn = "hk_skin_meshes") and hk_skin_meshes_refit: one body, the BLAS step apart
+static int skin_meshes(hk_ctx* c, const std::string& fn, bool refit, const hk_skin_pose* poses, uint32_t n,
+                       const float* models, const float* local_aabbs, uint32_t count, void* stream)
 {
     if (!c) return HK_ERR_INVALID;
-    if (!models || !local_aabbs || (n && !poses)) return fail(c, HK_ERR_INVALID, "hk_skin_meshes: null pointer");
-    HK_TRY(update_args_ok(c, count, "hk_skin_meshes"));
+    if (!models || !local_aabbs || (n && !poses)) return fail(c, HK_ERR_INVALID, fn + ": null pointer");
+    HK_TRY(update_args_ok(c, count, fn.c_str()));
     // every pose against the registered skins and the registry, before any device work: each a staged mesh with no
     // host streams (k_skin_vertices fills its part of them)
     std::vector<hk_mesh_desc> descs(n);
@@ -2250,7 +2286,7 @@ int hk_skin_meshes(hk_ctx* c, const hk_skin_pose* poses, uint32_t n, const float
     uint64_t n_vertices = 0, n_shapes = 0, n_joints = 0;
     for (uint32_t k = 0; k < n; ++k) {
         const hk_skin_pose& p = poses[k];
-        const std::string who = "hk_skin_meshes: pose " + std::to_string(k);
+        const std::string who = fn + ": pose " + std::to_string(k);
         if (!p.joints) return fail(c, HK_ERR_INVALID, who + " has a null pointer (joints)");
         const size_t sk = find_skin(c->skins, p.mesh);
         if (sk == c->skins.size())
@@ -2266,7 +2302,7 @@ int hk_skin_meshes(hk_ctx* c, const hk_skin_pose* poses, uint32_t n, const float
         HK_TRY(mesh_rewritable(c, who, at, s.vertex_count));
         tris[k] = (s.index.node[1] + 2u) / 3u;
         if (n_vertices + s.vertex_count > 0x40000000u || n_shapes + tris[k] > 0x40000000u)
-            return fail(c, HK_ERR_INVALID, "hk_skin_meshes: too many vertices or primitives in one call");
+            return fail(c, HK_ERR_INVALID, fn + ": too many vertices or primitives in one call");
         descs[k] = hk_mesh_desc{nullptr, nullptr, nullptr, s.vertex_count, nullptr, 0u, HKS_TRIANGLE_LIST};
         list[k] = &descs[k];
         slices[k] = s.index;
@@ -2286,7 +2322,7 @@ int hk_skin_meshes(hk_ctx* c, const hk_skin_pose* poses, uint32_t n, const float
     const size_t palette_bytes = ((size_t)n_joints * 64 + 255) & ~(size_t)255;
     MeshStaging stage;
     plan_mesh_staging(list, slices.data(), tris.data(), n_vertices, n_shapes, 0,
-                      palette_bytes + (size_t)n * sizeof(SkinSource), &stage);
+                      palette_bytes + (size_t)n * sizeof(SkinSource), &stage, refit);
     for (std::vector<MeshUpdate>* t : {&stage.tab, &stage.by_size})
         for (MeshUpdate& m : *t) m.has_normals = c->skins[skin_of[m.slot]].has_normals ? 1u : 0u;
     MeshAddArgs A;
@@ -2311,6 +2347,13 @@ int hk_skin_meshes(hk_ctx* c, const hk_skin_pose* poses, uint32_t n, const float
     K.normals = const_cast<float*>(A.M.normals);
     // after rebuild_instances' uploads, so that the posed boxes land on the device copy of local_aabbs
     const std::function<void(float*)> work = [&](float* device_aabbs) {
+        if (refit) {
+            timed(c, "refit_skin_vertices", st, [&] { launch_skin_vertices(K, st); });
+            enqueue_mesh_refit(c, A.M, st);
+            timed(c, "refit_skin_bounds", st,
+                  [&] { launch_skin_bounds(K, (const hk_instance*)c->buf[4], count, device_aabbs, st); });
+            return;
+        }
         timed(c, "skin_meshes", st, [&] {
             launch_skin_vertices(K, st);
             launch_mesh_update(A.M, st);
@@ -2319,7 +2362,18 @@ int hk_skin_meshes(hk_ctx* c, const hk_skin_pose* poses, uint32_t n, const float
         });
     };
     ml.device = A.M.levels;
+    if (refit) ml.slice.clear();  // the topology stays, and so does every depth: no levels to read back
     return rebuild_instances(c, models, local_aabbs, count, st, &ml, nullptr, &work);
+}
+int hk_skin_meshes(hk_ctx* c, const hk_skin_pose* poses, uint32_t n, const float* models, const float* local_aabbs,
+                   uint32_t count, void* stream)
+{
+    return skin_meshes(c, "hk_skin_meshes", false, poses, n, models, local_aabbs, count, stream);
+}
+int hk_skin_meshes_refit(hk_ctx* c, const hk_skin_pose* poses, uint32_t n, const float* models, const float* local_aabbs,
+                         uint32_t count, void* stream)
+{
+    return skin_meshes(c, "hk_skin_meshes_refit", true, poses, n, models, local_aabbs, count, stream);
 }
 
 // the checks hk_set_instances and hk_set_meshes share before the set is planned: the scene's BVHs can be rebuilt, and

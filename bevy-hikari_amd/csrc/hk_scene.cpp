@@ -10,6 +10,7 @@
 //   bvh 0.7.1 BVH::build + flatten_custom (third-party, restated from its published algorithm)
 #include "../../include/hikari_scene.h"
 #include "../../include/hk_skin.h"
+#include "../../include/hk_refit.h"
 
 #include <algorithm>
 #include <cmath>
@@ -699,6 +700,60 @@ int hks_skin_vertices(const float* positions, const float* normals, const uint16
         const V3 center = box.center(), half = (box.max - box.min) * 0.5f;
         const float a[6] = {center.x, center.y, center.z, half.x, half.y, half.z};
         std::memcpy(out_aabb, a, sizeof(a));
+    }
+    return HK_OK;
+}
+
+// A BLAS refit by include/hk_refit.h's rule.  The slice is checked as a bvh-0.7.1 flatten before the first store: every
+// entry node's range (i, exit) is a leaf, or two entry nodes whose ranges tile it, so by induction over the range
+// lengths the nodes form one tree over [0, node_count), and each primitive is some leaf's payload once.  The flatten
+// is pre-order, so one pass down the indices finds the boxes an entry node joins already refit.
+int hks_refit_nodes(const hk_primitive* primitives, uint32_t primitive_count, hk_node* nodes, uint32_t node_count)
+{
+    if (!primitives || !nodes || primitive_count == 0) return HK_ERR_INVALID;
+    if ((uint64_t)node_count != 3u * (uint64_t)primitive_count - 2u) return HK_ERR_INVALID;
+    const uint32_t n = node_count;
+    auto leaf = [&](uint32_t i) { return hk_refit_is_leaf(nodes[i].entry_index) != 0; };
+    // an entry node at i whose range ends at `end`
+    auto entry_to = [&](uint32_t i, uint32_t end) { return i < n && !leaf(i) && nodes[i].exit_index == end; };
+    std::vector<bool> seen(primitive_count, false);
+    for (uint32_t i = 0; i < n; ++i) {
+        const hk_node& nd = nodes[i];
+        if (leaf(i)) {
+            const uint32_t t = hk_refit_leaf_primitive(nd.entry_index);
+            if (nd.exit_index != i + 1u || t >= primitive_count || seen[t]) return HK_ERR_INVALID;
+            seen[t] = true;
+            continue;
+        }
+        const uint32_t e = nd.exit_index;
+        if (nd.entry_index != i + 1u || e <= i + 1u || e > n) return HK_ERR_INVALID;
+        if (leaf(i + 1u)) {
+            if (e != i + 2u) return HK_ERR_INVALID;
+        } else {
+            const uint32_t mid = nodes[i + 1u].exit_index;
+            if (mid <= i + 1u || mid >= e || !entry_to(mid, e)) return HK_ERR_INVALID;
+        }
+    }
+    // the root: a lone leaf, or the two entry nodes of the root's children tiling the slice
+    if (primitive_count == 1u ? !leaf(0) : (leaf(0) || !entry_to(nodes[0].exit_index, n))) return HK_ERR_INVALID;
+    for (uint32_t i = n; i-- > 0;) {
+        hk_node& nd = nodes[i];
+        if (leaf(i)) continue;
+        float box[6];
+        hk_refit_empty(box);
+        if (leaf(i + 1u)) {
+            float s[6];
+            hk_refit_shape(primitives + hk_refit_leaf_primitive(nodes[i + 1u].entry_index), s);
+            hk_refit_join(box, s, s + 3);
+        } else {
+            const hk_node &a = nodes[i + 1u], &b = nodes[a.exit_index];
+            hk_refit_join(box, a.min, a.max);
+            hk_refit_join(box, b.min, b.max);
+        }
+        for (int k = 0; k < 3; ++k) {
+            nd.min[k] = box[k];
+            nd.max[k] = box[3 + k];
+        }
     }
     return HK_OK;
 }

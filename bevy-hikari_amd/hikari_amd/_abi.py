@@ -252,6 +252,8 @@ def lib() -> C.CDLL:
         "hk_set_meshes_counts_error": (C.c_char_p, []),
         "hk_set_mesh_skins": (i32, [vp, C.POINTER(hk_mesh_skin), u32, vp]),
         "hk_skin_meshes": (i32, [vp, C.POINTER(hk_skin_pose), u32, vp, vp, u32, vp]),
+        "hk_refit_meshes": (i32, [vp, C.POINTER(hk_mesh_update), u32, vp, vp, u32, vp]),
+        "hk_skin_meshes_refit": (i32, [vp, C.POINTER(hk_skin_pose), u32, vp, vp, u32, vp]),
         "hk_scene_shared_transform": (i32, [vp, C.POINTER(i32)]),
         "hk_instance_set_counts": (i32, [C.POINTER(hk_scene_desc), C.POINTER(hk_instance_desc), u32, vp, C.POINTER(u32)]),
         "hk_read_scene_array": (i32, [vp, i32, vp, C.c_size_t]),
@@ -292,6 +294,7 @@ def lib() -> C.CDLL:
         "hks_tone_rect": (i32, [C.POINTER(i32), C.POINTER(i32), i32, u32, C.POINTER(i32)]),
         "hks_keep_tiles": (i32, [C.POINTER(i32), C.POINTER(i32), i32, u32, C.POINTER(u32)]),
         "hks_skin_vertices": (i32, [vp, vp, vp, vp, u32, vp, u32, vp, vp, vp]),
+        "hks_refit_nodes": (i32, [vp, u32, vp, u32]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -315,6 +318,7 @@ EXPORTED_SYMBOLS = [
     "hk_add_meshes", "hk_add_meshes_counts", "hk_add_meshes_counts_error", "hk_scene_capacity",
     "hk_set_meshes", "hk_set_meshes_counts", "hk_set_meshes_counts_error",
     "hk_set_mesh_skins", "hk_skin_meshes", "hks_skin_vertices",
+    "hk_refit_meshes", "hk_skin_meshes_refit", "hks_refit_nodes",
 ]
 
 

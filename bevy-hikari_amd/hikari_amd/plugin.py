@@ -340,11 +340,14 @@ class HikariRenderer:
         _check(self.ctx, self._L.hk_update_instances(self.ctx, m.ctypes.data, a.ctypes.data, len(m), _stream(stream)),
                "hk_update_instances")
 
-    def update_meshes(self, scene: Scene, mesh_ids, models=None, local_aabbs=None, stream=None) -> None:
+    def update_meshes(self, scene: Scene, mesh_ids, models=None, local_aabbs=None, stream=None,
+                      refit: bool = False) -> None:
         """Deformed meshes of an uploaded scene (hk_update_meshes): the positions and normals of `scene.meshes[i]` for
         each i in `mesh_ids` (same topology as uploaded) replace the uploaded ones on the GPU, which rebuilds those
         meshes' primitives and BLAS and then everything update_instances rebuilds.  models / local_aabbs: as for
-        update_instances (default: the scene's instance_models() / instance_local_aabbs())."""
+        update_instances (default: the scene's instance_models() / instance_local_aabbs()).  refit=True
+        (hk_refit_meshes): each listed BLAS keeps its tree and gets new boxes (include/hk_refit.h) instead of a rebuild:
+        much cheaper, and a tree that walks more nodes the further the mesh is from the pose it was built for."""
         m = np.ascontiguousarray(scene.instance_models() if models is None else models, np.float32).reshape(-1, 16)
         a = np.ascontiguousarray(scene.instance_local_aabbs() if local_aabbs is None else local_aabbs,
                                  np.float32).reshape(-1, 6)
@@ -364,8 +367,9 @@ class HikariRenderer:
             u.vertex_count = len(p)
             u.positions = p.ctypes.data
             u.normals = None if n is None else n.ctypes.data
-        _check(self.ctx, self._L.hk_update_meshes(self.ctx, ups, len(mesh_ids), m.ctypes.data, a.ctypes.data, len(m),
-                                                  _stream(stream)), "hk_update_meshes")
+        name = "hk_refit_meshes" if refit else "hk_update_meshes"
+        _check(self.ctx, getattr(self._L, name)(self.ctx, ups, len(mesh_ids), m.ctypes.data, a.ctypes.data, len(m),
+                                                _stream(stream)), name)
 
     def set_mesh_skins(self, scene: Scene, mesh_ids, keep_normals=(), stream=None) -> None:
         """Register the skins of `scene.meshes[i]` for each i in `mesh_ids` (hk_set_mesh_skins): the mesh's positions and
@@ -396,12 +400,14 @@ class HikariRenderer:
             s.joint_count = int(mesh.skin.joint_count)
         _check(self.ctx, self._L.hk_set_mesh_skins(self.ctx, arr, len(mesh_ids), _stream(stream)), "hk_set_mesh_skins")
 
-    def skin_meshes(self, scene: Scene, poses: dict, models=None, local_aabbs=None, stream=None) -> None:
+    def skin_meshes(self, scene: Scene, poses: dict, models=None, local_aabbs=None, stream=None,
+                    refit: bool = False) -> None:
         """Pose skinned meshes on the GPU (hk_skin_meshes): poses = {mesh id: (joint_count, 16) column-major joint
         matrices} for meshes registered by set_mesh_skins; the GPU skins their vertices, rebuilds their primitives and
         BLAS and then everything update_instances rebuilds, with the posed meshes' boxes derived on the device.
         `scene` gives the slices (scene.mesh_index) and, by default, models and local_aabbs (instance_models() /
-        instance_local_aabbs(); the rows of a posed mesh's instances are ignored)."""
+        instance_local_aabbs(); the rows of a posed mesh's instances are ignored).  refit=True (hk_skin_meshes_refit):
+        the posed meshes' BLAS are refit, not rebuilt, as in update_meshes."""
         m = np.ascontiguousarray(scene.instance_models() if models is None else models, np.float32).reshape(-1, 16)
         a = np.ascontiguousarray(scene.instance_local_aabbs() if local_aabbs is None else local_aabbs,
                                  np.float32).reshape(-1, 6)
@@ -416,8 +422,9 @@ class HikariRenderer:
             p.mesh = _abi.hk_mesh_index(v, pr, (C.c_uint32 * 2)(n0, nc))
             p.joints = j.ctypes.data
             p.joint_count = len(j)
-        _check(self.ctx, self._L.hk_skin_meshes(self.ctx, arr, len(poses), m.ctypes.data, a.ctypes.data, len(m),
-                                                _stream(stream)), "hk_skin_meshes")
+        name = "hk_skin_meshes_refit" if refit else "hk_skin_meshes"
+        _check(self.ctx, getattr(self._L, name)(self.ctx, arr, len(poses), m.ctypes.data, a.ctypes.data, len(m),
+                                                _stream(stream)), name)
 
     def set_instances(self, scene: Scene, previous=None, materials: bool = False, stream=None, models=None,
                       local_aabbs=None) -> None:
@@ -748,17 +755,19 @@ class HikariPlugin:
         r.tone_sum(s, stream)
         self.frame_number += 1
 
-    def update_meshes(self, scene: Scene, mesh_ids, models=None, local_aabbs=None, stream=None) -> None:
+    def update_meshes(self, scene: Scene, mesh_ids, models=None, local_aabbs=None, stream=None,
+                      refit: bool = False) -> None:
         """`prepare_mesh_assets` for modified meshes of unchanged topology (HikariRenderer.update_meshes)."""
-        self.renderer.update_meshes(scene, mesh_ids, models, local_aabbs, stream)
+        self.renderer.update_meshes(scene, mesh_ids, models, local_aabbs, stream, refit=refit)
 
     def set_mesh_skins(self, scene: Scene, mesh_ids, keep_normals=(), stream=None) -> None:
         """HikariRenderer.set_mesh_skins: the `SkinnedMesh` entities' bind poses and rigs, resident on the device."""
         self.renderer.set_mesh_skins(scene, mesh_ids, keep_normals, stream)
 
-    def skin_meshes(self, scene: Scene, poses: dict, models=None, local_aabbs=None, stream=None) -> None:
+    def skin_meshes(self, scene: Scene, poses: dict, models=None, local_aabbs=None, stream=None,
+                    refit: bool = False) -> None:
         """HikariRenderer.skin_meshes: this frame's joint palettes (`SkinnedMeshJoints` x inverse bind poses)."""
-        self.renderer.skin_meshes(scene, poses, models, local_aabbs, stream)
+        self.renderer.skin_meshes(scene, poses, models, local_aabbs, stream, refit=refit)
 
     def add_meshes(self, meshes, stream=None) -> list:
         """HikariRenderer.add_meshes: mesh assets created after the scene was uploaded (AssetEvent::Created)."""

@@ -286,6 +286,21 @@ def skin_vertices(mesh: Mesh, joints, aabb: bool = False):
     return (posed, box) if aabb else posed
 
 
+def refit_nodes(primitives, nodes) -> np.ndarray:
+    """One mesh's node slice refit on the host (hks_refit_nodes, include/hk_refit.h's rule): a copy of `nodes` (the
+    slice's bytes, 32 per node, indices relative to the slice) whose entry nodes carry the boxes of `primitives` (the
+    mesh's primitives after the deformation, 48 bytes each); leaves and every index stay.  Raises HikariError when the
+    slice is not a bvh-0.7.1 flatten of 3k - 2 nodes over the k primitives."""
+    p = np.ascontiguousarray(primitives).view(np.uint8).reshape(-1)
+    n = np.ascontiguousarray(nodes).view(np.uint8).reshape(-1).copy()
+    if len(p) % 48 or len(n) % 32:
+        raise ValueError("primitives are 48 bytes each, nodes 32")
+    rc = _abi.lib().hks_refit_nodes(p.ctypes.data, len(p) // 48, n.ctypes.data, len(n) // 32)
+    if rc != 0:
+        raise _abi.HikariError(f"hks_refit_nodes refused the slice ({rc}): not a flatten of 3k - 2 nodes over k primitives")
+    return n
+
+
 @dataclass
 class StandardMaterial:
     """Bevy 0.9 `StandardMaterial` defaults; colours given as linear RGBA.  Texture fields hold
@@ -466,6 +481,26 @@ class Scene:
                 s.meshes[i] = skin_vertices(m, joints)
         s.materials, s.instances, s.textures = self.materials, self.instances, self.textures
         return s
+
+    @staticmethod
+    def refitted(desc0: _abi.hk_scene_desc, scene1: "Scene", mesh_ids) -> _abi.hk_scene_desc:
+        """The scene a refit leaves (HikariRenderer.update_meshes / skin_meshes with refit=True): every array of
+        `scene1` as built, except the asset nodes, which are those of `desc0` (the scene before the call: same meshes,
+        same topology) with the slices of `mesh_ids` refit over scene1's primitives (refit_nodes).  scene1 is built if
+        it has not been.  The returned desc keeps its own node array and scene1 alive."""
+        d1 = scene1.desc if scene1.desc is not None else scene1.build()
+        if desc0.asset_nodes.count != d1.asset_nodes.count:
+            raise ValueError("the two scenes differ in their asset node count")
+        nodes = np.frombuffer(C.string_at(desc0.asset_nodes.data, desc0.asset_nodes.count * 32), np.uint8).copy()
+        prims = np.frombuffer(C.string_at(d1.primitives.data, d1.primitives.count * 48), np.uint8)
+        for i in mesh_ids:
+            _, p0, n0, nc = scene1.mesh_index(i)
+            k = (nc + 2) // 3
+            nodes[32 * n0:32 * (n0 + nc)] = refit_nodes(prims[48 * p0:48 * (p0 + k)], nodes[32 * n0:32 * (n0 + nc)])
+        d = _abi.hk_scene_desc.from_buffer_copy(d1)
+        d.asset_nodes.data = nodes.ctypes.data
+        d._keep = (nodes, scene1)
+        return d
 
     def instance_models(self) -> np.ndarray:
         """(n, 16) float32 column-major model matrices of the instances, in upload order."""

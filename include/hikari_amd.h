@@ -496,6 +496,29 @@ typedef struct hk_skin_pose {
 int hk_skin_meshes(hk_ctx* ctx, const hk_skin_pose* poses, uint32_t n, const float* models, const float* local_aabbs,
                    uint32_t count, void* stream);
 
+/* BLAS refit: hk_update_meshes and hk_skin_meshes with the BLAS of each listed mesh REFIT, not rebuilt.
+ * A refit keeps the tree the slice holds (every entry_index and exit_index, so the node count, the leaf order and
+ * the depth) and recomputes the box of every entry node from the deformed primitives, by the rule of
+ * include/hk_refit.h: the hk_minf / hk_maxf fold of the shape boxes of the leaves stored in the node's range.  The
+ * reference has no such path (it rebuilds, mesh.rs:77-166); the rule is this library's own.  It costs a scan of the
+ * slice spread over the whole device instead of a SAH build by one workgroup per mesh.
+ * QUALITY DEGRADES WITH THE DEFORMATION: the tree was chosen for the vertices it was built over.  Boxes stay tight around
+ * their leaves, but leaves that moved apart make sibling boxes overlap, and a tree refit far from the pose it was built
+ * for walks more nodes per ray.  It stays correct: every ray finds the hits a rebuilt tree finds, up to the order in
+ * which equal hits are met.  The caller decides when that matters and then calls hk_update_meshes / hk_skin_meshes on
+ * the same mesh, which rebuild from the current vertices and give the host builder's tree again; the library has no
+ * policy of its own and no quality query.
+ * Arguments, refusals, messages (with the function's own name in front) and states are those of hk_update_meshes and
+ * hk_skin_meshes; a refusal leaves the context unchanged; mesh_count == 0 / n == 0 is hk_update_instances.  Afterwards
+ * all nine arrays are what hks_build + hk_scene_upload give for the deformed scene, except that each listed mesh's
+ * slice of the asset nodes is the slice before the call passed through hikari_scene.h hks_refit_nodes with the mesh's
+ * new primitives (leaves carry their triangle's box on the device, as always).  The G-buffer stack bound does not move.
+ * Waits for the stream once. */
+int hk_refit_meshes(hk_ctx* ctx, const hk_mesh_update* meshes, uint32_t mesh_count, const float* models,
+                    const float* local_aabbs, uint32_t count, void* stream);
+int hk_skin_meshes_refit(hk_ctx* ctx, const hk_skin_pose* poses, uint32_t n, const float* models,
+                         const float* local_aabbs, uint32_t count, void* stream);
+
 /* the element capacities beside hk_scene_counts' counts, hk_scene_desc order: what each array holds before a call
  * has to allocate (hk_set_instances: 3, 4, 5, 7, 8; hk_add_meshes: 0, 1, 2; array 6 never grows).  HK_ERR_STATE
  * without a scene. */

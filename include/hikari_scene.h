@@ -89,6 +89,17 @@ int hks_skin_vertices(const float* positions, const float* normals, const uint16
                       const float* joint_weights, uint32_t vertex_count, const float* joints, uint32_t joint_count,
                       float* out_positions, float* out_normals, float out_aabb[6]);
 
+/* A BLAS refit on the host, by the rule of include/hk_refit.h: the host side of hk_refit_meshes' and
+ * hk_skin_meshes_refit's contract, and what a caller without a device uses.  nodes: one mesh's slice of the asset nodes,
+ * a bvh-0.7.1 flatten of node_count = 3 x primitive_count - 2 nodes with slice-relative indices; primitives: the mesh's
+ * primitive_count primitives after the deformation.  Every entry node's box becomes the hk_minf / hk_maxf fold of the
+ * shape boxes of the leaves in its range; entry_index, exit_index and every byte of a leaf stay.  One O(n) pass.
+ * Returns 0, or HK_ERR_INVALID with `nodes` untouched for a null pointer, node_count != 3 x primitive_count - 2, or a
+ * slice that is not a well-formed flatten: a leaf whose exit is not i + 1 or whose payload is not below primitive_count,
+ * a primitive in two leaves or in none, an entry node whose entry is not i + 1 or whose exit is not in (i + 1,
+ * node_count], or whose range (i, exit) is not tiled exactly by one leaf or by two entry nodes' ranges. */
+int hks_refit_nodes(const hk_primitive* primitives, uint32_t primitive_count, hk_node* nodes, uint32_t node_count);
+
 #ifdef __cplusplus
 }
 #endif
