@@ -1,6 +1,6 @@
 // hk_dynamic.hip — dynamic instances, deforming meshes, changed instance sets
-// (DESIGN §0 f8), appended meshes, new mesh lists, skinned meshes and the
-// BLAS refit on the device.
+// (DESIGN §0 f8), appended meshes, new mesh lists, skinned meshes, the
+// BLAS refit and the instance refit on the device.
 //
 // The reference re-runs `prepare_instances` on the CPU whenever a transform changes
 // (instance.rs:284-437: instance records with world AABBs and inverse-transpose models, the
@@ -1142,11 +1142,109 @@ __global__ __launch_bounds__(256) void k_backfill_nodes(const hk_node* tlas, uin
     if (i < n_lbvh && lbvh[i].entry_index >= HK_BVH_LEAF_FLAG) em[lbvh[i].entry_index - HK_BVH_LEAF_FLAG].node_index = i;
 }
 
-// what follows the instance records and their boxes: the TLAS, the emitters' areas, alias tables, records and light
-// BVH, and the leaf node indices
-static void launch_rebuild(const DynamicArgs& D, hipStream_t st)
+// ---- instance refit (include/hk_refit.h: the rule over given shape boxes, this project's own; the host
+// side is hk_scene.cpp hks_refit_boxes over the same header).  The TLAS and the light BVH keep their topology, so every
+// node_index in the instance and emissive records stays and nothing is backfilled; every entry node's box becomes the
+// hk_minf / hk_maxf fold of the shape boxes of the leaves stored in its range (i, exit).  One launch sequence serves
+// both trees: a table of at most two RefitTree records (node array, records, count), its nodes laid end to end.  The
+// tiers are k_refit_small's and k_refit_large's: a thread per node, ranges up to REFIT_SMALL scanned in registers,
+// larger ones listed (one atomicAdd on a counter the stream zeroed) for a workgroup each in the next launch.  Every
+// box is folded from leaves alone: nothing passes between workgroups inside a launch, no fence, no spin wait; the
+// stream orders the launches.
+// Where the shape boxes come from: the RECORDS.  S[t] of the TLAS is the min / max k_update_instances stored in
+// instance t, S[e] of the light BVH is position -+ radius of the emissive record k_update_emissives stored, the very
+// f32 operations that kernel puts into boxes[e].  So the refit never reads the boxes scratch, whose head
+// k_update_emissives overwrites with the emitters' boxes after k_update_instances filled it with the instances' (the
+// rebuild orders the two by building the TLAS in between; the refit has nothing to order), and never a leaf's own box:
+// the device TLAS carries leaf boxes from launch_fill_leaves, stale until refresh_tlas_derivatives refills them
+// after these launches.  Only min / max of entry nodes are written; the words the scans read (entry_index,
+// exit_index, the records) are written by nobody here.
+// Hostile sizes (hk_scene_upload takes any tree of 3n - 2 nodes): an exit past the tree is clamped, a payload past
+// the records is skipped, the list takes no more entries than it has room for.  Never taken on a well-formed tree.
+HKD void refit_tree_scan(const RefitTree& t, uint32_t j, float* box)
 {
-    const uint32_t n = D.n_instances;
+    const uint32_t entry = t.nodes[j].entry_index;
+    if (!hk_refit_is_leaf(entry)) return;
+    const uint32_t s = hk_refit_leaf_primitive(entry);
+    if (s >= t.shapes) return;  // (a built tree's payloads are its own shapes; never taken)
+    float b[6];
+    if (t.emitters) hk_refit_emitter_box((const hk_emissive*)t.records + s, b);
+    else hk_refit_instance_box((const hk_instance*)t.records + s, b);
+    hk_refit_join(box, b, b + 3);
+}
+// node g of the trees laid end to end: its tree (*i: its index there); tree 0 has 3 x shapes - 2 nodes
+HKD RefitTree refit_tree_of(const RefitTrees& T, uint32_t g, uint32_t* i)
+{
+    const uint32_t n0 = 3u * T.tree[0].shapes - 2u;
+    const uint32_t k = T.n_trees > 1u && g >= n0 ? 1u : 0u;
+    *i = g - (k ? n0 : 0u);
+    return k ? T.tree[1] : T.tree[0];
+}
+__global__ __launch_bounds__(256) void k_refit_trees_small(RefitTrees T, uint32_t* large, uint32_t large_room,
+                                                           uint32_t* n_large)
+{
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= T.n_nodes) return;
+    uint32_t i;
+    const RefitTree t = refit_tree_of(T, g, &i);
+    if (t.shapes == 0u) return;  // (no table entry without shapes; never taken)
+    const uint32_t count = 3u * t.shapes - 2u;
+    if (i >= count) return;
+    if (hk_refit_is_leaf(t.nodes[i].entry_index)) return;
+    const uint32_t exit = t.nodes[i].exit_index, e = exit < count ? exit : count;
+    if (e > i && e - i > REFIT_SMALL) {
+        const uint32_t at = atomicAdd(n_large, 1u);
+        if (at < large_room) large[at] = g;
+        return;
+    }
+    float box[6];
+    hk_refit_empty(box);
+    for (uint32_t j = i + 1u; j < e; ++j) refit_tree_scan(t, j, box);
+    for (int c = 0; c < 3; ++c) {
+        t.nodes[i].min[c] = box[c];
+        t.nodes[i].max[c] = box[3 + c];
+    }
+}
+__global__ __launch_bounds__(256) void k_refit_trees_large(RefitTrees T, const uint32_t* large, uint32_t large_room,
+                                                           const uint32_t* n_large)
+{
+    __shared__ CoopShared sh;
+    const uint32_t listed = *n_large < large_room ? *n_large : large_room;
+    const int op[6] = {0, 0, 0, 1, 1, 1};
+    for (uint32_t w = blockIdx.x; w < listed; w += gridDim.x) {  // (block-uniform)
+        const uint32_t g = large[w];
+        if (g >= T.n_nodes) continue;  // (k_refit_trees_small listed a node of the trees; never taken)
+        uint32_t i;
+        const RefitTree t = refit_tree_of(T, g, &i);
+        const uint32_t count = 3u * t.shapes - 2u;
+        if (t.shapes == 0u || i >= count) continue;  // (likewise)
+        const uint32_t exit = t.nodes[i].exit_index, e = exit < count ? exit : count;
+        float box[6];
+        hk_refit_empty(box);
+        for (uint32_t j = i + 1u + threadIdx.x; j < e; j += 256u) refit_tree_scan(t, j, box);
+        block_reduce<6>(box, op, sh);
+        if (threadIdx.x < 3u) t.nodes[i].min[threadIdx.x] = box[threadIdx.x];
+        else if (threadIdx.x < 6u) t.nodes[i].max[threadIdx.x - 3u] = box[threadIdx.x];
+    }
+}
+
+// the table of a refit: the TLAS over the instance records and, where there are emitters, the light BVH over theirs
+static RefitTrees refit_trees(const DynamicArgs& D)
+{
+    RefitTrees T;
+    T.tree[0] = RefitTree{D.tlas, D.instances, D.n_instances, 0u};
+    T.tree[1] = RefitTree{D.lbvh, D.emissives, D.n_emissives, 1u};
+    T.n_trees = D.n_emissives ? 2u : 1u;
+    T.n_nodes = 3u * D.n_instances - 2u + (D.n_emissives ? 3u * D.n_emissives - 2u : 0u);
+    return T;
+}
+
+// One step of what follows the uploads (hk_launch.h DynamicStep).  The list of large nodes of a refit lies in the
+// builds' segments, which a refit leaves unused (2 x max(n, m) x 12 B: more words than both trees have nodes); its
+// counter is flags[2], zeroed with the flags and otherwise a new instance set's.
+void launch_dynamic_step(const DynamicArgs& D, DynamicStep step, hipStream_t st)
+{
+    const uint32_t n = D.n_instances, m = D.n_emissives;
     auto build = [&](uint32_t count, hk_node* out, uint32_t* levels) {
         if (count <= BVH_LDS_SHAPES)
             hipLaunchKernelGGL(k_build_bvh<true>, dim3(1), dim3(256), 0, st, (const BBox*)D.boxes, count, D.buckets, out,
@@ -1155,24 +1253,62 @@ static void launch_rebuild(const DynamicArgs& D, hipStream_t st)
             hipLaunchKernelGGL(k_build_bvh<false>, dim3(1), dim3(256), 0, st, (const BBox*)D.boxes, count, D.buckets,
                                out, D.idx, (Segment*)D.segments, levels);
     };
-    build(n, D.tlas, D.flags + 1);
-    if (D.n_emissives) {
-        hipLaunchKernelGGL(k_emissive_areas, dim3((D.n_alias + 255u) / 256u), dim3(256), 0, st, D.emissives,
-                           D.n_emissives, D.instances, D.primitives, D.n_alias, D.areas);
-        hipLaunchKernelGGL(k_update_emissives, dim3(D.n_emissives), dim3(64), 0, st, D.emissives, D.n_emissives,
-                           D.instances, D.materials, D.alias, D.areas, (AliasWork*)D.alias_work, (BBox*)D.boxes);
-        build(D.n_emissives, D.lbvh, nullptr);
+    const uint32_t large_room = 6u * (n > m ? n : m);
+    switch (step) {
+    case DYN_RECORDS:
+        hipLaunchKernelGGL(k_update_instances, dim3((n + 255u) / 256u), dim3(256), 0, st, D.instances, n, D.models,
+                           D.local_aabbs, (BBox*)D.boxes, D.flags);
+        break;
+    case DYN_TLAS_BUILD:
+        build(n, D.tlas, D.flags + 1);
+        break;
+    case DYN_EMISSIVE_AREAS:
+        if (m)
+            hipLaunchKernelGGL(k_emissive_areas, dim3((D.n_alias + 255u) / 256u), dim3(256), 0, st, D.emissives, m,
+                               D.instances, D.primitives, D.n_alias, D.areas);
+        break;
+    case DYN_EMISSIVES:
+        if (m)
+            hipLaunchKernelGGL(k_update_emissives, dim3(m), dim3(64), 0, st, D.emissives, m, D.instances, D.materials,
+                               D.alias, D.areas, (AliasWork*)D.alias_work, (BBox*)D.boxes);
+        break;
+    case DYN_LBVH_BUILD:
+        if (m) build(m, D.lbvh, nullptr);
+        break;
+    case DYN_BACKFILL: {
+        const uint32_t k = 3u * n - 2u > 3u * m ? 3u * n - 2u : 3u * m;
+        hipLaunchKernelGGL(k_backfill_nodes, dim3((k + 255u) / 256u), dim3(256), 0, st, D.tlas, 3u * n - 2u, D.instances,
+                           D.lbvh, m ? 3u * m - 2u : 0u, D.emissives);
+        break;
     }
-    const uint32_t m = 3u * n - 2u > 3u * D.n_emissives ? 3u * n - 2u : 3u * D.n_emissives;
-    hipLaunchKernelGGL(k_backfill_nodes, dim3((m + 255u) / 256u), dim3(256), 0, st, D.tlas, 3u * n - 2u, D.instances,
-                       D.lbvh, D.n_emissives ? 3u * D.n_emissives - 2u : 0u, D.emissives);
+    case DYN_REFIT_SMALL: {
+        const RefitTrees T = refit_trees(D);
+        hipLaunchKernelGGL(k_refit_trees_small, dim3((T.n_nodes + 255u) / 256u), dim3(256), 0, st, T,
+                           (uint32_t*)D.segments, large_room, D.flags + 2);
+        break;
+    }
+    case DYN_REFIT_LARGE: {
+        // (nothing where neither tree can hold a large node: the bound of a BLAS slice holds for any such flatten)
+        const uint32_t bound = mesh_refit_large_bound(n) + mesh_refit_large_bound(m);
+        if (bound == 0u) break;
+        hipLaunchKernelGGL(k_refit_trees_large, dim3(bound < REFIT_LARGE_GRID ? bound : REFIT_LARGE_GRID), dim3(256), 0,
+                           st, refit_trees(D), (const uint32_t*)D.segments, large_room, (const uint32_t*)(D.flags + 2));
+        break;
+    }
+    }
+}
+
+// what follows the instance records and their boxes: the TLAS, the emitters' areas, alias tables, records and light
+// BVH, and the leaf node indices
+static void launch_rebuild(const DynamicArgs& D, hipStream_t st)
+{
+    for (DynamicStep s : {DYN_TLAS_BUILD, DYN_EMISSIVE_AREAS, DYN_EMISSIVES, DYN_LBVH_BUILD, DYN_BACKFILL})
+        launch_dynamic_step(D, s, st);
 }
 
 void launch_dynamic_update(const DynamicArgs& D, hipStream_t st)
 {
-    const uint32_t n = D.n_instances;
-    hipLaunchKernelGGL(k_update_instances, dim3((n + 255u) / 256u), dim3(256), 0, st, D.instances, n, D.models,
-                       D.local_aabbs, (BBox*)D.boxes, D.flags);
+    launch_dynamic_step(D, DYN_RECORDS, st);
     launch_rebuild(D, st);
 }
 

@@ -157,11 +157,33 @@ struct DynamicArgs {
     void* alias_work;          // 2 x alias entries x 8 B
     void* boxes;               // max(n, m) x 24 B
     uint32_t* idx;             // 2 x max(n, m)
-    void* segments;            // 2 x max(n, m) x 12 B
+    void* segments;            // 2 x max(n, m) x 12 B (a refit builds nothing: its list of large nodes lies here)
     uint32_t* flags;           // [0] singular transform, [1] TLAS split levels (G-buffer stack bound),
-                               // [2] emitters, [3] alias entries of a new instance set (launch_set_instances)
+                               // [2] emitters, [3] alias entries of a new instance set (launch_set_instances);
+                               // [2] of a refit: the listed large nodes (DYN_REFIT_SMALL counts them)
 };
 void launch_dynamic_update(const DynamicArgs& D, hipStream_t st);
+// launch_dynamic_update one launch at a time, for a caller that times each: RECORDS, TLAS_BUILD, EMISSIVE_AREAS,
+// EMISSIVES, LBVH_BUILD, BACKFILL in this order are launch_dynamic_update.  The instance refit (hk_refit_instances;
+// DESIGN §0 f13) is RECORDS, EMISSIVE_AREAS, EMISSIVES, REFIT_SMALL, REFIT_LARGE: both trees keep their topology and
+// get the boxes of include/hk_refit.h's rule from the records before them, no build and no backfill.  A step with
+// nothing to do (no emitters; no tree that can hold a large node) launches nothing.
+enum DynamicStep {
+    DYN_RECORDS, DYN_TLAS_BUILD, DYN_EMISSIVE_AREAS, DYN_EMISSIVES, DYN_LBVH_BUILD, DYN_BACKFILL, DYN_REFIT_SMALL,
+    DYN_REFIT_LARGE
+};
+void launch_dynamic_step(const DynamicArgs& D, DynamicStep step, hipStream_t st);
+// One tree of the instance refit: a bvh-0.7.1 flatten of 3 x shapes - 2 nodes over the records its leaves name
+// (emitters 0: hk_instance, 1: hk_emissive).  RefitTrees: the kernels' table, by value; n_nodes over all trees.
+struct RefitTree {
+    hk_node* nodes;
+    const void* records;
+    uint32_t shapes, emitters;
+};
+struct RefitTrees {
+    RefitTree tree[2];
+    uint32_t n_trees, n_nodes;
+};
 
 // A new instance set (hk_dynamic.hip): one record per instance, the layout of hk_instance_desc.
 struct InstanceDesc {

@@ -377,6 +377,7 @@ struct hk_ctx {
     bool heavy = false;           // the last hk_render_frame had spatial reuse or followed a denoised frame (pipeline_size)
     int dn_calls = 0;             // hk_denoise calls since the last hk_render_frame
     uint32_t gb_blas_depth = 0;   // BLAS part of it (the TLAS part changes with hk_update_instances)
+    uint32_t gb_tlas_depth = 0;   // TLAS part of it: set at upload and by every TLAS build; a refit keeps the tree
     void* dyn_scratch = nullptr;  // hk_update_instances scratch (sized at upload)
     size_t dyn_bytes = 0;
     // hk_update_meshes: the instanced meshes as upload recorded them (slice, vertices their primitives index, BLAS
@@ -1491,6 +1492,7 @@ int hk_scene_upload(hk_ctx* c, const hk_scene_desc* d)
         }
     }
     (void)scene_stack_need(d, &c->gb_stack_need, &c->gb_blas_depth);  // (node ranges checked above)
+    c->gb_tlas_depth = c->gb_stack_need - c->gb_blas_depth;
     release(c->dyn_scratch);
     c->dyn_bytes = 0;
     release(c->mesh_scratch);
@@ -1836,9 +1838,13 @@ static int carve(hk_ctx* c, void** scratch, size_t* have, const size_t* bytes, i
 // (null: the current set with new models).  mesh_work (hk_skin_meshes): what the caller enqueues on `st` between the
 // uploads and the instance kernels, given the device copy of local_aabbs, whose rows it may overwrite.  ml with no
 // slices (a refit): meshes changed and no depth did.
+// refit (hk_refit_instances and the _all calls; never with a set, whose topology is another): the TLAS and
+// the light BVH keep their trees and get new boxes by include/hk_refit.h's rule, in place of the two builds and the
+// backfill.  No TLAS is built, so nobody writes flags[1]: the TLAS depth is the context's, which a build alone moves.
+// Everything else, the one wait included, is the rebuilding call's.
 static int rebuild_instances(hk_ctx* c, const float* models, const float* local_aabbs, uint32_t count, hipStream_t st,
                              const MeshLevels* ml, const SetChange* set = nullptr,
-                             const std::function<void(float*)>* mesh_work = nullptr)
+                             const std::function<void(float*)>* mesh_work = nullptr, bool refit = false)
 {
     HK_TRY(c->sch.gb_join(st));
     HK_TRY(c->sch.gb_serialize(false));
@@ -1915,14 +1921,26 @@ static int rebuild_instances(hk_ctx* c, const float* models, const float* local_
     S.n_prev = n_before;
     S.new_prev = (float*)part[10];
     S.emitter = (uint2*)part[11];
-    timed(c, set ? "set_instances" : "update_instances", st, [&] {
+    // (the spans inside the call's own: one per launch, the same launches in the same order as launch_dynamic_update)
+    auto step = [&](const char* name, DynamicStep s) { timed(c, name, st, [&] { launch_dynamic_step(D, s, st); }); };
+    timed(c, set ? "set_instances" : refit ? "refit_instances" : "update_instances", st, [&] {
         if (set) {
             launch_set_instances(D, S, st);
             (void)hipMemcpyAsync(c->prev_models, S.new_prev, (size_t)n * 64, hipMemcpyDeviceToDevice, st);
         } else {
-            launch_dynamic_update(D, st);
+            step("instances.records", DYN_RECORDS);
+            if (!refit) step("instances.tlas_build", DYN_TLAS_BUILD);
+            step("instances.emissive_areas", DYN_EMISSIVE_AREAS);
+            step("instances.emissives", DYN_EMISSIVES);
+            if (refit) {
+                step("instances.refit_small", DYN_REFIT_SMALL);
+                step("instances.refit_large", DYN_REFIT_LARGE);
+            } else {
+                step("instances.lbvh_build", DYN_LBVH_BUILD);
+                step("instances.backfill", DYN_BACKFILL);
+            }
         }
-        refresh_tlas_derivatives(c, st);
+        timed(c, "instances.derivatives", st, [&] { refresh_tlas_derivatives(c, st); });
     });
     HK_HIP(c, hipGetLastError());
     uint32_t flags[4] = {0, 0, 0, 0};
@@ -1935,13 +1953,14 @@ static int rebuild_instances(hk_ctx* c, const float* models, const float* local_
         for (size_t k = 0; k < levels.size(); ++k) c->meshes[ml->slice[k]].depth = levels[k];
         c->gb_blas_depth = used_depth(c->meshes);
     }
-    if (ml || set) c->gb_stack_need = flags[1] + c->gb_blas_depth;
+    if (!refit) c->gb_tlas_depth = flags[1];
+    if (ml || set) c->gb_stack_need = c->gb_tlas_depth + c->gb_blas_depth;
     if (set && (flags[2] != m || flags[3] != n_alias))
         return fail(c, HK_ERR_HIP, "hk_set_instances: the device counted " + std::to_string(flags[2]) + " emitters and " +
                                        std::to_string(flags[3]) + " alias entries, the host " + std::to_string(m) +
                                        " and " + std::to_string(n_alias));
     if (flags[0]) return fail(c, HK_ERR_INVALID, "singular instance transform");
-    c->gb_stack_need = flags[1] + c->gb_blas_depth;
+    c->gb_stack_need = c->gb_tlas_depth + c->gb_blas_depth;
     c->models_dirty = true;  // the next G-buffer reads the models before this update as the previous ones
     // one kernel derives every record's inverse_transpose_model from its model with the same code: equal model bits
     // give equal record bits
@@ -1975,6 +1994,13 @@ int hk_update_instances(hk_ctx* c, const float* models, const float* local_aabbs
     HK_TRY(update_args_ok(c, count, "hk_update_instances"));
     (void)hipSetDevice(c->device);
     return rebuild_instances(c, models, local_aabbs, count, pick(c, stream), nullptr);
+}
+int hk_refit_instances(hk_ctx* c, const float* models, const float* local_aabbs, uint32_t count, void* stream)
+{
+    if (!c || !models || !local_aabbs) return HK_ERR_INVALID;
+    HK_TRY(update_args_ok(c, count, "hk_refit_instances"));
+    (void)hipSetDevice(c->device);
+    return rebuild_instances(c, models, local_aabbs, count, pick(c, stream), nullptr, nullptr, nullptr, true);
 }
 
 // Meshes on their way to a build (hk_update_meshes, hk_add_meshes and the new entries of hk_set_meshes): the tables in
@@ -2117,9 +2143,10 @@ static void enqueue_mesh_refit(hk_ctx* c, const MeshUpdateArgs& M, hipStream_t s
     timed(c, "refit_derivatives", st, [&] { refresh_blas_derivatives(c, st, c->count[2]); });
 }
 
-// hk_update_meshes (fn = "hk_update_meshes") and hk_refit_meshes: one body, the BLAS step apart
-static int update_meshes(hk_ctx* c, const std::string& fn, bool refit, const hk_mesh_update* meshes, uint32_t mesh_count,
-                         const float* models, const float* local_aabbs, uint32_t count, void* stream)
+// hk_update_meshes (fn = "hk_update_meshes"), hk_refit_meshes and hk_refit_meshes_all: one body, the BLAS step apart
+// (refit) and the instance trees kept or not (refit_trees)
+static int update_meshes(hk_ctx* c, const std::string& fn, bool refit, bool refit_trees, const hk_mesh_update* meshes,
+                         uint32_t mesh_count, const float* models, const float* local_aabbs, uint32_t count, void* stream)
 {
     if (!c) return HK_ERR_INVALID;
     if (!meshes || !models || !local_aabbs) return fail(c, HK_ERR_INVALID, fn + ": null pointer");
@@ -2154,7 +2181,8 @@ static int update_meshes(hk_ctx* c, const std::string& fn, bool refit, const hk_
     }
     (void)hipSetDevice(c->device);
     hipStream_t st = pick(c, stream);
-    if (mesh_count == 0) return rebuild_instances(c, models, local_aabbs, count, st, nullptr);
+    if (mesh_count == 0)
+        return rebuild_instances(c, models, local_aabbs, count, st, nullptr, nullptr, nullptr, refit_trees);
     HK_TRY(c->sch.gb_join(st));
     HK_TRY(c->sch.gb_serialize(false));
     MeshStaging stage;
@@ -2171,17 +2199,22 @@ static int update_meshes(hk_ctx* c, const std::string& fn, bool refit, const hk_
     HK_HIP(c, hipGetLastError());
     ml.device = A.M.levels;
     if (refit) ml.slice.clear();  // the topology stays, and so does every depth: no levels to read back
-    return rebuild_instances(c, models, local_aabbs, count, st, &ml);
+    return rebuild_instances(c, models, local_aabbs, count, st, &ml, nullptr, nullptr, refit_trees);
 }
 int hk_update_meshes(hk_ctx* c, const hk_mesh_update* meshes, uint32_t mesh_count, const float* models,
                      const float* local_aabbs, uint32_t count, void* stream)
 {
-    return update_meshes(c, "hk_update_meshes", false, meshes, mesh_count, models, local_aabbs, count, stream);
+    return update_meshes(c, "hk_update_meshes", false, false, meshes, mesh_count, models, local_aabbs, count, stream);
 }
 int hk_refit_meshes(hk_ctx* c, const hk_mesh_update* meshes, uint32_t mesh_count, const float* models,
                     const float* local_aabbs, uint32_t count, void* stream)
 {
-    return update_meshes(c, "hk_refit_meshes", true, meshes, mesh_count, models, local_aabbs, count, stream);
+    return update_meshes(c, "hk_refit_meshes", true, false, meshes, mesh_count, models, local_aabbs, count, stream);
+}
+int hk_refit_meshes_all(hk_ctx* c, const hk_mesh_update* meshes, uint32_t mesh_count, const float* models,
+                        const float* local_aabbs, uint32_t count, void* stream)
+{
+    return update_meshes(c, "hk_refit_meshes_all", true, true, meshes, mesh_count, models, local_aabbs, count, stream);
 }
 
 // The four resident skin streams in one block at `cap` vertices each (hk_ctx::skin_block), every stream 256-aligned
@@ -2266,9 +2299,10 @@ int hk_set_mesh_skins(hk_ctx* c, const hk_mesh_skin* skins, uint32_t n, void* st
     return HK_OK;
 }
 
-// hk_skin_meshes (fn = "hk_skin_meshes") and hk_skin_meshes_refit: one body, the BLAS step apart
-static int skin_meshes(hk_ctx* c, const std::string& fn, bool refit, const hk_skin_pose* poses, uint32_t n,
-                       const float* models, const float* local_aabbs, uint32_t count, void* stream)
+// hk_skin_meshes (fn = "hk_skin_meshes"), hk_skin_meshes_refit and hk_skin_meshes_refit_all: one body, the BLAS step
+// apart (refit) and the instance trees kept or not (refit_trees)
+static int skin_meshes(hk_ctx* c, const std::string& fn, bool refit, bool refit_trees, const hk_skin_pose* poses,
+                       uint32_t n, const float* models, const float* local_aabbs, uint32_t count, void* stream)
 {
     if (!c) return HK_ERR_INVALID;
     if (!models || !local_aabbs || (n && !poses)) return fail(c, HK_ERR_INVALID, fn + ": null pointer");
@@ -2315,7 +2349,7 @@ static int skin_meshes(hk_ctx* c, const std::string& fn, bool refit, const hk_sk
     }
     (void)hipSetDevice(c->device);
     hipStream_t st = pick(c, stream);
-    if (n == 0) return rebuild_instances(c, models, local_aabbs, count, st, nullptr);
+    if (n == 0) return rebuild_instances(c, models, local_aabbs, count, st, nullptr, nullptr, nullptr, refit_trees);
     HK_TRY(c->sch.gb_join(st));
     HK_TRY(c->sch.gb_serialize(false));
     // the caller's part of the staging: the palettes one after another, then the SkinSource table
@@ -2363,17 +2397,22 @@ static int skin_meshes(hk_ctx* c, const std::string& fn, bool refit, const hk_sk
     };
     ml.device = A.M.levels;
     if (refit) ml.slice.clear();  // the topology stays, and so does every depth: no levels to read back
-    return rebuild_instances(c, models, local_aabbs, count, st, &ml, nullptr, &work);
+    return rebuild_instances(c, models, local_aabbs, count, st, &ml, nullptr, &work, refit_trees);
 }
 int hk_skin_meshes(hk_ctx* c, const hk_skin_pose* poses, uint32_t n, const float* models, const float* local_aabbs,
                    uint32_t count, void* stream)
 {
-    return skin_meshes(c, "hk_skin_meshes", false, poses, n, models, local_aabbs, count, stream);
+    return skin_meshes(c, "hk_skin_meshes", false, false, poses, n, models, local_aabbs, count, stream);
 }
 int hk_skin_meshes_refit(hk_ctx* c, const hk_skin_pose* poses, uint32_t n, const float* models, const float* local_aabbs,
                          uint32_t count, void* stream)
 {
-    return skin_meshes(c, "hk_skin_meshes_refit", true, poses, n, models, local_aabbs, count, stream);
+    return skin_meshes(c, "hk_skin_meshes_refit", true, false, poses, n, models, local_aabbs, count, stream);
+}
+int hk_skin_meshes_refit_all(hk_ctx* c, const hk_skin_pose* poses, uint32_t n, const float* models,
+                             const float* local_aabbs, uint32_t count, void* stream)
+{
+    return skin_meshes(c, "hk_skin_meshes_refit_all", true, true, poses, n, models, local_aabbs, count, stream);
 }
 
 // the checks hk_set_instances and hk_set_meshes share before the set is planned: the scene's BVHs can be rebuilt, and

@@ -704,24 +704,26 @@ int hks_skin_vertices(const float* positions, const float* normals, const uint16
     return HK_OK;
 }
 
-// A BLAS refit by include/hk_refit.h's rule.  The slice is checked as a bvh-0.7.1 flatten before the first store: every
-// entry node's range (i, exit) is a leaf, or two entry nodes whose ranges tile it, so by induction over the range
-// lengths the nodes form one tree over [0, node_count), and each primitive is some leaf's payload once.  The flatten
-// is pre-order, so one pass down the indices finds the boxes an entry node joins already refit.
-int hks_refit_nodes(const hk_primitive* primitives, uint32_t primitive_count, hk_node* nodes, uint32_t node_count)
+// A refit by include/hk_refit.h's rule, over the shape boxes shape(t, s) gives (s: min xyz, max xyz).  The flatten is
+// checked as bvh-0.7.1's before the first store: every entry node's range (i, exit) is a leaf, or two entry nodes whose
+// ranges tile it, so by induction over the range lengths the nodes form one tree over [0, node_count), and each shape is
+// some leaf's payload once.  The flatten is pre-order, so one pass down the indices finds the boxes an entry node joins
+// already refit.
+extern "C++" {
+template <class Shape>
+static int refit_flat(uint32_t shape_count, hk_node* nodes, uint32_t node_count, Shape shape)
 {
-    if (!primitives || !nodes || primitive_count == 0) return HK_ERR_INVALID;
-    if ((uint64_t)node_count != 3u * (uint64_t)primitive_count - 2u) return HK_ERR_INVALID;
+    if ((uint64_t)node_count != 3u * (uint64_t)shape_count - 2u) return HK_ERR_INVALID;
     const uint32_t n = node_count;
     auto leaf = [&](uint32_t i) { return hk_refit_is_leaf(nodes[i].entry_index) != 0; };
     // an entry node at i whose range ends at `end`
     auto entry_to = [&](uint32_t i, uint32_t end) { return i < n && !leaf(i) && nodes[i].exit_index == end; };
-    std::vector<bool> seen(primitive_count, false);
+    std::vector<bool> seen(shape_count, false);
     for (uint32_t i = 0; i < n; ++i) {
         const hk_node& nd = nodes[i];
         if (leaf(i)) {
             const uint32_t t = hk_refit_leaf_primitive(nd.entry_index);
-            if (nd.exit_index != i + 1u || t >= primitive_count || seen[t]) return HK_ERR_INVALID;
+            if (nd.exit_index != i + 1u || t >= shape_count || seen[t]) return HK_ERR_INVALID;
             seen[t] = true;
             continue;
         }
@@ -735,7 +737,7 @@ int hks_refit_nodes(const hk_primitive* primitives, uint32_t primitive_count, hk
         }
     }
     // the root: a lone leaf, or the two entry nodes of the root's children tiling the slice
-    if (primitive_count == 1u ? !leaf(0) : (leaf(0) || !entry_to(nodes[0].exit_index, n))) return HK_ERR_INVALID;
+    if (shape_count == 1u ? !leaf(0) : (leaf(0) || !entry_to(nodes[0].exit_index, n))) return HK_ERR_INVALID;
     for (uint32_t i = n; i-- > 0;) {
         hk_node& nd = nodes[i];
         if (leaf(i)) continue;
@@ -743,7 +745,7 @@ int hks_refit_nodes(const hk_primitive* primitives, uint32_t primitive_count, hk
         hk_refit_empty(box);
         if (leaf(i + 1u)) {
             float s[6];
-            hk_refit_shape(primitives + hk_refit_leaf_primitive(nodes[i + 1u].entry_index), s);
+            shape(hk_refit_leaf_primitive(nodes[i + 1u].entry_index), s);
             hk_refit_join(box, s, s + 3);
         } else {
             const hk_node &a = nodes[i + 1u], &b = nodes[a.exit_index];
@@ -756,6 +758,24 @@ int hks_refit_nodes(const hk_primitive* primitives, uint32_t primitive_count, hk
         }
     }
     return HK_OK;
+}
+}  // extern "C++"
+
+// A BLAS refit: the shape boxes folded from the mesh's primitives
+int hks_refit_nodes(const hk_primitive* primitives, uint32_t primitive_count, hk_node* nodes, uint32_t node_count)
+{
+    if (!primitives || !nodes || primitive_count == 0) return HK_ERR_INVALID;
+    return refit_flat(primitive_count, nodes, node_count,
+                      [&](uint32_t t, float* s) { hk_refit_shape(primitives + t, s); });
+}
+
+// A refit over given shape boxes (the TLAS over the instances' boxes, the light BVH over the emitters')
+int hks_refit_boxes(const float* boxes, uint32_t count, hk_node* nodes, uint32_t node_count)
+{
+    if (!boxes || !nodes || count == 0) return HK_ERR_INVALID;
+    return refit_flat(count, nodes, node_count, [&](uint32_t t, float* s) {
+        for (int k = 0; k < 6; ++k) s[k] = boxes[6u * (size_t)t + k];
+    });
 }
 
 }  // extern "C"

@@ -254,6 +254,9 @@ def lib() -> C.CDLL:
         "hk_skin_meshes": (i32, [vp, C.POINTER(hk_skin_pose), u32, vp, vp, u32, vp]),
         "hk_refit_meshes": (i32, [vp, C.POINTER(hk_mesh_update), u32, vp, vp, u32, vp]),
         "hk_skin_meshes_refit": (i32, [vp, C.POINTER(hk_skin_pose), u32, vp, vp, u32, vp]),
+        "hk_refit_instances": (i32, [vp, vp, vp, u32, vp]),
+        "hk_refit_meshes_all": (i32, [vp, C.POINTER(hk_mesh_update), u32, vp, vp, u32, vp]),
+        "hk_skin_meshes_refit_all": (i32, [vp, C.POINTER(hk_skin_pose), u32, vp, vp, u32, vp]),
         "hk_scene_shared_transform": (i32, [vp, C.POINTER(i32)]),
         "hk_instance_set_counts": (i32, [C.POINTER(hk_scene_desc), C.POINTER(hk_instance_desc), u32, vp, C.POINTER(u32)]),
         "hk_read_scene_array": (i32, [vp, i32, vp, C.c_size_t]),
@@ -295,6 +298,7 @@ def lib() -> C.CDLL:
         "hks_keep_tiles": (i32, [C.POINTER(i32), C.POINTER(i32), i32, u32, C.POINTER(u32)]),
         "hks_skin_vertices": (i32, [vp, vp, vp, vp, u32, vp, u32, vp, vp, vp]),
         "hks_refit_nodes": (i32, [vp, u32, vp, u32]),
+        "hks_refit_boxes": (i32, [vp, u32, vp, u32]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -319,6 +323,7 @@ EXPORTED_SYMBOLS = [
     "hk_set_meshes", "hk_set_meshes_counts", "hk_set_meshes_counts_error",
     "hk_set_mesh_skins", "hk_skin_meshes", "hks_skin_vertices",
     "hk_refit_meshes", "hk_skin_meshes_refit", "hks_refit_nodes",
+    "hk_refit_instances", "hk_refit_meshes_all", "hk_skin_meshes_refit_all", "hks_refit_boxes",
 ]
 
 

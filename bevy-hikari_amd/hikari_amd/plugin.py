@@ -329,25 +329,29 @@ class HikariRenderer:
     def tone_sum(self, settings: _abi.hk_settings, stream=None) -> None:
         _check(self.ctx, self._L.hk_tone_sum(self.ctx, C.byref(settings), _stream(stream)), "hk_tone_sum")
 
-    def update_instances(self, models: np.ndarray, local_aabbs: np.ndarray, stream=None) -> None:
+    def update_instances(self, models: np.ndarray, local_aabbs: np.ndarray, stream=None, refit: bool = False) -> None:
         """New transforms of every instance (hk_update_instances): (n, 16) column-major models and
         (n, 6) local AABBs (center, half extents); the GPU rebuilds instances, TLAS, emissives and
-        the light BVH."""
+        the light BVH.  refit=True (hk_refit_instances): the TLAS and the light BVH keep their trees and get new
+        boxes (include/hk_refit.h) instead of a rebuild: cheaper, and trees that cost more to walk the further the
+        instances are from where the trees were built; call without refit to rebuild."""
         m = np.ascontiguousarray(models, np.float32).reshape(-1, 16)
         a = np.ascontiguousarray(local_aabbs, np.float32).reshape(-1, 6)
         if len(m) != len(a):
             raise ValueError("models and local_aabbs differ in length")
-        _check(self.ctx, self._L.hk_update_instances(self.ctx, m.ctypes.data, a.ctypes.data, len(m), _stream(stream)),
-               "hk_update_instances")
+        name = "hk_refit_instances" if refit else "hk_update_instances"
+        _check(self.ctx, getattr(self._L, name)(self.ctx, m.ctypes.data, a.ctypes.data, len(m), _stream(stream)), name)
 
     def update_meshes(self, scene: Scene, mesh_ids, models=None, local_aabbs=None, stream=None,
-                      refit: bool = False) -> None:
+                      refit=False) -> None:
         """Deformed meshes of an uploaded scene (hk_update_meshes): the positions and normals of `scene.meshes[i]` for
         each i in `mesh_ids` (same topology as uploaded) replace the uploaded ones on the GPU, which rebuilds those
         meshes' primitives and BLAS and then everything update_instances rebuilds.  models / local_aabbs: as for
         update_instances (default: the scene's instance_models() / instance_local_aabbs()).  refit=True
         (hk_refit_meshes): each listed BLAS keeps its tree and gets new boxes (include/hk_refit.h) instead of a rebuild:
-        much cheaper, and a tree that walks more nodes the further the mesh is from the pose it was built for."""
+        much cheaper, and a tree that walks more nodes the further the mesh is from the pose it was built for.
+        refit="all" (hk_refit_meshes_all): the TLAS and the light BVH are refit as well, as by
+        update_instances(refit=True)."""
         m = np.ascontiguousarray(scene.instance_models() if models is None else models, np.float32).reshape(-1, 16)
         a = np.ascontiguousarray(scene.instance_local_aabbs() if local_aabbs is None else local_aabbs,
                                  np.float32).reshape(-1, 6)
@@ -367,7 +371,7 @@ class HikariRenderer:
             u.vertex_count = len(p)
             u.positions = p.ctypes.data
             u.normals = None if n is None else n.ctypes.data
-        name = "hk_refit_meshes" if refit else "hk_update_meshes"
+        name = "hk_refit_meshes_all" if refit == "all" else "hk_refit_meshes" if refit else "hk_update_meshes"
         _check(self.ctx, getattr(self._L, name)(self.ctx, ups, len(mesh_ids), m.ctypes.data, a.ctypes.data, len(m),
                                                 _stream(stream)), name)
 
@@ -401,13 +405,14 @@ class HikariRenderer:
         _check(self.ctx, self._L.hk_set_mesh_skins(self.ctx, arr, len(mesh_ids), _stream(stream)), "hk_set_mesh_skins")
 
     def skin_meshes(self, scene: Scene, poses: dict, models=None, local_aabbs=None, stream=None,
-                    refit: bool = False) -> None:
+                    refit=False) -> None:
         """Pose skinned meshes on the GPU (hk_skin_meshes): poses = {mesh id: (joint_count, 16) column-major joint
         matrices} for meshes registered by set_mesh_skins; the GPU skins their vertices, rebuilds their primitives and
         BLAS and then everything update_instances rebuilds, with the posed meshes' boxes derived on the device.
         `scene` gives the slices (scene.mesh_index) and, by default, models and local_aabbs (instance_models() /
         instance_local_aabbs(); the rows of a posed mesh's instances are ignored).  refit=True (hk_skin_meshes_refit):
-        the posed meshes' BLAS are refit, not rebuilt, as in update_meshes."""
+        the posed meshes' BLAS are refit, not rebuilt, as in update_meshes; refit="all" (hk_skin_meshes_refit_all): the
+        TLAS and the light BVH too."""
         m = np.ascontiguousarray(scene.instance_models() if models is None else models, np.float32).reshape(-1, 16)
         a = np.ascontiguousarray(scene.instance_local_aabbs() if local_aabbs is None else local_aabbs,
                                  np.float32).reshape(-1, 6)
@@ -422,7 +427,7 @@ class HikariRenderer:
             p.mesh = _abi.hk_mesh_index(v, pr, (C.c_uint32 * 2)(n0, nc))
             p.joints = j.ctypes.data
             p.joint_count = len(j)
-        name = "hk_skin_meshes_refit" if refit else "hk_skin_meshes"
+        name = "hk_skin_meshes_refit_all" if refit == "all" else "hk_skin_meshes_refit" if refit else "hk_skin_meshes"
         _check(self.ctx, getattr(self._L, name)(self.ctx, arr, len(poses), m.ctypes.data, a.ctypes.data, len(m),
                                                 _stream(stream)), name)
 
@@ -755,8 +760,12 @@ class HikariPlugin:
         r.tone_sum(s, stream)
         self.frame_number += 1
 
+    def update_instances(self, models, local_aabbs, stream=None, refit: bool = False) -> None:
+        """`prepare_instances` for moved instances (HikariRenderer.update_instances; refit=True keeps both trees)."""
+        self.renderer.update_instances(models, local_aabbs, stream, refit=refit)
+
     def update_meshes(self, scene: Scene, mesh_ids, models=None, local_aabbs=None, stream=None,
-                      refit: bool = False) -> None:
+                      refit=False) -> None:
         """`prepare_mesh_assets` for modified meshes of unchanged topology (HikariRenderer.update_meshes)."""
         self.renderer.update_meshes(scene, mesh_ids, models, local_aabbs, stream, refit=refit)
 
@@ -765,7 +774,7 @@ class HikariPlugin:
         self.renderer.set_mesh_skins(scene, mesh_ids, keep_normals, stream)
 
     def skin_meshes(self, scene: Scene, poses: dict, models=None, local_aabbs=None, stream=None,
-                    refit: bool = False) -> None:
+                    refit=False) -> None:
         """HikariRenderer.skin_meshes: this frame's joint palettes (`SkinnedMeshJoints` x inverse bind poses)."""
         self.renderer.skin_meshes(scene, poses, models, local_aabbs, stream, refit=refit)
 

@@ -301,6 +301,36 @@ def refit_nodes(primitives, nodes) -> np.ndarray:
     return n
 
 
+def refit_boxes(boxes, nodes) -> np.ndarray:
+    """A flattened tree refit on the host over given shape boxes (hks_refit_boxes, include/hk_refit.h's rule): a copy of
+    `nodes` (32 bytes per node) whose entry nodes carry the fold of `boxes` ((count, 6) float32: min xyz, max xyz; the
+    leaf with payload t contributes boxes[t]) over the leaves in their ranges; leaves and every index stay.  Raises
+    HikariError when the nodes are not a bvh-0.7.1 flatten of 3 x count - 2 nodes over the count boxes."""
+    b = np.ascontiguousarray(boxes, np.float32).reshape(-1, 6)
+    n = np.ascontiguousarray(nodes).view(np.uint8).reshape(-1).copy()
+    if len(n) % 32:
+        raise ValueError("nodes are 32 bytes each")
+    rc = _abi.lib().hks_refit_boxes(b.ctypes.data, len(b), n.ctypes.data, len(n) // 32)
+    if rc != 0:
+        raise _abi.HikariError(f"hks_refit_boxes refused the tree ({rc}): not a flatten of 3k - 2 nodes over k boxes")
+    return n
+
+
+def instance_boxes(instances) -> np.ndarray:
+    """(n, 6) float32 shape boxes of the TLAS from hk_instance records (176 bytes each): min xyz, max xyz."""
+    w = np.ascontiguousarray(instances).view(np.uint8).reshape(-1, 176).view(np.float32)
+    return np.concatenate([w[:, 0:3], w[:, 4:7]], axis=1).copy()
+
+
+def emitter_boxes(emissives) -> np.ndarray:
+    """(m, 6) float32 shape boxes of the light BVH from hk_emissive records (64 bytes each): the sphere's box,
+    position - radius and position + radius, one float32 operation per component (include/hk_refit.h)."""
+    w = np.ascontiguousarray(emissives).view(np.uint8).reshape(-1, 64).view(np.float32)
+    pos, r = w[:, 4:7], w[:, 7:8]
+    with np.errstate(invalid="ignore"):
+        return np.concatenate([pos - r, pos + r], axis=1).astype(np.float32)
+
+
 @dataclass
 class StandardMaterial:
     """Bevy 0.9 `StandardMaterial` defaults; colours given as linear RGBA.  Texture fields hold
@@ -500,6 +530,43 @@ class Scene:
         d = _abi.hk_scene_desc.from_buffer_copy(d1)
         d.asset_nodes.data = nodes.ctypes.data
         d._keep = (nodes, scene1)
+        return d
+
+    @staticmethod
+    def refitted_instances(desc0: _abi.hk_scene_desc, scene1) -> _abi.hk_scene_desc:
+        """The scene an instance refit leaves (HikariRenderer.update_instances with refit=True): every array of `scene1`
+        (a Scene, built if it has not been, or a desc such as Scene.refitted returns, for the refit="all" calls) as
+        built, except that the instance nodes and the emissive nodes are those of `desc0` (the scene before the call:
+        same instances, same emitters) refit over scene1's instance and emitter boxes (refit_boxes), and that every
+        node_index of scene1's instance and emissive records is desc0's.  The returned desc keeps its own arrays and
+        scene1 alive."""
+        if isinstance(scene1, _abi.hk_scene_desc):
+            d1 = scene1
+        else:
+            d1 = scene1.desc if scene1.desc is not None else scene1.build()
+        for f in ("instances", "instance_nodes", "emissives", "emissive_nodes"):
+            if getattr(desc0, f).count != getattr(d1, f).count:
+                raise ValueError(f"the two scenes differ in their {f} count")
+
+        def words(d, f, size):
+            a = getattr(d, f)
+            return np.frombuffer(C.string_at(a.data, a.count * size), np.uint8).copy().reshape(-1, size).view(np.uint32)
+
+        inst, inst0 = words(d1, "instances", 176), words(desc0, "instances", 176)
+        inst[:, 7] = inst0[:, 7]
+        tlas = refit_boxes(instance_boxes(inst), words(desc0, "instance_nodes", 32))
+        d = _abi.hk_scene_desc.from_buffer_copy(d1)
+        d.instances.data = inst.ctypes.data
+        d.instance_nodes.data = tlas.ctypes.data
+        keep = [inst, tlas, scene1]
+        if d1.emissives.count:
+            em, em0 = words(d1, "emissives", 64), words(desc0, "emissives", 64)
+            em[:, 13] = em0[:, 13]
+            lbvh = refit_boxes(emitter_boxes(em), words(desc0, "emissive_nodes", 32))
+            d.emissives.data = em.ctypes.data
+            d.emissive_nodes.data = lbvh.ctypes.data
+            keep += [em, lbvh]
+        d._keep = tuple(keep)
         return d
 
     def instance_models(self) -> np.ndarray:

@@ -519,6 +519,32 @@ int hk_refit_meshes(hk_ctx* ctx, const hk_mesh_update* meshes, uint32_t mesh_cou
 int hk_skin_meshes_refit(hk_ctx* ctx, const hk_skin_pose* poses, uint32_t n, const float* models,
                          const float* local_aabbs, uint32_t count, void* stream);
 
+/* Instance refit: hk_update_instances with the TLAS and the light BVH REFIT, not rebuilt.  Both trees
+ * keep every entry_index and exit_index, so every node_index in the instance and emissive records stays too, and each
+ * entry node's box becomes the fold of include/hk_refit.h's rule over the shape boxes of the leaves in its range: an
+ * instance's world box for the TLAS, an emitter's sphere box (position -+ radius) for the light BVH.  The reference has
+ * no such path (it rebuilds, instance.rs:284-437); the rule is this library's own.  The records, alias tables and
+ * emitters are computed as by hk_update_instances; the two one-workgroup SAH builds and the node_index backfill are
+ * replaced by one launch over all nodes of both trees and at most one more over their large nodes.
+ * QUALITY DEGRADES WITH THE MOTION, as for a BLAS refit: boxes stay tight around their leaves, but instances that moved
+ * apart make sibling boxes overlap, and a tree refit far from where it was built costs more to walk.  It stays correct.
+ * The caller decides when that matters and then calls hk_update_instances (or any rebuilding call), which builds both
+ * trees from the current boxes and gives the host builder's trees again; the library has no policy and no quality
+ * query.  A refit cannot follow a changed set: hk_set_instances and hk_set_meshes always rebuild.
+ * Arguments, refusals, messages (with the function's own name in front) and states are hk_update_instances': previous
+ * models for the motion vectors, the shared-transform and scene-box state, the singular-transform refusal.  Afterwards
+ * all nine arrays are what hks_build + hk_scene_upload give for the scene with the new models, except that the
+ * instance nodes and the emissive nodes are those before the call passed through hikari_scene.h hks_refit_boxes with
+ * the new instance and emitter boxes, and every node_index is the one before the call.  The G-buffer stack bound does
+ * not move.  A steady refit allocates nothing.  Waits for the stream once.
+ * hk_refit_meshes_all / hk_skin_meshes_refit_all: hk_refit_meshes / hk_skin_meshes_refit with the two instance trees
+ * refit as well, so that no tree is built in the call. */
+int hk_refit_instances(hk_ctx* ctx, const float* models, const float* local_aabbs, uint32_t count, void* stream);
+int hk_refit_meshes_all(hk_ctx* ctx, const hk_mesh_update* meshes, uint32_t mesh_count, const float* models,
+                        const float* local_aabbs, uint32_t count, void* stream);
+int hk_skin_meshes_refit_all(hk_ctx* ctx, const hk_skin_pose* poses, uint32_t n, const float* models,
+                             const float* local_aabbs, uint32_t count, void* stream);
+
 /* the element capacities beside hk_scene_counts' counts, hk_scene_desc order: what each array holds before a call
  * has to allocate (hk_set_instances: 3, 4, 5, 7, 8; hk_add_meshes: 0, 1, 2; array 6 never grows).  HK_ERR_STATE
  * without a scene. */

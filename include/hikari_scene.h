@@ -100,6 +100,14 @@ int hks_skin_vertices(const float* positions, const float* normals, const uint16
  * node_count], or whose range (i, exit) is not tiled exactly by one leaf or by two entry nodes' ranges. */
 int hks_refit_nodes(const hk_primitive* primitives, uint32_t primitive_count, hk_node* nodes, uint32_t node_count);
 
+/* The same refit over GIVEN shape boxes (include/hk_refit.h): the host side of hk_refit_instances'
+ * contract.  boxes: count x 6 floats, min xyz then max xyz; the leaf with payload t contributes boxes[t].  For the TLAS
+ * boxes[t] is instance t's world box (the min / max of its record), for the light BVH emitter e's sphere box (position -
+ * radius, position + radius, one f32 operation per component).  nodes: a bvh-0.7.1 flatten of node_count = 3 x count - 2
+ * nodes.  What is stored, what stays, the refusals and the well-formedness checks are hks_refit_nodes' with count for
+ * primitive_count; `nodes` is untouched on refusal.  One O(n) backwards pass, no device. */
+int hks_refit_boxes(const float* boxes, uint32_t count, hk_node* nodes, uint32_t node_count);
+
 #ifdef __cplusplus
 }
 #endif
