@@ -1,6 +1,6 @@
 // hk_dynamic.hip — dynamic instances, deforming meshes, changed instance sets
 // (DESIGN §0 f8), appended meshes, new mesh lists, skinned meshes, the
-// BLAS refit and the instance refit on the device.
+// BLAS refit, the instance refit and the tree costs on the device.
 //
 // The reference re-runs `prepare_instances` on the CPU whenever a transform changes
 // (instance.rs:284-437: instance records with world AABBs and inverse-transpose models, the
@@ -18,6 +18,7 @@
 #include "hk_launch.h"
 #include "../../include/hk_skin.h"
 #include "../../include/hk_refit.h"
+#include "../../include/hk_cost.h"
 
 namespace hk {
 
@@ -1296,6 +1297,118 @@ void launch_dynamic_step(const DynamicArgs& D, DynamicStep step, hipStream_t st)
         break;
     }
     }
+}
+
+// ---- tree costs (include/hk_cost.h: the rule, this project's own; the host side is hk_scene.cpp
+// hks_tree_cost over the same header).  How expensive the resident trees are to walk, for a caller that refits and has
+// to decide when to rebuild.  One launch serves every listed tree: a table of CostSlice records (hk_launch.h), their
+// nodes laid end to end as RefitTrees lays two, a thread per node.  A thread finds its slice by bisection over the
+// slices' first nodes, loads its node as two 16-byte words and, where it is an entry node, weighs its half area against
+// the slice's root's (the join of the slice's two top entries, which every entry thread of the slice loads for itself:
+// the same two nodes for a whole slice, out of L1/L2).  A leaf contributes nothing.
+// The sums are 64-bit INTEGERS (32.32 fixed point), so they have no order and the words are the host's whatever the
+// arrival order: no float atomics.  A workgroup's 256 consecutive nodes touch at most 256 consecutive slices; each has
+// a row of LDS accumulators.  A wave whose 64 nodes lie in one slice (the common case) sums in registers (__shfl_xor)
+// and adds once to the row, a wave that straddles slices adds lane by lane; after the barrier one thread per touched
+// slice adds the row to the slice's global accumulators, which the stream zeroed before the launch: one global add per
+// field per workgroup per slice it touches.  Nothing passes between workgroups inside the launch: no fence, no spin
+// wait; the stream orders the zeroing, the launch and the readback.  root_half_area has one writer, node 0's thread.
+// Hostile trees (hk_scene_upload takes any nodes): every index is bounded by the slice's count alone: an exit past the
+// slice is clamped, a top entry's exit past the slice leaves the root node 0's box alone.  Never taken on a
+// well-formed tree.
+struct CostShared {
+    unsigned long long inner[256], leaf[256];
+    uint32_t entries[256];
+};
+// the slice that holds node g of the launch: the last one that starts at or before it (every slice has a node)
+HKD uint32_t cost_slice_of(const CostSlice* tab, uint32_t n, uint32_t g)
+{
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (tab[mid].first <= g) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+// node i of a slice as two 16-byte loads: its box (min xyz, max xyz), entry_index and exit_index
+HKD void cost_load_node(const hk_node* nodes, uint32_t i, float* box, uint32_t* entry, uint32_t* exit)
+{
+    const float4* p = (const float4*)(nodes + i);
+    const float4 a = p[0], b = p[1];
+    box[0] = a.x, box[1] = a.y, box[2] = a.z;
+    box[3] = b.x, box[4] = b.y, box[5] = b.z;
+    *entry = __float_as_uint(a.w);
+    *exit = __float_as_uint(b.w);
+}
+// R of a slice of count >= 2 nodes
+HKD float cost_root_half_area(const hk_node* nodes, uint32_t count)
+{
+    float a[6], b[6], root[6];
+    uint32_t entry, exit;
+    cost_load_node(nodes, 0u, a, &entry, &exit);
+    // (a top entry's exit past the slice: node 0's box alone, joined twice, which changes nothing; registers throughout)
+    cost_load_node(nodes, exit < count ? exit : 0u, b, &entry, &exit);
+    hk_cost_root(a, b, root);
+    return hk_cost_half_area(root);
+}
+__global__ __launch_bounds__(256) void k_tree_cost(const CostSlice* tab, uint32_t n_slices, uint32_t n_nodes,
+                                                   hk_tree_cost* out)
+{
+    __shared__ CostShared sh;
+    const uint32_t g0 = blockIdx.x * 256u, g = g0 + threadIdx.x;
+    sh.inner[threadIdx.x] = 0ull;
+    sh.leaf[threadIdx.x] = 0ull;
+    sh.entries[threadIdx.x] = 0u;
+    __syncthreads();
+    const uint32_t s0 = cost_slice_of(tab, n_slices, g0);  // (block-uniform: g0 < n_nodes by the grid's size)
+    // a thread past the last node stands in the last slice with nothing to add, so that every lane reaches the shuffles
+    const uint32_t s = g < n_nodes ? cost_slice_of(tab, n_slices, g) : n_slices - 1u;
+    unsigned long long inner = 0ull, leaf = 0ull;
+    uint32_t entries = 0u;
+    if (g < n_nodes) {
+        const CostSlice c = tab[s];
+        const uint32_t i = g - c.first;
+        if (c.count > 1u && i < c.count) {  // (a lone leaf has no entry node)
+            float box[6];
+            uint32_t entry, exit;
+            cost_load_node(c.nodes, i, box, &entry, &exit);
+            if (!hk_refit_is_leaf(entry)) {
+                const float R = cost_root_half_area(c.nodes, c.count);
+                const unsigned long long q = hk_cost_weight(hk_cost_half_area(box), R);
+                if (hk_cost_over_leaf(i, exit < c.count ? exit : c.count)) leaf = q;
+                else inner = q;
+                entries = 1u;
+                if (i == 0u) out[c.slot].root_half_area = R;
+            }
+        }
+    }
+    const uint32_t row = s - s0;  // (< 256: the slices between two nodes of one workgroup)
+    if (__shfl(s, 0, 64) == __shfl(s, 63, 64)) {  // (s rises with the lane: the whole wave in one slice)
+        for (int o = 32; o > 0; o >>= 1) {
+            inner += __shfl_xor(inner, o, 64);
+            leaf += __shfl_xor(leaf, o, 64);
+            entries += __shfl_xor(entries, o, 64);
+        }
+        if ((threadIdx.x & 63u) != 0u) entries = 0u;  // (lane 0 adds for the wave)
+    }
+    if (entries && row < 256u) {
+        atomicAdd(&sh.inner[row], inner);
+        atomicAdd(&sh.leaf[row], leaf);
+        atomicAdd(&sh.entries[row], entries);
+    }
+    __syncthreads();
+    if (sh.entries[threadIdx.x]) {  // (a touched slice: s0 + threadIdx.x < n_slices)
+        hk_tree_cost* o = out + tab[s0 + threadIdx.x].slot;
+        atomicAdd((unsigned long long*)&o->inner, sh.inner[threadIdx.x]);
+        atomicAdd((unsigned long long*)&o->leaf, sh.leaf[threadIdx.x]);
+        atomicAdd(&o->entries, sh.entries[threadIdx.x]);
+    }
+}
+void launch_tree_cost(const CostSlice* table, uint32_t n_slices, uint32_t n_nodes, hk_tree_cost* out, hipStream_t st)
+{
+    if (n_slices == 0u || n_nodes == 0u) return;
+    hipLaunchKernelGGL(k_tree_cost, dim3((n_nodes + 255u) / 256u), dim3(256), 0, st, table, n_slices, n_nodes, out);
 }
 
 // what follows the instance records and their boxes: the TLAS, the emitters' areas, alias tables, records and light

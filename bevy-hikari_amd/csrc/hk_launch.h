@@ -185,6 +185,16 @@ struct RefitTrees {
     uint32_t n_trees, n_nodes;
 };
 
+// Tree costs (hk_tree_costs; include/hk_cost.h): one launch over the nodes of every listed tree laid end
+// to end, as RefitTrees lays two.  CostSlice: one tree, a flatten of `count` >= 1 nodes that starts at node `first` of
+// the launch (the running sum of the counts before it) and whose cost goes to out[slot]; every slice has a slot of its
+// own.  out: zeroed on the stream before the launch; the kernel adds into it and stores each slot's root_half_area.
+struct CostSlice {
+    const hk_node* nodes;
+    uint32_t count, first, slot, pad;
+};
+void launch_tree_cost(const CostSlice* table, uint32_t n_slices, uint32_t n_nodes, hk_tree_cost* out, hipStream_t st);
+
 // A new instance set (hk_dynamic.hip): one record per instance, the layout of hk_instance_desc.
 struct InstanceDesc {
     hk_mesh_index mesh;

@@ -380,6 +380,12 @@ struct hk_ctx {
     uint32_t gb_tlas_depth = 0;   // TLAS part of it: set at upload and by every TLAS build; a refit keeps the tree
     void* dyn_scratch = nullptr;  // hk_update_instances scratch (sized at upload)
     size_t dyn_bytes = 0;
+    // hk_tree_costs: the device block (slice table, accumulators), its bytes, and the host sides of both, which keep
+    // their capacity from call to call
+    void* cost_scratch = nullptr;
+    size_t cost_bytes = 0;
+    std::vector<CostSlice> cost_table;
+    std::vector<hk_tree_cost> cost_host;
     // hk_update_meshes: the instanced meshes as upload recorded them (slice, vertices their primitives index, BLAS
     // depth), the per-node mesh tables of the BLAS derivatives (primitive offset, node base, node count) and scratch
     struct MeshSlice {
@@ -1176,6 +1182,7 @@ void hk_destroy(hk_ctx* c)
     release(c->walk_nodes[1]);
     release(c->collapse_scratch);
     release(c->dyn_scratch);
+    release(c->cost_scratch);
     release(c->blas_aux);
     release(c->mesh_scratch);
     release(c->skin_block);
@@ -2001,6 +2008,60 @@ int hk_refit_instances(hk_ctx* c, const float* models, const float* local_aabbs,
     HK_TRY(update_args_ok(c, count, "hk_refit_instances"));
     (void)hipSetDevice(c->device);
     return rebuild_instances(c, models, local_aabbs, count, pick(c, stream), nullptr, nullptr, nullptr, true);
+}
+
+// Tree costs (include/hk_cost.h).  Every check first; then the table of the trees asked for (slot 0: the
+// TLAS, 1: the light BVH, 2 + j: mesh_ids[j]'s slice from the registry; a tree without nodes has no table entry and
+// keeps its zeros), the zeroed accumulators, one launch and one readback on `st`, and the call's one wait.  Only the
+// scratch is written: the scene arrays are read as the last edit's wait left them, so nothing is joined or serialized.
+int hk_tree_costs(hk_ctx* c, const uint32_t* mesh_ids, uint32_t mesh_count, hk_tree_cost* tlas, hk_tree_cost* lights,
+                  hk_tree_cost* meshes, void* stream)
+{
+    if (!c) return HK_ERR_INVALID;
+    if (mesh_count && !mesh_ids) return fail(c, HK_ERR_INVALID, "hk_tree_costs: null pointer");
+    if (!c->has_scene) return fail(c, HK_ERR_STATE, "no scene uploaded (hk_scene_upload)");
+    for (uint32_t j = 0; j < mesh_count; ++j)
+        if (mesh_ids[j] >= c->meshes.size())
+            return fail(c, HK_ERR_INVALID, "hk_tree_costs: mesh " + std::to_string(mesh_ids[j]) + " of " +
+                                               std::to_string(c->meshes.size()) + " known mesh slices");
+    const uint32_t n_listed = meshes ? mesh_count : 0u;
+    const size_t slots = 2u + (size_t)n_listed;
+    std::vector<CostSlice>& table = c->cost_table;
+    table.clear();
+    uint64_t n_nodes = 0;
+    auto add = [&](const void* nodes, uint32_t count, uint32_t slot) {
+        if (count == 0u) return;
+        table.push_back(CostSlice{(const hk_node*)nodes, count, (uint32_t)n_nodes, slot, 0u});
+        n_nodes += count;
+    };
+    if (tlas) add(c->buf[5], c->count[5], 0u);
+    if (lights) add(c->buf[7], c->count[7], 1u);
+    for (uint32_t j = 0; j < n_listed && n_nodes <= 0xFFFFFFFFull; ++j) {
+        const hk_mesh_index& m = c->meshes[mesh_ids[j]].index;  // (inside the asset nodes: checked where it became known)
+        add((const hk_node*)c->buf[2] + m.node[0], m.node[1], 2u + j);
+    }
+    if (n_nodes > 0xFFFFFF00ull) return fail(c, HK_ERR_INVALID, "hk_tree_costs: more than 2^32 nodes listed");
+    c->cost_host.assign(slots, hk_tree_cost{0, 0, 0.0f, 0});
+    if (!table.empty()) {
+        (void)hipSetDevice(c->device);
+        hipStream_t st = pick(c, stream);
+        const size_t sz[] = {table.size() * sizeof(CostSlice), slots * sizeof(hk_tree_cost)};
+        char* part[2];
+        HK_TRY(carve(c, &c->cost_scratch, &c->cost_bytes, sz, 2, part));
+        HK_HIP(c, hipMemcpyAsync(part[0], table.data(), sz[0], hipMemcpyHostToDevice, st));
+        HK_HIP(c, hipMemsetAsync(part[1], 0, sz[1], st));
+        timed(c, "tree_costs", st, [&] {
+            launch_tree_cost((const CostSlice*)part[0], (uint32_t)table.size(), (uint32_t)n_nodes, (hk_tree_cost*)part[1],
+                             st);
+        });
+        HK_HIP(c, hipGetLastError());
+        HK_HIP(c, hipMemcpyAsync(c->cost_host.data(), part[1], sz[1], hipMemcpyDeviceToHost, st));
+        HK_HIP(c, hipStreamSynchronize(st));
+    }
+    if (tlas) *tlas = c->cost_host[0];
+    if (lights) *lights = c->cost_host[1];
+    for (uint32_t j = 0; j < n_listed; ++j) meshes[j] = c->cost_host[2u + j];
+    return HK_OK;
 }
 
 // Meshes on their way to a build (hk_update_meshes, hk_add_meshes and the new entries of hk_set_meshes): the tables in

@@ -11,6 +11,7 @@
 #include "../../include/hikari_scene.h"
 #include "../../include/hk_skin.h"
 #include "../../include/hk_refit.h"
+#include "../../include/hk_cost.h"
 
 #include <algorithm>
 #include <cmath>
@@ -709,11 +710,10 @@ int hks_skin_vertices(const float* positions, const float* normals, const uint16
 // ranges tile it, so by induction over the range lengths the nodes form one tree over [0, node_count), and each shape is
 // some leaf's payload once.  The flatten is pre-order, so one pass down the indices finds the boxes an entry node joins
 // already refit.
-extern "C++" {
-template <class Shape>
-static int refit_flat(uint32_t shape_count, hk_node* nodes, uint32_t node_count, Shape shape)
+// (flat_ok: the check alone, which hks_tree_cost shares)
+static bool flat_ok(uint32_t shape_count, const hk_node* nodes, uint32_t node_count)
 {
-    if ((uint64_t)node_count != 3u * (uint64_t)shape_count - 2u) return HK_ERR_INVALID;
+    if ((uint64_t)node_count != 3u * (uint64_t)shape_count - 2u) return false;
     const uint32_t n = node_count;
     auto leaf = [&](uint32_t i) { return hk_refit_is_leaf(nodes[i].entry_index) != 0; };
     // an entry node at i whose range ends at `end`
@@ -723,21 +723,29 @@ static int refit_flat(uint32_t shape_count, hk_node* nodes, uint32_t node_count,
         const hk_node& nd = nodes[i];
         if (leaf(i)) {
             const uint32_t t = hk_refit_leaf_primitive(nd.entry_index);
-            if (nd.exit_index != i + 1u || t >= shape_count || seen[t]) return HK_ERR_INVALID;
+            if (nd.exit_index != i + 1u || t >= shape_count || seen[t]) return false;
             seen[t] = true;
             continue;
         }
         const uint32_t e = nd.exit_index;
-        if (nd.entry_index != i + 1u || e <= i + 1u || e > n) return HK_ERR_INVALID;
+        if (nd.entry_index != i + 1u || e <= i + 1u || e > n) return false;
         if (leaf(i + 1u)) {
-            if (e != i + 2u) return HK_ERR_INVALID;
+            if (e != i + 2u) return false;
         } else {
             const uint32_t mid = nodes[i + 1u].exit_index;
-            if (mid <= i + 1u || mid >= e || !entry_to(mid, e)) return HK_ERR_INVALID;
+            if (mid <= i + 1u || mid >= e || !entry_to(mid, e)) return false;
         }
     }
     // the root: a lone leaf, or the two entry nodes of the root's children tiling the slice
-    if (shape_count == 1u ? !leaf(0) : (leaf(0) || !entry_to(nodes[0].exit_index, n))) return HK_ERR_INVALID;
+    return shape_count == 1u ? leaf(0) : (!leaf(0) && entry_to(nodes[0].exit_index, n));
+}
+extern "C++" {
+template <class Shape>
+static int refit_flat(uint32_t shape_count, hk_node* nodes, uint32_t node_count, Shape shape)
+{
+    if (!flat_ok(shape_count, nodes, node_count)) return HK_ERR_INVALID;
+    const uint32_t n = node_count;
+    auto leaf = [&](uint32_t i) { return hk_refit_is_leaf(nodes[i].entry_index) != 0; };
     for (uint32_t i = n; i-- > 0;) {
         hk_node& nd = nodes[i];
         if (leaf(i)) continue;
@@ -776,6 +784,40 @@ int hks_refit_boxes(const float* boxes, uint32_t count, hk_node* nodes, uint32_t
     return refit_flat(count, nodes, node_count, [&](uint32_t t, float* s) {
         for (int k = 0; k < 6; ++k) s[k] = boxes[6u * (size_t)t + k];
     });
+}
+
+// The cost of a flattened tree by include/hk_cost.h's rule: the root from the two top entries, then one pass down the
+// entry nodes.  The flatten is checked as a refit checks it (flat_ok), so every index below is inside the slice.
+int hks_tree_cost(const hk_node* nodes, uint32_t count, hk_tree_cost* out)
+{
+    if (!out || (count && !nodes)) return HK_ERR_INVALID;
+    hk_tree_cost cost = {0, 0, 0.0f, 0};
+    if (count) {
+        if ((count + 2u) % 3u != 0 || !flat_ok((count + 2u) / 3u, nodes, count)) return HK_ERR_INVALID;
+        auto box_of = [&](uint32_t i, float* b) {
+            for (int k = 0; k < 3; ++k) {
+                b[k] = nodes[i].min[k];
+                b[3 + k] = nodes[i].max[k];
+            }
+        };
+        if (count > 1u) {
+            float a[6], b[6], root[6];
+            box_of(0, a);
+            box_of(nodes[0].exit_index, b);
+            hk_cost_root(a, b, root);
+            cost.root_half_area = hk_cost_half_area(root);
+        }
+        for (uint32_t i = 0; i < count; ++i) {
+            if (hk_refit_is_leaf(nodes[i].entry_index)) continue;
+            float b[6];
+            box_of(i, b);
+            const uint64_t q = hk_cost_weight(hk_cost_half_area(b), cost.root_half_area);
+            (hk_cost_over_leaf(i, nodes[i].exit_index) ? cost.leaf : cost.inner) += q;
+            cost.entries++;
+        }
+    }
+    *out = cost;
+    return HK_OK;
 }
 
 }  // extern "C"

@@ -173,6 +173,11 @@ class hk_present_target(C.Structure):
                 ("vp_h", C.c_uint32), ("input", C.c_int32)]
 
 
+class hk_tree_cost(C.Structure):
+    """include/hikari_amd.h hk_tree_cost (hk_tree_costs, hks_tree_cost; the rule: include/hk_cost.h)."""
+    _fields_ = [("inner", C.c_uint64), ("leaf", C.c_uint64), ("root_half_area", C.c_float), ("entries", C.c_uint32)]
+
+
 class hk_counters(C.Structure):
     _fields_ = [("traverse_top", C.c_uint64), ("traverse_emitter", C.c_uint64), ("primary", C.c_uint64),
                 ("primary_reused", C.c_uint64)]
@@ -257,6 +262,7 @@ def lib() -> C.CDLL:
         "hk_refit_instances": (i32, [vp, vp, vp, u32, vp]),
         "hk_refit_meshes_all": (i32, [vp, C.POINTER(hk_mesh_update), u32, vp, vp, u32, vp]),
         "hk_skin_meshes_refit_all": (i32, [vp, C.POINTER(hk_skin_pose), u32, vp, vp, u32, vp]),
+        "hk_tree_costs": (i32, [vp, C.POINTER(u32), u32] + [C.POINTER(hk_tree_cost)] * 3 + [vp]),
         "hk_scene_shared_transform": (i32, [vp, C.POINTER(i32)]),
         "hk_instance_set_counts": (i32, [C.POINTER(hk_scene_desc), C.POINTER(hk_instance_desc), u32, vp, C.POINTER(u32)]),
         "hk_read_scene_array": (i32, [vp, i32, vp, C.c_size_t]),
@@ -299,6 +305,7 @@ def lib() -> C.CDLL:
         "hks_skin_vertices": (i32, [vp, vp, vp, vp, u32, vp, u32, vp, vp, vp]),
         "hks_refit_nodes": (i32, [vp, u32, vp, u32]),
         "hks_refit_boxes": (i32, [vp, u32, vp, u32]),
+        "hks_tree_cost": (i32, [vp, u32, C.POINTER(hk_tree_cost)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -324,6 +331,7 @@ EXPORTED_SYMBOLS = [
     "hk_set_mesh_skins", "hk_skin_meshes", "hks_skin_vertices",
     "hk_refit_meshes", "hk_skin_meshes_refit", "hks_refit_nodes",
     "hk_refit_instances", "hk_refit_meshes_all", "hk_skin_meshes_refit_all", "hks_refit_boxes",
+    "hk_tree_costs", "hks_tree_cost",
 ]
 
 

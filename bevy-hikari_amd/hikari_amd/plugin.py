@@ -16,6 +16,7 @@ from typing import Optional
 import numpy as np
 
 from . import _abi
+from .cost import TreeCost
 from .scene import Mesh, Scene, load_noise, texture_array
 from .settings import HikariSettings, HikariUniversalSettings, PresentFormat
 
@@ -495,6 +496,20 @@ class HikariRenderer:
         _check(self.ctx, self._L.hk_scene_capacity(self.ctx, out), "hk_scene_capacity")
         return list(out)
 
+    def tree_costs(self, mesh_ids=(), stream=None) -> dict:
+        """How expensive the resident trees are to walk (hk_tree_costs; the rule: include/hk_cost.h), computed on the
+        GPU in one launch: {"tlas": TreeCost, "lights": TreeCost (zeros without emitters), "meshes": [TreeCost of the
+        BLAS of each id in `mesh_ids`]}.  A mesh id indexes the context's known slices in the order they became known:
+        after upload_scene the distinct meshes in the order the instances first carry them.  Reads the scene, changes
+        nothing; what a caller that refits decides a rebuild with (hikari_amd.RefitPolicy)."""
+        ids = np.ascontiguousarray(mesh_ids, np.uint32).reshape(-1)
+        tlas, lights = _abi.hk_tree_cost(), _abi.hk_tree_cost()
+        meshes = (_abi.hk_tree_cost * max(len(ids), 1))()
+        _check(self.ctx, self._L.hk_tree_costs(self.ctx, ids.ctypes.data_as(C.POINTER(C.c_uint32)) if len(ids) else None,
+                                               len(ids), tlas, lights, meshes, _stream(stream)), "hk_tree_costs")
+        return {"tlas": TreeCost.from_c(tlas), "lights": TreeCost.from_c(lights),
+                "meshes": [TreeCost.from_c(meshes[j]) for j in range(len(ids))]}
+
     def scene_shared_transform(self) -> bool:
         """Every instance of the current scene carries one bit-identical transform (hk_scene_shared_transform): the
         walks then compute one local ray per walk while option shared_xform is on."""
@@ -763,6 +778,10 @@ class HikariPlugin:
     def update_instances(self, models, local_aabbs, stream=None, refit: bool = False) -> None:
         """`prepare_instances` for moved instances (HikariRenderer.update_instances; refit=True keeps both trees)."""
         self.renderer.update_instances(models, local_aabbs, stream, refit=refit)
+
+    def tree_costs(self, mesh_ids=(), stream=None) -> dict:
+        """The resident trees' costs (HikariRenderer.tree_costs): what decides between a refit and a rebuild."""
+        return self.renderer.tree_costs(mesh_ids, stream)
 
     def update_meshes(self, scene: Scene, mesh_ids, models=None, local_aabbs=None, stream=None,
                       refit=False) -> None:

@@ -507,7 +507,7 @@ int hk_skin_meshes(hk_ctx* ctx, const hk_skin_pose* poses, uint32_t n, const flo
  * for walks more nodes per ray.  It stays correct: every ray finds the hits a rebuilt tree finds, up to the order in
  * which equal hits are met.  The caller decides when that matters and then calls hk_update_meshes / hk_skin_meshes on
  * the same mesh, which rebuild from the current vertices and give the host builder's tree again; the library has no
- * policy of its own and no quality query.
+ * policy of its own, and hk_tree_costs (below) is the quality query to decide with.
  * Arguments, refusals, messages (with the function's own name in front) and states are those of hk_update_meshes and
  * hk_skin_meshes; a refusal leaves the context unchanged; mesh_count == 0 / n == 0 is hk_update_instances.  Afterwards
  * all nine arrays are what hks_build + hk_scene_upload give for the deformed scene, except that each listed mesh's
@@ -529,8 +529,9 @@ int hk_skin_meshes_refit(hk_ctx* ctx, const hk_skin_pose* poses, uint32_t n, con
  * QUALITY DEGRADES WITH THE MOTION, as for a BLAS refit: boxes stay tight around their leaves, but instances that moved
  * apart make sibling boxes overlap, and a tree refit far from where it was built costs more to walk.  It stays correct.
  * The caller decides when that matters and then calls hk_update_instances (or any rebuilding call), which builds both
- * trees from the current boxes and gives the host builder's trees again; the library has no policy and no quality
- * query.  A refit cannot follow a changed set: hk_set_instances and hk_set_meshes always rebuild.
+ * trees from the current boxes and gives the host builder's trees again; the library has no policy, and hk_tree_costs
+ * (below) is the quality query to decide with.  A refit cannot follow a changed set: hk_set_instances and hk_set_meshes
+ * always rebuild.
  * Arguments, refusals, messages (with the function's own name in front) and states are hk_update_instances': previous
  * models for the motion vectors, the shared-transform and scene-box state, the singular-transform refusal.  Afterwards
  * all nine arrays are what hks_build + hk_scene_upload give for the scene with the new models, except that the
@@ -544,6 +545,35 @@ int hk_refit_meshes_all(hk_ctx* ctx, const hk_mesh_update* meshes, uint32_t mesh
                         const float* local_aabbs, uint32_t count, void* stream);
 int hk_skin_meshes_refit_all(hk_ctx* ctx, const hk_skin_pose* poses, uint32_t n, const float* models,
                              const float* local_aabbs, uint32_t count, void* stream);
+
+/* Tree costs: how expensive the resident trees are to walk, by the rule of include/hk_cost.h, computed ON
+ * THE GPU from the nodes as they stand: what a caller that refits (hk_refit_instances, hk_refit_meshes, the _all calls)
+ * decides a rebuild with.  The reference has no such query (it never refits); the rule is this library's own.
+ *   hk_tree_cost: over the entry nodes of one flattened tree, each weighted by q = its box's half area over the root's,
+ *   as a 32.32 fixed-point number: `leaf` sums q over the entry nodes above one leaf (the expected shape tests of a ray
+ *   that meets the root box, x 2^32), `inner` over the others (the expected further box tests); `entries` counts them and
+ *   root_half_area is the divisor.  A tree of one shape has no entry node: every field is 0.  The library fixes no SAH
+ *   constants: (c_box x inner + c_shape x leaf) / 2^32 with the caller's.  Only the RATIO of two trees over the same
+ *   shapes means anything (a refit tree against the same tree at its last build, or against a rebuilt one).
+ * tlas / lights: the cost of the TLAS / the light BVH (zeros for a scene without emitters).  meshes[j]: the cost of the
+ * BLAS of mesh mesh_ids[j], an index into the context's known slices in the order they became known: at hk_scene_upload
+ * the distinct slices in the order in which the instances first carry them, then each slice as hk_set_instances
+ * registered or hk_add_meshes appended it; after hk_set_meshes its list's order.  Ids may repeat and come in any order.
+ * Any out pointer may be NULL: that tree is not computed.  One launch serves every listed tree; the sums are integer
+ * adds, so every field is bit-reproducible and equals hikari_scene.h hks_tree_cost on the same nodes.
+ * The call READS the scene and writes only scratch of its own: all nine arrays, the picture, the histories and the
+ * G-buffer stack bound are untouched, and the frames that follow are bit-identical to frames without it.  The scratch
+ * keeps a capacity beside its size: a steady query allocates nothing.  Waits for the stream once.
+ * HK_ERR_INVALID with a message that names hk_tree_costs, the context unchanged: mesh_ids NULL with mesh_count != 0; an
+ * id at or past the number of known slices.  HK_ERR_STATE without a scene. */
+typedef struct hk_tree_cost {
+    uint64_t inner;
+    uint64_t leaf;
+    float root_half_area;
+    uint32_t entries;
+} hk_tree_cost; /* 24 bytes */
+int hk_tree_costs(hk_ctx* ctx, const uint32_t* mesh_ids, uint32_t mesh_count, hk_tree_cost* tlas, hk_tree_cost* lights,
+                  hk_tree_cost* meshes, void* stream);
 
 /* the element capacities beside hk_scene_counts' counts, hk_scene_desc order: what each array holds before a call
  * has to allocate (hk_set_instances: 3, 4, 5, 7, 8; hk_add_meshes: 0, 1, 2; array 6 never grows).  HK_ERR_STATE

@@ -108,6 +108,15 @@ int hks_refit_nodes(const hk_primitive* primitives, uint32_t primitive_count, hk
  * primitive_count; `nodes` is untouched on refusal.  One O(n) backwards pass, no device. */
 int hks_refit_boxes(const float* boxes, uint32_t count, hk_node* nodes, uint32_t node_count);
 
+/* The cost of a flattened tree on the host, by the rule of include/hk_cost.h: the host side of hk_tree_costs' contract,
+ * and what a caller without a device uses.  nodes: `count` nodes, a bvh-0.7.1 flatten of count = 3k - 2 nodes over k
+ * shapes (a mesh's slice of the asset nodes, the instance nodes, the emissive nodes).  out: every field as hikari_amd.h
+ * hk_tree_cost describes; count == 0 (no tree: a scene without emitters) and count == 1 (a lone leaf) give zeros.  Leaf
+ * boxes are not read.  One O(n) pass, no device.  Returns 0, or HK_ERR_INVALID with `out` untouched for a null pointer
+ * (out; nodes with count != 0), a count that is not 3k - 2, or a slice that is not a well-formed flatten, by
+ * hks_refit_boxes' checks. */
+int hks_tree_cost(const hk_node* nodes, uint32_t count, hk_tree_cost* out);
+
 #ifdef __cplusplus
 }
 #endif
