@@ -300,3 +300,12 @@ def emissive_records(desc) -> np.ndarray:
     range."""
     from parity import host_scene_array
     return np.frombuffer(host_scene_array(desc, 8, np.dtype((np.void, 64))).tobytes(), np.uint32).reshape(-1, 16)
+
+
+# ------------------------------------------------------------------ applying a step to a HikariRenderer
+def apply(r, name: str, k: int, **kw):
+    """Step k's hk_set_instances on `r` (kw: models, local_aabbs or stream in place of the step's own)."""
+    c = case(name)
+    scene = c.scenes[k]
+    kw.setdefault("local_aabbs", local_aabbs(scene))
+    r.set_instances(scene, previous=c.previous[k], materials=c.materials, **kw)

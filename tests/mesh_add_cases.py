@@ -318,3 +318,21 @@ def new_slices(name: str, k: int) -> list:
     c = case(name)
     first = len(c.scenes[k].meshes) - len(c.new[k])
     return [c.scenes[k].mesh_index(i) for i in range(first, len(c.scenes[k].meshes))]
+
+
+# ------------------------------------------------------------------ applying a step to a HikariRenderer
+def add(r, name: str, k: int, stream=None) -> list:
+    """Step k's hk_add_meshes on `r`: the slices it returns."""
+    return r.add_meshes(case(name).new[k], stream=stream)
+
+
+def spawn(r, name: str, k: int, stream=None):
+    """Step k's hk_set_instances on `r`, after its add."""
+    c = case(name)
+    scene = c.scenes[k]
+    r.set_instances(scene, previous=c.previous[k], local_aabbs=local_aabbs(scene), stream=stream)
+
+
+def added_so_far(name: str, k: int) -> list:
+    """The slices of every mesh that steps 1..k added: registered on the device, instanced or not."""
+    return [s for j in range(1, k + 1) for s in new_slices(name, j)]

@@ -437,3 +437,16 @@ def slices(name: str, k: int) -> list:
 
 def local_aabbs(scene) -> np.ndarray:
     return mc.local_aabbs(scene)
+
+
+# ------------------------------------------------------------------ applying a step to a HikariRenderer
+def step(r, name: str, k: int, stream=None) -> list:
+    """Step k's hk_set_meshes on `r`: the slices it returns."""
+    c = case(name)
+    scene = c.scenes[k]
+    return r.set_meshes(scene, entries(name, k), previous=c.previous[k], local_aabbs=local_aabbs(scene), stream=stream)
+
+
+def host_slices(name: str, k: int) -> list:
+    """slices(name, k) as tuples of Python ints, as HikariRenderer.set_meshes returns them."""
+    return [tuple(int(x) for x in s) for s in slices(name, k)]

@@ -268,12 +268,13 @@ def assert_instance_update_matches_host(r, desc, skip_empty=False):
     # TLAS: identical except that the device copy carries the instance box in each leaf
     h = host_scene_array(desc, 5, NODE_DT)
     g = r.scene_array(5, NODE_DT, len(h))
-    assert np.array_equal(h["entry"], g["entry"]) and np.array_equal(h["exit"], g["exit"])
+    assert np.array_equal(h["entry"], g["entry"]) and np.array_equal(h["exit"], g["exit"]), "array 5: links differ"
     inner = h["entry"] < 0x80000000
-    assert h[inner].tobytes() == g[inner].tobytes()
+    assert h[inner].tobytes() == g[inner].tobytes(), "array 5: inner nodes differ"
     inst = np.frombuffer(host_scene_array(desc, 4, inst_dt).tobytes(), np.float32).reshape(-1, 44)
     leaf_ids = h["entry"][~inner] - 0x80000000
-    assert np.array_equal(g["min"][~inner], inst[leaf_ids, 0:3]) and np.array_equal(g["max"][~inner], inst[leaf_ids, 4:7])
+    assert (np.array_equal(g["min"][~inner], inst[leaf_ids, 0:3])
+            and np.array_equal(g["max"][~inner], inst[leaf_ids, 4:7])), "array 5: leaf boxes differ"
 
 
 def assert_rebuild_bitwise(r, desc):
@@ -285,4 +286,5 @@ def assert_rebuild_bitwise(r, desc):
     leaf = h["entry"] >= 0x80000000
     inst = np.frombuffer(host_scene_array(desc, 4, np.dtype((np.void, 176))).tobytes(), np.float32).reshape(-1, 44)
     ids = h["entry"][leaf] - 0x80000000
-    assert g["min"][leaf].tobytes() == inst[ids, 0:3].tobytes() and g["max"][leaf].tobytes() == inst[ids, 4:7].tobytes()
+    assert (g["min"][leaf].tobytes() == inst[ids, 0:3].tobytes()
+            and g["max"][leaf].tobytes() == inst[ids, 4:7].tobytes()), "array 5: leaf boxes differ"

@@ -228,3 +228,17 @@ def posed(name: str, k: int = 0):
         s = c.scene0.posed(c.poses[k], c.keep_normals)
         c._posed[k] = (s, s.build())
     return c._posed[k]
+
+
+# ------------------------------------------------------------------ the caller's boxes
+WRONG_BOX = np.array([9.0, -7.0, 5.0, 123.0, 0.5, 77.0], np.float32)
+
+
+def caller_aabbs(scene, posed_meshes) -> np.ndarray:
+    """mesh_cases.local_aabbs of the scene as given (the bind pose), with WRONG_BOX in the rows the library derives:
+    hk_skin_meshes ignores the caller's box of a posed mesh's instances."""
+    a = mc.local_aabbs(scene)
+    for i, (mesh, _, _) in enumerate(scene.instances):
+        if mesh in posed_meshes:
+            a[i] = WRONG_BOX
+    return a

@@ -28,19 +28,16 @@ The branch of csrc/hk_dynamic.hip each case exists for:
   neg_zero                       min / max of zeros of both signs, in k_update_instances and in the box joins
   deep_lds_edge .. too_deep      `levels`, the TLAS part of the G-buffer walk's stack bound: 16, 17, 64 and 65
   singular                       the singular flag
+The shared checks (arrays, frames, planes, rays, stream, raw calls) are tests/scene_edits.py's.
 """
-import ctypes
-
 import numpy as np
 import pytest
 
 import dynamic_cases as dc
-from parity import (RACY, assert_rebuild_bitwise, canon_plane, compare_frame, hip_runtime, mismatch_report, passes,
-                    renderer)
+from parity import assert_rebuild_bitwise, renderer
+from scene_edits import DEPTH_SIZE, EditFrames, assert_planes, caller_stream, gbuffer_planes
 
 pytestmark = pytest.mark.gpu
-
-DEPTH_SIZE = (64, 48)
 
 
 def _update(r, scene, stream=None):
@@ -77,42 +74,13 @@ def test_frames_after_rebuild_match_oracle(name):
     test_ladder_instance_update_matches_host_rebuild renders them (the oracle sees scene0, then scene1; one thread,
     spatial reuse off, the racy scatter targets within their tolerance), and the ray counters: what is derived from
     the rebuilt TLAS (leaf boxes, wide layout, collapsed walk nodes) and from the rebuilt alias and emissive tables."""
-    from hikari_amd import HikariSettings, Upscale, frame_inputs, load_noise
-    from oracle import Oracle
     scene0, scene1 = dc.case(name)
     d1 = dc.built1(name)
-    cam, lights = dc.camera_for(name)
-    w, h = dc.FRAME_SIZE
-    r = renderer(scene0, (w, h))
-    _update(r, scene1)
-    assert_rebuild_bitwise(r, d1)
-    st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=False)
-    o = Oracle(scene0.desc, load_noise(), w, h, 1.0, threads=1)
-    o.set_scene(d1)
-    s = st.to_c()
-    errors = []
-    for f in range(2):
-        fi = frame_inputs(f, cam, lights, w, h)
-        for x in (r, o):
-            passes(x, s, fi)
-        compare_frame(r, o, f, errors, racy=RACY)
-    assert not errors, "\n".join(errors[:10])
-    assert r.counters() == o.counters()
-    depth = canon_plane(11, o.output(11)).view(np.float32).reshape(h, w, 4)[..., 3]
-    assert (depth > 0).mean() > 0.2  # the view sees the instances
-    o.close()
-    r.close()
-
-
-def _gbuffer_planes(x, fi):
-    x.render_gbuffer(fi)
-    return [canon_plane(oid, x.output(oid)) for oid in (11, 12, 13, 14)]
-
-
-def _assert_planes(got, want, label):
-    for k, (a, b) in enumerate(zip(got, want)):
-        m = mismatch_report(a, b, f"{label}: output {11 + k}")
-        assert not m, m
+    with EditFrames(scene0, dc.camera_for(name), dc.FRAME_SIZE, floor=0.2) as fr:
+        _update(fr.r, scene1)
+        assert_rebuild_bitwise(fr.r, d1)
+        fr.set_scene(d1)
+        fr.frames(2)
 
 
 @pytest.mark.parametrize("name", ["deep_lds_edge", "deep_over_lds", "deep_at_limit"])
@@ -128,13 +96,13 @@ def test_tlas_deepened_by_an_update(name):
     w, h = DEPTH_SIZE
     fi = frame_inputs(0, cam, lights, w, h)
     o = Oracle(d1, load_noise(), w, h, 1.0)
-    want = _gbuffer_planes(o, fi)
+    want = gbuffer_planes(o, fi)
     assert (want[0].view(np.float32).reshape(h, w, 4)[..., 3] > 0).mean() > 0.005  # some of them are in view
     for opts in ({}, {"gbuffer_stack_full": 1}, {"gbuffer_deep": 1}):
         r = renderer(scene0, (w, h), options=opts)
         _update(r, scene1)
         assert_rebuild_bitwise(r, d1)
-        _assert_planes(_gbuffer_planes(r, fi), want, f"{name} {opts}")
+        assert_planes(gbuffer_planes(r, fi), want, f"{name} {opts}")
         r.close()
     o.close()
 
@@ -163,9 +131,9 @@ def test_update_to_a_tlas_too_deep_for_the_gbuffer_walk():
     _update(r, scene0)
     assert_rebuild_bitwise(r, scene0.desc)
     o = Oracle(scene0.desc, load_noise(), w, h, 1.0)
-    want = _gbuffer_planes(o, fi)
+    want = gbuffer_planes(o, fi)
     assert (want[0].view(np.float32).reshape(h, w, 4)[..., 3] > 0).mean() > 0.1
-    _assert_planes(_gbuffer_planes(r, fi), want, "back on scene0")
+    assert_planes(gbuffer_planes(r, fi), want, "back on scene0")
     o.close()
     r.close()
 
@@ -185,9 +153,9 @@ def test_singular_transform_is_refused_and_the_context_stays_usable():
     assert_rebuild_bitwise(r, scene0.desc)
     fi = frame_inputs(0, cam, lights, w, h)
     o = Oracle(scene0.desc, load_noise(), w, h, 1.0)
-    want = _gbuffer_planes(o, fi)
+    want = gbuffer_planes(o, fi)
     assert (want[0].view(np.float32).reshape(h, w, 4)[..., 3] > 0).mean() > 0.1
-    _assert_planes(_gbuffer_planes(r, fi), want, "after the refused update")
+    assert_planes(gbuffer_planes(r, fi), want, "after the refused update")
     o.close()
     r.close()
 
@@ -206,20 +174,15 @@ def test_one_context_several_scenes():
 
 
 def test_update_on_a_caller_stream():
-    """tlas_1281 with update_instances(..., stream=s) on a stream of the caller's.  hk_update_instances is documented to
-    wait for its stream once (the singular check), so the rebuilt arrays are complete when it returns, and
-    hk_read_scene_array, which synchronises only the context's own stream before a blocking copy, reads them whole;
-    the test synchronises s first all the same.  The stream is created in the HIP runtime the library loads
-    (parity.hip_runtime): a stream of another runtime copy in the process is not a handle the library can take, and
-    torch.cuda.current_stream().cuda_stream, which bench.py passes, is handle 0, the context's own stream that every
-    other test here runs on."""
+    """tlas_1281 with update_instances(..., stream=s) on a stream of the caller's (scene_edits.caller_stream).
+    hk_update_instances is documented to wait for its stream once (the singular check), so the rebuilt arrays are
+    complete when it returns, and hk_read_scene_array, which synchronises only the context's own stream before a
+    blocking copy, reads them whole; the test synchronises s first all the same.  torch.cuda.current_stream().cuda_stream,
+    which bench.py passes, is handle 0, the context's own stream that every other test here runs on."""
     scene0, scene1 = dc.case("tlas_1281")
     r = renderer(scene0)
-    hip = hip_runtime()
-    s = ctypes.c_void_p()
-    assert hip.hipStreamCreate(ctypes.byref(s)) == 0
-    _update(r, scene1, s)
-    assert hip.hipStreamSynchronize(s) == 0
-    assert_rebuild_bitwise(r, dc.built1("tlas_1281"))
-    r.close()
-    assert hip.hipStreamDestroy(s) == 0
+    with caller_stream() as (s, sync):
+        _update(r, scene1, s)
+        sync()
+        assert_rebuild_bitwise(r, dc.built1("tlas_1281"))
+        r.close()

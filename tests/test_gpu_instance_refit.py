@@ -18,22 +18,20 @@ What each case exists for in csrc/hk_dynamic.hip:
   swapped, coincident          the stalest tree; every shape box equal
   neg_zero, unchanged          zeros of both signs under an unordered fold; the boxes the tree was built from
   moving                       frames across the call: previous models, motion vectors
+The shared checks (arrays, frames, planes, rays, stream, raw calls) are tests/scene_edits.py's.
 """
 import copy
-import ctypes
 
 import numpy as np
 import pytest
 
 import dynamic_cases as dc
 import instance_refit_cases as ic
-from parity import (NODE_DT, RACY, assert_rebuild_bitwise, canon_plane, compare_frame, hip_runtime, host_scene_array,
-                    mismatch_report, passes, renderer)
-from test_gpu_mesh_update import assert_mesh_rebuild_bitwise
+from parity import NODE_DT, assert_rebuild_bitwise, host_scene_array, renderer
+from scene_edits import (EditFrames, assert_mesh_arrays, assert_planes, assert_scene_is, caller_stream, gbuffer_planes,
+                         models_and_aabbs, ptr, raw_call)
 
 pytestmark = pytest.mark.gpu
-
-MATERIAL_DT = np.dtype((np.void, 80))
 
 
 def _refit(r, scene, stream=None, refit=True):
@@ -43,17 +41,6 @@ def _refit(r, scene, stream=None, refit=True):
 def _expect(desc0, scene1):
     from hikari_amd import Scene
     return Scene.refitted_instances(desc0, scene1)
-
-
-def assert_scene_is(r, desc):
-    """All nine arrays and their counts: vertices, primitives and asset nodes (leaves with their triangle's box),
-    materials, and what the instance calls derive (alias table, instances, TLAS with the instance boxes in its leaves,
-    light BVH, emissives)."""
-    from parity import SCENE_ARRAYS
-    assert r.scene_counts() == [getattr(desc, a).count for a in SCENE_ARRAYS]
-    assert_mesh_rebuild_bitwise(r, desc)
-    h = host_scene_array(desc, 6, MATERIAL_DT)
-    assert h.tobytes() == r.scene_array(6, MATERIAL_DT, len(h)).tobytes(), "array 6 differs"
 
 
 # ------------------------------------------------------------------ arrays
@@ -117,12 +104,11 @@ def test_refit_after_set_instances():
     """instance_set_cases' spawn_pooled: the set hk_set_instances spawned into, then moved by a refit: the trees of the
     set's build are kept, over its counts."""
     import instance_set_cases as sc
-    from test_gpu_instance_set import _set, assert_set_matches_host
     name = "spawn_pooled"
     c = sc.case(name)
     r = renderer(c.scenes[0])
-    _set(r, name, 1)
-    assert_set_matches_host(r, sc.built(name, 1), c.materials)
+    sc.apply(r, name, 1)
+    assert_scene_is(r, sc.built(name, 1), meshes=False, materials=c.materials)
     moved = _moved_copy(c.scenes[1], 1)
     r.update_instances(moved.instance_models(), sc.local_aabbs(moved), refit=True)
     want = _expect(sc.built(name, 1), moved)
@@ -135,19 +121,18 @@ def test_refit_after_add_meshes_and_a_spawn():
     """mesh_add_cases' then_update: a mesh appended by hk_add_meshes and spawned by hk_set_instances, then every
     instance moved by a refit."""
     import mesh_add_cases as ac
-    from test_gpu_mesh_add import _add, _added_so_far, _set, assert_mesh_arrays
     name = "then_update"
     c = ac.case(name)
     r = renderer(c.scenes[0])
     last = len(c.scenes) - 1
     for k in list(ac.steps(name))[1:]:
-        _add(r, name, k)
-        _set(r, name, k)
+        ac.add(r, name, k)
+        ac.spawn(r, name, k)
     moved = _moved_copy(c.scenes[last], 2)
     r.update_instances(moved.instance_models(), ac.local_aabbs(moved), refit=True)
     want = _expect(ac.built(name, last), moved)
     assert_rebuild_bitwise(r, want)
-    assert_mesh_arrays(r, want, _added_so_far(name, last))
+    assert_mesh_arrays(r, want, ac.added_so_far(name, last))
     r.close()
 
 
@@ -172,13 +157,12 @@ def test_refit_meshes_all_is_the_composition():
 def test_skin_meshes_refit_all_is_the_composition():
     import skin_cases as sc
     from hikari_amd import Scene
-    from test_gpu_skin import caller_aabbs
     name = sc.FRAME_CASES[0]
     c = sc.case(name)
     r = renderer(c.scene0)
     r.set_mesh_skins(c.scene0, c.skinned, c.keep_normals)
     pose = c.poses[0]
-    r.skin_meshes(c.scene0, pose, local_aabbs=caller_aabbs(c.scene0, set(pose)), refit="all")
+    r.skin_meshes(c.scene0, pose, local_aabbs=sc.caller_aabbs(c.scene0, set(pose)), refit="all")
     blas = Scene.refitted(c.scene0.desc, sc.posed(name, 0)[0], list(pose))
     assert_scene_is(r, Scene.refitted_instances(c.scene0.desc, blas))
     r.close()
@@ -190,35 +174,18 @@ def _frames(name, options=None, wavefront=False, before=0):
     off, the racy scatter targets within their tolerance; the oracle takes the refitted desc by set_scene, which keeps
     its previous models as the context keeps its own), and the ray counters: what is derived from the refit TLAS (leaf
     boxes, wide layout, collapsed walk nodes) and the refit light BVH is what the frames walk."""
-    from hikari_amd import HikariSettings, Upscale, frame_inputs, load_noise
-    from oracle import Oracle
     scene0, scene1 = ic.case(name)
     d1 = ic.refitted(name)
-    cam, lights = ic.camera_for(name)
-    w, h = ic.FRAME_SIZE
-    r = renderer(scene0, (w, h), options=options, wavefront=wavefront)
-    o = Oracle(scene0.desc, load_noise(), w, h, 1.0, threads=1)
-    s = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=False).to_c()
-    errors = []
-    for f in range(before + 2):
-        if f == before:
-            _refit(r, scene1)
-            assert_scene_is(r, d1)
-            o.set_scene(d1)
-        fi = frame_inputs(f, cam, lights, w, h)
-        for x in (r, o):
-            passes(x, s, fi)
-        compare_frame(r, o, f, errors, racy=RACY)
-        if before and f == before:  # the frame after the call: the instances moved on screen since the one before
-            depth = canon_plane(11, o.output(11)).view(np.float32).reshape(h, w, 4)[..., 3]
-            velocity = canon_plane(15, o.output(15)).view(np.float32).reshape(h, w, 4)[..., :2]
+    with EditFrames(scene0, ic.camera_for(name), ic.FRAME_SIZE, floor=0.02, options=options, wavefront=wavefront) as fr:
+        fr.frames(before)
+        _refit(fr.r, scene1)
+        assert_scene_is(fr.r, d1)
+        fr.set_scene(d1)
+        fr.frames(1)
+        if before:  # the frame after the call: the instances moved on screen since the one before
+            depth, velocity = fr.oracle_plane(11)[..., 3], fr.oracle_plane(15)[..., :2]
             assert (np.abs(velocity[depth > 0]) > 1e-4).any()
-    assert not errors, "\n".join(errors[:10])
-    assert r.counters() == o.counters()
-    depth = canon_plane(11, o.output(11)).view(np.float32).reshape(h, w, 4)[..., 3]
-    assert (depth > 0).mean() > 0.02  # the view sees the instances
-    o.close()
-    r.close()
+        fr.frames(1)
 
 
 @pytest.mark.parametrize("name", ic.FRAME_CASES)
@@ -242,11 +209,6 @@ def test_frames_with_the_wavefront_pass():
     _frames(ic.VARIANT_CASE, wavefront=True)
 
 
-def _gbuffer_planes(x, fi):
-    x.render_gbuffer(fi)
-    return [canon_plane(oid, x.output(oid)) for oid in (11, 12, 13, 14)]
-
-
 def test_the_deep_chain_is_walked_at_its_own_depth():
     """deep: the kept TLAS is a chain whose stack bound is 64, the models a rebuild would give a shallow tree for.  The
     G-buffer planes equal the oracle's on the refitted desc in the default context and with gbuffer_stack_full and
@@ -259,15 +221,13 @@ def test_the_deep_chain_is_walked_at_its_own_depth():
     w, h = ic.FRAME_SIZE
     fi = frame_inputs(0, cam, lights, w, h)
     o = Oracle(d1, load_noise(), w, h, 1.0)
-    want = _gbuffer_planes(o, fi)
+    want = gbuffer_planes(o, fi)
     assert (want[0].view(np.float32).reshape(h, w, 4)[..., 3] > 0).mean() > 0.02
     for opts in ({}, {"gbuffer_stack_full": 1}, {"gbuffer_deep": 1}):
         r = renderer(scene0, (w, h), options=opts)
         _refit(r, scene1)
         assert_scene_is(r, d1)
-        for k, (a, b) in enumerate(zip(_gbuffer_planes(r, fi), want)):
-            m = mismatch_report(a, b, f"deep {opts}: output {11 + k}")
-            assert not m, m
+        assert_planes(gbuffer_planes(r, fi), want, f"deep {opts}")
         r.close()
     o.close()
 
@@ -297,11 +257,8 @@ def test_the_stack_bound_is_unchanged_by_the_call():
 
 # ------------------------------------------------------------------ refusals
 def _raw(r, scene, count=None, models=True, aabbs=True):
-    m = np.ascontiguousarray(scene.instance_models(), np.float32)
-    a = np.ascontiguousarray(scene.instance_local_aabbs(), np.float32)
-    rc_ = r._L.hk_refit_instances(r.ctx, m.ctypes.data if models else None, a.ctypes.data if aabbs else None,
-                                  len(m) if count is None else count, None)
-    return rc_, r._L.hk_last_error(r.ctx).decode()
+    m, a = models_and_aabbs(scene, scene.instance_local_aabbs())
+    return raw_call(r, "hk_refit_instances", ptr(m, models), ptr(a, aabbs), len(m) if count is None else count, None)
 
 
 def test_refusals_leave_the_context_usable():
@@ -340,14 +297,11 @@ def test_refit_on_a_caller_stream():
     name = "many_large"
     scene0, scene1 = ic.case(name)
     r = renderer(scene0)
-    hip = hip_runtime()
-    s = ctypes.c_void_p()
-    assert hip.hipStreamCreate(ctypes.byref(s)) == 0
-    _refit(r, scene1, stream=s)
-    assert hip.hipStreamSynchronize(s) == 0
-    assert_scene_is(r, ic.refitted(name))
-    r.close()
-    assert hip.hipStreamDestroy(s) == 0
+    with caller_stream() as (s, sync):
+        _refit(r, scene1, stream=s)
+        sync()
+        assert_scene_is(r, ic.refitted(name))
+        r.close()
 
 
 def test_plugin_forwards_refit():

@@ -2,6 +2,7 @@
 tests/test_instance_set_cases.py, without a GPU) uploaded as step 0 and set to each later step; the rebuilt alias table,
 instances, TLAS, light BVH and emissives compared byte for byte with the host builder's, the counts with its desc's,
 frames, G-buffers and counters against the CPU oracle on the host-built scene.
+The shared checks (arrays, frames, planes, rays, stream, raw calls) are tests/scene_edits.py's.
 
 The branch of csrc/hk_dynamic.hip or csrc/hk_runtime.hip each case exists for is listed in instance_set_cases.py."""
 import copy
@@ -12,29 +13,11 @@ import numpy as np
 import pytest
 
 import instance_set_cases as ic
-from parity import (RACY, assert_rebuild_bitwise, canon_plane, compare_frame, hip_runtime, host_scene_array,
-                    mismatch_report, passes, renderer)
+from parity import hip_runtime, renderer
+from scene_edits import (MOTION_PLANES, EditFrames, assert_mesh_rebuild_bitwise, assert_planes, assert_scene_is,
+                         gbuffer_planes, raw_call)
 
 pytestmark = pytest.mark.gpu
-
-MATERIAL_DT = np.dtype((np.void, 80))
-
-
-def _set(r, name, k, **kw):
-    c = ic.case(name)
-    scene = c.scenes[k]
-    kw.setdefault("local_aabbs", ic.local_aabbs(scene))
-    r.set_instances(scene, previous=c.previous[k], materials=c.materials, **kw)
-
-
-def assert_set_matches_host(r, desc, materials=False):
-    """The five rebuilt arrays byte for byte the host build's (an empty host array is not read back: its count must be
-    zero), the nine counts the desc's, and the materials where they were sent."""
-    assert r.scene_counts() == ic.desc_counts(desc)
-    assert_rebuild_bitwise(r, desc)
-    if materials:
-        h = host_scene_array(desc, 6, MATERIAL_DT)
-        assert h.tobytes() == r.scene_array(6, MATERIAL_DT, len(h)).tobytes(), "array 6 differs"
 
 
 @pytest.mark.parametrize("name", list(ic.CASES))
@@ -45,8 +28,8 @@ def test_rebuilt_arrays_match_host_builder(name):
     r = renderer(c.scenes[0])
     assert r.scene_counts() == ic.desc_counts(c.scenes[0].desc)
     for k in list(ic.steps(name))[1:]:
-        _set(r, name, k)
-        assert_set_matches_host(r, ic.built(name, k), c.materials)
+        ic.apply(r, name, k)
+        assert_scene_is(r, ic.built(name, k), meshes=False, materials=c.materials)
     r.close()
 
 
@@ -54,11 +37,11 @@ def test_one_context_another_upload_resets_the_capacity():
     """from_one_129 grows every array; uploading to_one's scene and setting its step on the same context starts from
     that upload's sizes."""
     r = renderer(ic.case("from_one_129").scenes[0])
-    _set(r, "from_one_129", 1)
-    assert_set_matches_host(r, ic.built("from_one_129", 1))
+    ic.apply(r, "from_one_129", 1)
+    assert_scene_is(r, ic.built("from_one_129", 1), meshes=False, materials=False)
     r.upload_scene(ic.case("to_one").scenes[0])
-    _set(r, "to_one", 1)
-    assert_set_matches_host(r, ic.built("to_one", 1))
+    ic.apply(r, "to_one", 1)
+    assert_scene_is(r, ic.built("to_one", 1), meshes=False, materials=False)
     r.close()
 
 
@@ -68,32 +51,14 @@ def _frames(name, options=None):
     desc; one thread, spatial reuse off): the racy scatter targets within their tolerance, everything else bit-exact,
     and equal ray counters.  No survivor moves in these cases, so the oracle's restart of the previous models on a
     changed count and the mapping agree."""
-    from hikari_amd import HikariSettings, Upscale, frame_inputs, load_noise
-    from oracle import Oracle
     c = ic.case(name)
-    cam, lights = ic.camera_for(name)
-    w, h = ic.FRAME_SIZE
-    r = renderer(c.scenes[0], (w, h), options=options)
-    o = Oracle(c.scenes[0].desc, load_noise(), w, h, 1.0, threads=1, textures=c.scenes[0].textures)
-    s = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=False).to_c()
-    errors, f = [], 0
-    for k in ic.steps(name):
-        if k:
-            _set(r, name, k)
-            assert_set_matches_host(r, ic.built(name, k), c.materials)
-            o.set_scene(ic.built(name, k))
-        for _ in range(2):
-            fi = frame_inputs(f, cam, lights, w, h)
-            for x in (r, o):
-                passes(x, s, fi)
-            compare_frame(r, o, f, errors, racy=RACY)
-            f += 1
-        assert not errors, f"step {k}\n" + "\n".join(errors[:10])
-    assert r.counters() == o.counters()
-    depth = canon_plane(11, o.output(11)).view(np.float32).reshape(h, w, 4)[..., 3]
-    assert (depth > 0).mean() > 0.05  # the view covers some of the scene
-    o.close()
-    r.close()
+    with EditFrames(c.scenes[0], ic.camera_for(name), ic.FRAME_SIZE, floor=0.05, options=options) as fr:
+        for k in ic.steps(name):
+            if k:
+                ic.apply(fr.r, name, k)
+                assert_scene_is(fr.r, ic.built(name, k), meshes=False, materials=c.materials)
+                fr.set_scene(ic.built(name, k))
+            fr.frames(2, f"step {k}")
 
 
 @pytest.mark.parametrize("name", [n for n in ic.FRAME_CASES if n not in ("stage_edge", "deeper_blas")])
@@ -112,11 +77,6 @@ def test_frames_across_the_lds_stack_levels(options):
 
 
 # ------------------------------------------------------------------ previous models
-def _gbuffer_planes(x, fi):
-    x.render_gbuffer(fi)
-    return [canon_plane(oid, x.output(oid)) for oid in (11, 12, 13, 14, 15)]
-
-
 def _moved_copy(scene, seed):
     """The scene's pool and instance list with every instance moved a little (seeded)."""
     rng = np.random.default_rng(seed)
@@ -149,19 +109,16 @@ def test_previous_models_follow_the_mapping(name):
     w, h = ic.FRAME_SIZE
     fis = [frame_inputs(f, cam, lights, w, h) for f in (0, 1)]
     o = Oracle(p.build(), load_noise(), w, h, 1.0)
-    _gbuffer_planes(o, fis[0])
+    gbuffer_planes(o, fis[0], MOTION_PLANES)
     o.set_scene(new.build())
-    want = _gbuffer_planes(o, fis[1])
+    want = gbuffer_planes(o, fis[1], MOTION_PLANES)
     velocity = want[4].view(np.float32).reshape(h, w, 4)[..., :2]
     assert (velocity != 0).any()  # a moving survivor is in view
     r = renderer(old, (w, h))
-    _gbuffer_planes(r, fis[0])
+    gbuffer_planes(r, fis[0], MOTION_PLANES)
     r.set_instances(new, previous=previous, local_aabbs=ic.local_aabbs(new))
-    assert_set_matches_host(r, new.desc)
-    got = _gbuffer_planes(r, fis[1])
-    for k, (a, b) in enumerate(zip(got, want)):
-        m = mismatch_report(a, b, f"{name}: output {11 + k}")
-        assert not m, m
+    assert_scene_is(r, new.desc, meshes=False, materials=False)
+    assert_planes(gbuffer_planes(r, fis[1], MOTION_PLANES), want, name)
     o.close()
     r.close()
 
@@ -170,14 +127,13 @@ def test_previous_models_follow_the_mapping(name):
 def test_updates_after_a_set_take_the_current_set():
     """After spawn_pooled's set: hk_update_instances with the new count, and hk_update_meshes on the mesh the set
     change instanced first; both leave the host builder's arrays."""
-    from test_gpu_mesh_update import assert_mesh_rebuild_bitwise
     name = "spawn_pooled"
     c = ic.case(name)
     r = renderer(c.scenes[0])
-    _set(r, name, 1)
+    ic.apply(r, name, 1)
     moved = _moved_copy(c.scenes[1], [ic.SEED, 78])
     r.update_instances(moved.instance_models(), ic.local_aabbs(moved))
-    assert_set_matches_host(r, moved.build())
+    assert_scene_is(r, moved.build(), meshes=False, materials=False)
     with pytest.raises(Exception, match="every instance"):
         r.update_instances(c.scenes[0].instance_models(), ic.local_aabbs(c.scenes[0]))  # the count before the set
     deformed = copy.copy(moved)
@@ -201,9 +157,8 @@ def _raw_set(r, scene, entries, count=None, models=True, aabbs=True, set_=True):
     m = np.ascontiguousarray(np.tile(np.eye(4, dtype=np.float32).reshape(1, 16), (max(1, n), 1)))
     a = np.ascontiguousarray(np.tile(np.array([[0, 0, 0, 0.1, 0.0, 0.1]], np.float32), (max(1, n), 1)))
     arr = (_abi.hk_instance_desc * max(1, n))(*entries)
-    rc = r._L.hk_set_instances(r.ctx, arr if set_ else None, m.ctypes.data if models else None,
-                               a.ctypes.data if aabbs else None, n if count is None else count, None, None)
-    return rc, r._L.hk_last_error(r.ctx).decode()
+    return raw_call(r, "hk_set_instances", arr if set_ else None, m.ctypes.data if models else None,
+                    a.ctypes.data if aabbs else None, n if count is None else count, None, None)
 
 
 def test_refusals_leave_the_context_usable():
@@ -246,9 +201,9 @@ def test_refusals_leave_the_context_usable():
     for label, kw, text in refused:
         rc, msg = _raw_set(r, scene, **kw)
         assert rc == _abi.HK_ERR_INVALID and text in msg, (label, rc, msg)
-        assert_set_matches_host(r, scene.desc)
-    _set(r, name, 1)
-    assert_set_matches_host(r, ic.built(name, 1))
+        assert_scene_is(r, scene.desc, meshes=False, materials=False)
+    ic.apply(r, name, 1)
+    assert_scene_is(r, ic.built(name, 1), meshes=False, materials=False)
     r.close()
 
 
@@ -260,11 +215,11 @@ def test_a_singular_model_fails_and_a_valid_set_repairs_it():
     models = c.scenes[1].instance_models().copy()
     models[2, 4:8] = 0.0  # a zero column
     with pytest.raises(HikariError, match="singular instance transform"):
-        _set(r, name, 1, models=models)
+        ic.apply(r, name, 1, models=models)
     assert r.scene_counts() == ic.desc_counts(ic.built(name, 1))  # the set is the new one
     # the same entities again: every instance maps to itself
     r.set_instances(c.scenes[1], previous=list(range(len(models))), local_aabbs=ic.local_aabbs(c.scenes[1]))
-    assert_set_matches_host(r, ic.built(name, 1))
+    assert_scene_is(r, ic.built(name, 1), meshes=False, materials=False)
     r.close()
 
 
@@ -286,7 +241,7 @@ def test_a_steady_toggle_allocates_nothing():
         return free.value
 
     def toggle():
-        _set(r, name, 1)
+        ic.apply(r, name, 1)
         r.set_instances(c.scenes[0], previous=back, local_aabbs=ic.local_aabbs(c.scenes[0]))
 
     toggle()
@@ -300,7 +255,7 @@ def test_a_steady_toggle_allocates_nothing():
         if windows[-1] == 0:
             break
     assert 0 in windows, windows
-    assert_set_matches_host(r, c.scenes[0].desc)
+    assert_scene_is(r, c.scenes[0].desc, meshes=False, materials=False)
     r.close()
 
 
@@ -312,18 +267,18 @@ def test_a_set_past_the_capacity_grows_by_half_and_stays():
     r = renderer(c.scenes[0])
     before = r.scene_capacity()
     assert before == [max(1, n) for n in ic.desc_counts(c.scenes[0].desc)]
-    _set(r, name, 1)
+    ic.apply(r, name, 1)
     counts, after = r.scene_counts(), r.scene_capacity()
     for i in (3, 4, 5, 7, 8):
         assert counts[i] > before[i], (i, counts, before)  # (the case: every one of them has to grow)
         assert after[i] == max(counts[i], before[i] + before[i] // 2), (i, counts, before, after)
     for i in (0, 1, 2, 6):
         assert after[i] == before[i], (i, before, after)
-    _set(r, name, 2)
+    ic.apply(r, name, 2)
     assert r.scene_capacity() == after
-    _set(r, name, 1)
+    ic.apply(r, name, 1)
     assert r.scene_capacity() == after
-    assert_set_matches_host(r, ic.built(name, 1))
+    assert_scene_is(r, ic.built(name, 1), meshes=False, materials=False)
     r.close()
 
 
@@ -333,5 +288,5 @@ def test_plugin_forwards_set_instances():
     c = ic.case(name)
     p = HikariPlugin(c.scenes[0])
     p.set_instances(c.scenes[1], previous=c.previous[1])
-    assert_set_matches_host(p.renderer, ic.built(name, 1))
+    assert_scene_is(p.renderer, ic.built(name, 1), meshes=False, materials=False)
     p.renderer.close()

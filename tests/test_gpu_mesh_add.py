@@ -3,121 +3,44 @@ tests/test_mesh_add_cases.py, without a GPU) uploaded as step 0; each step's mes
 with hk_set_instances.  The appended vertices and primitives byte for byte the host builder's, the BLAS with its
 topology, the earlier slices and arrays 3-8 untouched by the add, everything the instance rebuild derives afterwards;
 frames, G-buffers, traced rays and counters against the CPU oracle on the host-built scenes.
+The shared checks (arrays, frames, planes, rays, stream, raw calls) are tests/scene_edits.py's.
 
 The branch of csrc/hk_dynamic.hip or csrc/hk_runtime.hip each case exists for is listed in mesh_add_cases.py."""
-import ctypes
-
 import numpy as np
 import pytest
 
 import instance_set_cases as ic
 import mesh_add_cases as ac
-import mesh_cases as mc
-from parity import (NODE_DT, RACY, assert_rebuild_bitwise, canon_plane, compare_frame, hip_runtime, host_scene_array,
-                    mismatch_report, passes, renderer)
+from parity import assert_rebuild_bitwise, renderer
+from scene_edits import (DEPTH_SIZE, ELEM_DT, EditFrames, assert_mesh_arrays, assert_planes, assert_traces_equal_fresh,
+                         caller_stream, device_arrays, gbuffer_planes, raw_call)
 
 pytestmark = pytest.mark.gpu
-
-DEPTH_SIZE = (64, 48)
-VERTEX_DT, PRIM_DT = np.dtype((np.void, 32)), np.dtype((np.void, 48))
-ELEM_DT = [VERTEX_DT, PRIM_DT, NODE_DT, np.dtype((np.void, 8)), np.dtype((np.void, 176)), NODE_DT,
-           np.dtype((np.void, 80)), NODE_DT, np.dtype((np.void, 64))]
-
-
-def _add(r, name, k, stream=None):
-    return r.add_meshes(ac.case(name).new[k], stream=stream)
-
-
-def _set(r, name, k, stream=None):
-    c = ac.case(name)
-    scene = c.scenes[k]
-    r.set_instances(scene, previous=c.previous[k], local_aabbs=ac.local_aabbs(scene), stream=stream)
-
-
-def _added_so_far(name, k) -> list:
-    return [s for j in range(1, k + 1) for s in ac.new_slices(name, j)]
-
-
-# ---- the leaf boxes of the device's asset nodes, restated (as tests/test_gpu_mesh_update.py restates them):
-# k_fill_blas_leaves takes vmin(a, vmin(b, c)) and vmax(a, vmax(b, c)) of the triangle's corners with the device's
-# fminf / fmaxf, which order -0 below +0
-def _device_min(p):
-    m = p.min(axis=1)
-    zero, neg = m == 0.0, (p.view(np.uint32) == 0x80000000).any(axis=1)
-    m[zero & neg], m[zero & ~neg] = -0.0, 0.0
-    return m
-
-
-def _device_max(p):
-    m = p.max(axis=1)
-    zero, pos = m == 0.0, (p.view(np.uint32) == 0).any(axis=1)
-    m[zero & pos], m[zero & ~pos] = 0.0, -0.0
-    return m
-
-
-def test_device_min_max_restate_the_sign_of_zero():
-    p = np.array([[[0.0, -0.0, 1.0], [-0.0, -0.0, 2.0], [0.0, -0.0, 0.0]]], np.float32)
-    assert _device_min(p).view(np.uint32).tolist() == [[0x80000000, 0x80000000, 0]]
-    assert _device_max(p).view(np.uint32).tolist() == [[0, 0x80000000, 0x40000000]]
-
-
-def _expected_asset_nodes(desc, added):
-    """The host's asset nodes with the leaves of every instanced mesh and of every added mesh (`added`: their slices,
-    instanced or not) carrying their triangle's box; the leaves of a pooled mesh nobody registered stay empty."""
-    nodes = host_scene_array(desc, 2, NODE_DT).copy()
-    corners = np.ascontiguousarray(
-        np.frombuffer(host_scene_array(desc, 1, PRIM_DT).tobytes(), np.float32).reshape(-1, 3, 4)[:, :, :3])
-    for _, prim, n0, nc in set(mc.mesh_slices(desc)) | set(added):
-        part = nodes[n0: n0 + nc]
-        leaf = part["entry"] >= 0x80000000
-        tri = corners[prim + (part["entry"][leaf] - 0x80000000)]
-        part["min"][leaf], part["max"][leaf] = _device_min(tri), _device_max(tri)
-    return nodes
-
-
-def assert_mesh_arrays(r, desc, added):
-    """Arrays 0 and 1 byte for byte the host's; array 2: entry / exit everywhere, inner nodes whole, every leaf of an
-    instanced or added mesh the byte image of its triangle's box; counts 0-2 the host's."""
-    assert r.scene_counts()[:3] == ic.desc_counts(desc)[:3]
-    for idx, dt in ((0, VERTEX_DT), (1, PRIM_DT)):
-        h = host_scene_array(desc, idx, dt)
-        assert h.tobytes() == r.scene_array(idx, dt, len(h)).tobytes(), f"array {idx} differs"
-    want = _expected_asset_nodes(desc, added)
-    got = r.scene_array(2, NODE_DT, len(want))
-    assert np.array_equal(want["entry"], got["entry"]) and np.array_equal(want["exit"], got["exit"])
-    inner = want["entry"] < 0x80000000
-    assert want[inner].tobytes() == got[inner].tobytes()
-    assert want.tobytes() == got.tobytes()
-
-
-def _device_arrays(r, which):
-    counts = r.scene_counts()
-    return [r.scene_array(i, ELEM_DT[i], counts[i]).tobytes() if counts[i] else b"" for i in which]
 
 
 def _add_and_check(r, name, k):
     """Step k's hk_add_meshes alone: the returned slices are the host's, arrays 0-2 the host's for the pool with the
     new meshes, their earlier elements and arrays 3-8 byte for byte what the device held before, counts 3-8 too."""
     counts = r.scene_counts()
-    old_low, old_high = _device_arrays(r, range(3)), _device_arrays(r, range(3, 9))
-    slices = _add(r, name, k)
+    old_low, old_high = device_arrays(r, range(3)), device_arrays(r, range(3, 9))
+    slices = ac.add(r, name, k)
     assert slices == [tuple(int(x) for x in s) for s in ac.new_slices(name, k)]
     desc = ac.add_only(name, k).desc
     assert r.scene_counts() == ic.desc_counts(desc) and r.scene_counts()[3:] == counts[3:]
-    assert_mesh_arrays(r, desc, _added_so_far(name, k))
+    assert_mesh_arrays(r, desc, ac.added_so_far(name, k))
     for i, before in enumerate(old_low):
         now = r.scene_array(i, ELEM_DT[i], r.scene_counts()[i])
         assert now[:counts[i]].tobytes() == before, f"array {i}: an earlier slice changed"
-    assert _device_arrays(r, range(3, 9)) == old_high
+    assert device_arrays(r, range(3, 9)) == old_high
     assert_rebuild_bitwise(r, ac.built(name, k - 1))
 
 
 def _set_and_check(r, name, k, stream=None):
-    _set(r, name, k, stream)
+    ac.spawn(r, name, k, stream)
     desc = ac.built(name, k)
     assert r.scene_counts() == ic.desc_counts(desc)
     assert_rebuild_bitwise(r, desc)
-    assert_mesh_arrays(r, desc, _added_so_far(name, k))
+    assert_mesh_arrays(r, desc, ac.added_so_far(name, k))
 
 
 @pytest.mark.parametrize("name", list(ac.CASES))
@@ -135,7 +58,7 @@ def test_added_and_spawned_arrays_match_host_builder(name):
         desc = ac.built_update(name)
         assert r.scene_counts() == ic.desc_counts(desc)
         assert_rebuild_bitwise(r, desc)
-        assert_mesh_arrays(r, desc, _added_so_far(name, len(c.scenes) - 1))
+        assert_mesh_arrays(r, desc, ac.added_so_far(name, len(c.scenes) - 1))
     r.close()
 
 
@@ -156,7 +79,7 @@ def test_capacity_grows_keeps_and_resets():
     seen = [cap]
     for k in list(ac.steps(name))[1:]:
         before = r.scene_capacity()
-        _add(r, name, k)
+        ac.add(r, name, k)
         after, counts = r.scene_capacity(), r.scene_counts()
         assert all(n <= m for n, m in zip(counts, after))
         assert after[:3] == [m if n <= m else _grown(n, m) for n, m in zip(counts[:3], before[:3])]
@@ -179,40 +102,15 @@ def _frames(name, options=None, wavefront=False, after_add=False):
     """Per step: the add (after_add: then two 32 x 24 frames against the oracle still on the scene before, the picture
     being untouched), the set, and two frames against the oracle on the host-built scene (Oracle.set_scene; one thread,
     spatial reuse off, the racy scatter targets within their tolerance); equal ray counters at the end."""
-    from hikari_amd import HikariSettings, Upscale, frame_inputs, load_noise
-    from oracle import Oracle
-    c = ac.case(name)
-    cam, lights = ac.camera_for(name)
-    w, h = ac.FRAME_SIZE
-    r = renderer(c.scenes[0], (w, h), options=options, wavefront=wavefront)
-    o = Oracle(c.scenes[0].desc, load_noise(), w, h, 1.0, threads=1, textures=c.scenes[0].textures)
-    s = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=False).to_c()
-    errors, f = [], 0
-
-    def two_frames(label):
-        nonlocal f
-        for _ in range(2):
-            fi = frame_inputs(f, cam, lights, w, h)
-            for x in (r, o):
-                passes(x, s, fi)
-            compare_frame(r, o, f, errors, racy=RACY)
-            f += 1
-        assert not errors, f"{label}\n" + "\n".join(errors[:10])
-
-    for k in list(ac.steps(name))[1:]:
-        _add_and_check(r, name, k)
-        if after_add:
-            two_frames(f"step {k} after the add")
-        _set_and_check(r, name, k)
-        o.set_scene(ac.built(name, k))
-        two_frames(f"step {k} after the set")
-    assert r.counters() == o.counters()
-    depth = canon_plane(11, o.output(11)).view(np.float32).reshape(h, w, 4)[..., 3]
-    assert (depth > 0).mean() > 0.05  # the view covers some of the scene
-    lit = canon_plane(10, o.output(10)).view(np.float16).astype(np.float32)
-    assert np.isfinite(lit).all()
-    o.close()
-    r.close()
+    with EditFrames(ac.case(name).scenes[0], ac.camera_for(name), ac.FRAME_SIZE, floor=0.05, finite=True,
+                     options=options, wavefront=wavefront) as fr:
+        for k in list(ac.steps(name))[1:]:
+            _add_and_check(fr.r, name, k)
+            if after_add:
+                fr.frames(2, f"step {k} after the add")
+            _set_and_check(fr.r, name, k)
+            fr.set_scene(ac.built(name, k))
+            fr.frames(2, f"step {k} after the set")
 
 
 @pytest.mark.parametrize("name", [n for n in ac.FRAME_CASES if n != "stage_edge_add"])
@@ -237,17 +135,6 @@ def test_frames_with_the_wavefront_pass():
 
 
 # ------------------------------------------------------------------ stack bound
-def _gbuffer_planes(x, fi):
-    x.render_gbuffer(fi)
-    return [canon_plane(oid, x.output(oid)) for oid in (11, 12, 13, 14)]
-
-
-def _assert_planes(got, want, label):
-    for k, (a, b) in enumerate(zip(got, want)):
-        m = mismatch_report(a, b, f"{label}: output {11 + k}")
-        assert not m, m
-
-
 def test_stack_bound_moves_with_the_spawn_not_the_add():
     """deep_new: the G-buffer planes after the add equal the oracle's on the scene before (a deep mesh nobody carries
     leaves the bound alone), those after the spawn the oracle's on the new scene, whose bound is 17: in the default
@@ -261,18 +148,18 @@ def test_stack_bound_moves_with_the_spawn_not_the_add():
     w, h = DEPTH_SIZE
     fi = frame_inputs(0, cam, lights, w, h)
     o = Oracle(c.scenes[0].desc, load_noise(), w, h, 1.0)
-    before = _gbuffer_planes(o, fi)
+    before = gbuffer_planes(o, fi)
     o.set_scene(ac.built(name, 1))
-    after = _gbuffer_planes(o, fi)
+    after = gbuffer_planes(o, fi)
     assert any((a != b).any() for a, b in zip(before, after))  # the new mesh is in view
     o.close()
     for opts in ac.STACK_OPTIONS:
         r = renderer(c.scenes[0], (w, h), options=opts)
-        _assert_planes(_gbuffer_planes(r, fi), before, f"{opts} uploaded")
+        assert_planes(gbuffer_planes(r, fi), before, f"{opts} uploaded")
         _add_and_check(r, name, 1)
-        _assert_planes(_gbuffer_planes(r, fi), before, f"{opts} after the add")
+        assert_planes(gbuffer_planes(r, fi), before, f"{opts} after the add")
         _set_and_check(r, name, 1)
-        _assert_planes(_gbuffer_planes(r, fi), after, f"{opts} after the spawn")
+        assert_planes(gbuffer_planes(r, fi), after, f"{opts} after the spawn")
         r.close()
 
 
@@ -283,21 +170,11 @@ def test_traced_rays_after_add_and_spawn_equal_a_fresh_context():
     c = ac.case(name)
     final = c.scenes[1]
     ac.built(name, 1)
-    rng = np.random.default_rng(ac.SEED)
-    n = 256
-    org = rng.uniform([-1.5, 0.0, 1.0], [1.5, 2.0, 4.0], (n, 3))
-    d = rng.uniform([-1.5, 0.0, -0.5], [1.5, 2.0, 0.2], (n, 3)) - org
-    d /= np.linalg.norm(d, axis=1, keepdims=True)
-    rays = np.concatenate([org, d], axis=1).astype(np.float32)
-    early = np.where(rng.random(n) < 0.5, 0.0, 65535.0).astype(np.float32)
-    excl = rng.integers(0, len(final.instances) + 1, n).astype(np.uint32)
     r = renderer(c.scenes[0], ac.FRAME_SIZE)
-    _add(r, name, 1)
-    _set(r, name, 1)
+    ac.add(r, name, 1)
+    ac.spawn(r, name, 1)
     fresh = renderer(final, ac.FRAME_SIZE)
-    a, b = r.trace(rays, None, early, excl), fresh.trace(rays, None, early, excl)
-    assert np.array_equal(a, b)
-    assert (b[:, 3] < len(final.instances)).mean() > 0.3  # many of them hit
+    b = assert_traces_equal_fresh(r, fresh, ac.SEED, len(final.instances))
     new = {len(final.instances) - 1, len(final.instances) - 2}
     assert np.isin(b[:, 3], list(new)).any()  # some of them a new mesh
     fresh.close()
@@ -311,8 +188,7 @@ def _raw_add(r, descs, n=None, slices=True):
     count = len(descs) if n is None and descs is not None else (n or 0)
     arr = (_abi.hk_mesh_desc * max(1, count))(*(descs or [])) if descs is not None else None
     out = (_abi.hk_mesh_index * max(1, count))()
-    rc = r._L.hk_add_meshes(r.ctx, arr, count, out if slices else None, None)
-    return rc, r._L.hk_last_error(r.ctx).decode()
+    return raw_call(r, "hk_add_meshes", arr, count, out if slices else None, None)
 
 
 def test_refusals_leave_the_context_usable():
@@ -344,22 +220,18 @@ def test_refusals_leave_the_context_usable():
 
 # ------------------------------------------------------------------ stream, plugin
 def test_add_on_a_caller_stream():
-    """tris_1281 with add_meshes(..., stream=s) and set_instances on a stream of the caller's, created in the HIP
-    runtime the library loads (parity.hip_runtime): hk_add_meshes waits for its stream once, so the arrays are
-    complete when it returns; the test synchronises s all the same."""
+    """tris_1281 with add_meshes(..., stream=s) and set_instances on a stream of the caller's
+    (scene_edits.caller_stream): hk_add_meshes waits for its stream once, so the arrays are complete when it returns;
+    the test synchronises s all the same."""
     name = "tris_1281"
-    c = ac.case(name)
-    r = renderer(c.scenes[0])
-    hip = hip_runtime()
-    s = ctypes.c_void_p()
-    assert hip.hipStreamCreate(ctypes.byref(s)) == 0
-    assert _add(r, name, 1, stream=s) == [tuple(int(x) for x in v) for v in ac.new_slices(name, 1)]
-    assert hip.hipStreamSynchronize(s) == 0
-    assert_mesh_arrays(r, ac.add_only(name, 1).desc, _added_so_far(name, 1))
-    _set_and_check(r, name, 1, stream=s)
-    assert hip.hipStreamSynchronize(s) == 0
-    r.close()
-    assert hip.hipStreamDestroy(s) == 0
+    r = renderer(ac.case(name).scenes[0])
+    with caller_stream() as (s, sync):
+        assert ac.add(r, name, 1, stream=s) == [tuple(int(x) for x in v) for v in ac.new_slices(name, 1)]
+        sync()
+        assert_mesh_arrays(r, ac.add_only(name, 1).desc, ac.added_so_far(name, 1))
+        _set_and_check(r, name, 1, stream=s)
+        sync()
+        r.close()
 
 
 def test_plugin_forwards_add_meshes():
@@ -368,7 +240,7 @@ def test_plugin_forwards_add_meshes():
     c = ac.case(name)
     p = HikariPlugin(c.scenes[0])
     assert p.add_meshes(c.new[1]) == [tuple(int(x) for x in v) for v in ac.new_slices(name, 1)]
-    assert_mesh_arrays(p.renderer, ac.add_only(name, 1).desc, _added_so_far(name, 1))
+    assert_mesh_arrays(p.renderer, ac.add_only(name, 1).desc, ac.added_so_far(name, 1))
     p.set_instances(c.scenes[1], previous=c.previous[1])
     assert p.renderer.scene_counts() == ic.desc_counts(ac.built(name, 1))
     assert_rebuild_bitwise(p.renderer, ac.built(name, 1))

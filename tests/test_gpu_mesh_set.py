@@ -2,115 +2,32 @@
 tests/test_mesh_set_cases.py, without a GPU) uploaded as step 0; each step's mesh list and instance set given to the GPU
 in one call.  The returned slices, all nine counts and all nine arrays byte for byte the host builder's for that step;
 frames, G-buffers, motion vectors, traced rays and counters against the CPU oracle on the host-built scenes.
+The shared checks (arrays, frames, planes, rays, stream, raw calls) are tests/scene_edits.py's.
 
 The branch of csrc/hk_dynamic.hip or csrc/hk_runtime.hip each case exists for is listed in mesh_set_cases.py."""
-import ctypes
-
 import numpy as np
 import pytest
 
 import instance_set_cases as ic
-import mesh_cases as mc
 import mesh_set_cases as sc
-from parity import (NODE_DT, RACY, assert_rebuild_bitwise, canon_plane, compare_frame, hip_runtime, host_scene_array,
-                    mismatch_report, passes, renderer)
+from parity import renderer
+from scene_edits import (DEPTH_SIZE, MOTION_PLANES, EditFrames, assert_mesh_arrays, assert_planes, assert_scene_is,
+                         assert_traces_equal_fresh, caller_stream, device_arrays, gbuffer_planes, ptr, raw_call)
 
 pytestmark = pytest.mark.gpu
-
-DEPTH_SIZE = (64, 48)
-VERTEX_DT, PRIM_DT = np.dtype((np.void, 32)), np.dtype((np.void, 48))
-ELEM_DT = [VERTEX_DT, PRIM_DT, NODE_DT, np.dtype((np.void, 8)), np.dtype((np.void, 176)), NODE_DT,
-           np.dtype((np.void, 80)), NODE_DT, np.dtype((np.void, 64))]
-
-
-def _step(r, name, k, stream=None):
-    c = sc.case(name)
-    scene = c.scenes[k]
-    return r.set_meshes(scene, sc.entries(name, k), previous=c.previous[k], local_aabbs=sc.local_aabbs(scene),
-                        stream=stream)
-
-
-def _host_slices(name, k) -> list:
-    return [tuple(int(x) for x in s) for s in sc.slices(name, k)]
-
-
-# ---- the leaf boxes of the device's asset nodes, restated as tests/test_gpu_mesh_add.py restates them:
-# k_fill_blas_leaves takes vmin(a, vmin(b, c)) and vmax(a, vmax(b, c)) of the triangle's corners with the device's
-# fminf / fmaxf, which order -0 below +0
-def _device_min(p):
-    m = p.min(axis=1)
-    zero, neg = m == 0.0, (p.view(np.uint32) == 0x80000000).any(axis=1)
-    m[zero & neg], m[zero & ~neg] = -0.0, 0.0
-    return m
-
-
-def _device_max(p):
-    m = p.max(axis=1)
-    zero, pos = m == 0.0, (p.view(np.uint32) == 0).any(axis=1)
-    m[zero & pos], m[zero & ~pos] = 0.0, -0.0
-    return m
-
-
-def _expected_asset_nodes(desc, registered):
-    """The host's asset nodes with the leaves of every registered slice carrying their triangle's box."""
-    nodes = host_scene_array(desc, 2, NODE_DT).copy()
-    corners = np.ascontiguousarray(
-        np.frombuffer(host_scene_array(desc, 1, PRIM_DT).tobytes(), np.float32).reshape(-1, 3, 4)[:, :, :3])
-    for _, prim, n0, nc in set(mc.mesh_slices(desc)) | set(registered):
-        part = nodes[n0: n0 + nc]
-        leaf = part["entry"] >= 0x80000000
-        tri = corners[prim + (part["entry"][leaf] - 0x80000000)]
-        part["min"][leaf], part["max"][leaf] = _device_min(tri), _device_max(tri)
-    return nodes
-
-
-def assert_mesh_arrays(r, desc, registered):
-    """Arrays 0 and 1 byte for byte the host's; array 2: entry / exit everywhere, inner nodes whole, every leaf of a
-    registered slice the byte image of its triangle's box; counts 0-2 the host's."""
-    assert r.scene_counts()[:3] == ic.desc_counts(desc)[:3]
-    for idx, dt in ((0, VERTEX_DT), (1, PRIM_DT)):
-        h = host_scene_array(desc, idx, dt)
-        assert h.tobytes() == r.scene_array(idx, dt, len(h)).tobytes(), f"array {idx} differs"
-    want = _expected_asset_nodes(desc, registered)
-    got = r.scene_array(2, NODE_DT, len(want))
-    assert np.array_equal(want["entry"], got["entry"]) and np.array_equal(want["exit"], got["exit"])
-    inner = want["entry"] < 0x80000000
-    assert want[inner].tobytes() == got[inner].tobytes()
-    assert want.tobytes() == got.tobytes()
-
-
-def assert_scene_is(r, desc, registered):
-    """All nine counts and arrays the host build's: 0-2 by assert_mesh_arrays, 3, 4, 7, 8 and the TLAS by
-    assert_rebuild_bitwise (its leaves carry the instance boxes on the device), its entries, exits and inner nodes and
-    the materials here."""
-    assert r.scene_counts() == ic.desc_counts(desc)
-    assert_mesh_arrays(r, desc, registered)
-    assert_rebuild_bitwise(r, desc)
-    want = host_scene_array(desc, 5, NODE_DT)
-    got = r.scene_array(5, NODE_DT, len(want))
-    assert np.array_equal(want["entry"], got["entry"]) and np.array_equal(want["exit"], got["exit"])
-    inner = want["entry"] < 0x80000000
-    assert want[inner].tobytes() == got[inner].tobytes()
-    mats = host_scene_array(desc, 6, ELEM_DT[6])
-    assert mats.tobytes() == r.scene_array(6, ELEM_DT[6], len(mats)).tobytes()
-
-
-def _device_arrays(r, which=range(9)):
-    counts = r.scene_counts()
-    return [r.scene_array(i, ELEM_DT[i], counts[i]).tobytes() if counts[i] else b"" for i in which]
 
 
 def _step_and_check(r, name, k, stream=None):
     """Step k's call: the returned slices are the host's, and every listed slice is registered, so every leaf carries
     its box."""
-    assert _step(r, name, k, stream) == _host_slices(name, k)
-    assert_scene_is(r, sc.built(name, k), _host_slices(name, k))
+    assert sc.step(r, name, k, stream) == sc.host_slices(name, k)
+    assert_scene_is(r, sc.built(name, k), sc.host_slices(name, k))
 
 
 def _after_and_check(r, name):
     c = sc.case(name)
     last = len(c.scenes) - 1
-    registered = _host_slices(name, last)
+    registered = sc.host_slices(name, last)
     kind = c.after[0]
     if kind == "add":
         _, new, scene = c.after
@@ -144,9 +61,9 @@ def test_arrays_after_every_step_match_host_builder(name):
 def test_identity_keeps_every_byte():
     name = "identity"
     r = renderer(sc.case(name).scenes[0])
-    before = _device_arrays(r)
+    before = device_arrays(r)
     _step_and_check(r, name, 1)
-    now = _device_arrays(r)
+    now = device_arrays(r)
     # (array 2's leaves: the quad's and both meshes' were registered by the upload already; the TLAS's too)
     assert now == before
     r.close()
@@ -186,7 +103,7 @@ def test_capacity_grows_by_the_rule_and_back_and_forth_fits():
     back = [(s1.mesh_index(k), len(m.positions)) for k, m in enumerate(s1.meshes) if any(m is o for o in s0.meshes)]
     where = {key: i for i, key in enumerate(s1.keys)}
     got = r.set_meshes(s0, back, previous=[where.get(key) for key in s0.keys], local_aabbs=sc.local_aabbs(s0))
-    assert got == _host_slices(name, 0)
+    assert got == sc.host_slices(name, 0)
     assert_scene_is(r, sc.built(name, 0), got)
     assert r.scene_capacity()[:3] == grown[:3]
     _step_and_check(r, name, 1)
@@ -200,33 +117,13 @@ def _frames(name, options=None, wavefront=False):
     (Oracle.set_scene; one thread, spatial reuse off, the racy scatter targets within their tolerance), the reservoir
     history carried across the steps; equal ray counters at the end.  Where a survivor moves (replace_*) the instance
     count stays, so the oracle's previous models by index and the call's `previous` agree."""
-    from hikari_amd import HikariSettings, Upscale, frame_inputs, load_noise
-    from oracle import Oracle
-    c = sc.case(name)
-    cam, lights = sc.camera_for(name)
-    w, h = sc.FRAME_SIZE
-    r = renderer(c.scenes[0], (w, h), options=options, wavefront=wavefront)
-    o = Oracle(c.scenes[0].desc, load_noise(), w, h, 1.0, threads=1, textures=c.scenes[0].textures)
-    s = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=False).to_c()
-    errors, f = [], 0
-    for k in sc.steps(name):
-        if k:
-            _step_and_check(r, name, k)
-            o.set_scene(sc.built(name, k))
-        for _ in range(2):
-            fi = frame_inputs(f, cam, lights, w, h)
-            for x in (r, o):
-                passes(x, s, fi)
-            compare_frame(r, o, f, errors, racy=RACY)
-            f += 1
-        assert not errors, f"step {k}\n" + "\n".join(errors[:10])
-    assert r.counters() == o.counters()
-    depth = canon_plane(11, o.output(11)).view(np.float32).reshape(h, w, 4)[..., 3]
-    assert (depth > 0).mean() > 0.05  # the view covers some of the scene
-    lit = canon_plane(10, o.output(10)).view(np.float16).astype(np.float32)
-    assert np.isfinite(lit).all()
-    o.close()
-    r.close()
+    with EditFrames(sc.case(name).scenes[0], sc.camera_for(name), sc.FRAME_SIZE, floor=0.05, finite=True,
+                     options=options, wavefront=wavefront) as fr:
+        for k in sc.steps(name):
+            if k:
+                _step_and_check(fr.r, name, k)
+                fr.set_scene(sc.built(name, k))
+            fr.frames(2, f"step {k}")
 
 
 @pytest.mark.parametrize("name", sc.FRAME_CASES)
@@ -251,17 +148,6 @@ def test_frames_with_the_wavefront_pass():
 
 
 # ------------------------------------------------------------------ motion vectors, stack bound
-def _gbuffer_planes(x, fi):
-    x.render_gbuffer(fi)
-    return [canon_plane(oid, x.output(oid)) for oid in (11, 12, 13, 14, 15)]
-
-
-def _assert_planes(got, want, label):
-    for k, (a, b) in enumerate(zip(got, want)):
-        m = mismatch_report(a, b, f"{label}: output {11 + k}")
-        assert not m, m
-
-
 @pytest.mark.parametrize("name", list(sc.REPLACE))
 def test_motion_vectors_span_a_replacement(name):
     """The replaced mesh's instance moves in the step and carries `previous`: the G-buffer after the call, velocity
@@ -273,15 +159,15 @@ def test_motion_vectors_span_a_replacement(name):
     w, h = sc.FRAME_SIZE
     fis = [frame_inputs(f, cam, lights, w, h) for f in (0, 1)]
     o = Oracle(c.scenes[0].desc, load_noise(), w, h, 1.0)
-    _gbuffer_planes(o, fis[0])
+    gbuffer_planes(o, fis[0], MOTION_PLANES)
     o.set_scene(sc.built(name, 1))
-    want = _gbuffer_planes(o, fis[1])
+    want = gbuffer_planes(o, fis[1], MOTION_PLANES)
     velocity = want[4].view(np.float32).reshape(h, w, 4)[..., :2]
     assert (velocity != 0).any()  # the moving instance is in view
     r = renderer(c.scenes[0], (w, h))
-    _gbuffer_planes(r, fis[0])
+    gbuffer_planes(r, fis[0], MOTION_PLANES)
     _step_and_check(r, name, 1)
-    _assert_planes(_gbuffer_planes(r, fis[1]), want, name)
+    assert_planes(gbuffer_planes(r, fis[1], MOTION_PLANES), want, name)
     o.close()
     r.close()
 
@@ -298,16 +184,16 @@ def test_stack_bound_falls_with_the_drop():
     w, h = DEPTH_SIZE
     fi = frame_inputs(0, cam, lights, w, h)
     o = Oracle(c.scenes[0].desc, load_noise(), w, h, 1.0)
-    before = _gbuffer_planes(o, fi)[:4]
+    before = gbuffer_planes(o, fi)
     o.set_scene(sc.built(name, 1))
-    after = _gbuffer_planes(o, fi)[:4]
+    after = gbuffer_planes(o, fi)
     assert any((a != b).any() for a, b in zip(before, after))  # the deep mesh was in view
     o.close()
     for opts in sc.STACK_OPTIONS:
         r = renderer(c.scenes[0], (w, h), options=opts)
-        _assert_planes(_gbuffer_planes(r, fi)[:4], before, f"{opts} uploaded")
+        assert_planes(gbuffer_planes(r, fi), before, f"{opts} uploaded")
         _step_and_check(r, name, 1)
-        _assert_planes(_gbuffer_planes(r, fi)[:4], after, f"{opts} after the drop")
+        assert_planes(gbuffer_planes(r, fi), after, f"{opts} after the drop")
         r.close()
 
 
@@ -318,20 +204,10 @@ def test_traced_rays_after_a_step_equal_a_fresh_context():
     c = sc.case(name)
     final = c.scenes[1]
     sc.built(name, 1)
-    rng = np.random.default_rng(sc.SEED)
-    n = 256
-    org = rng.uniform([-1.5, 0.0, 1.0], [1.5, 2.0, 4.0], (n, 3))
-    d = rng.uniform([-1.5, 0.0, -0.5], [1.5, 3.0, 0.2], (n, 3)) - org
-    d /= np.linalg.norm(d, axis=1, keepdims=True)
-    rays = np.concatenate([org, d], axis=1).astype(np.float32)
-    early = np.where(rng.random(n) < 0.5, 0.0, 65535.0).astype(np.float32)
-    excl = rng.integers(0, len(final.instances) + 1, n).astype(np.uint32)
     r = renderer(c.scenes[0], sc.FRAME_SIZE)
-    _step(r, name, 1)
+    sc.step(r, name, 1)
     fresh = renderer(final, sc.FRAME_SIZE)
-    a, b = r.trace(rays, None, early, excl), fresh.trace(rays, None, early, excl)
-    assert np.array_equal(a, b)
-    assert (b[:, 3] < len(final.instances)).mean() > 0.3  # many of them hit
+    b = assert_traces_equal_fresh(r, fresh, sc.SEED, len(final.instances), top=3.0)
     assert (b[:, 3][b[:, 3] < len(final.instances)] >= 2).any()  # some of them a mesh of the rack
     fresh.close()
     r.close()
@@ -342,10 +218,8 @@ def _raw_set(r, entries, n, descs, count, models, aabbs, slices=True):
     """hk_set_meshes with hand-made arguments: its return code and message."""
     from hikari_amd import _abi
     out = (_abi.hk_mesh_index * max(1, n))()
-    rc = r._L.hk_set_meshes(r.ctx, entries, n, out if slices else None, descs,
-                            None if models is None else models.ctypes.data, None if aabbs is None else aabbs.ctypes.data,
-                            count, None, None)
-    return rc, r._L.hk_last_error(r.ctx).decode()
+    return raw_call(r, "hk_set_meshes", entries, n, out if slices else None, descs, ptr(models), ptr(aabbs), count, None,
+                    None)
 
 
 def test_refusals_leave_the_context_usable():
@@ -406,13 +280,13 @@ def test_refusals_leave_the_context_usable():
     w, h = sc.FRAME_SIZE
     fi = frame_inputs(0, cam, lights, w, h)
     r = renderer(s0, (w, h))
-    picture = _gbuffer_planes(r, fi)
-    cap, arrays = r.scene_capacity(), _device_arrays(r)
+    picture = gbuffer_planes(r, fi, MOTION_PLANES)
+    cap, arrays = r.scene_capacity(), device_arrays(r)
 
     def unchanged(label):
         assert r.scene_counts() == ic.desc_counts(s0.desc) and r.scene_capacity() == cap, label
-        assert _device_arrays(r) == arrays, label
-        _assert_planes(_gbuffer_planes(r, fi), picture, label)
+        assert device_arrays(r) == arrays, label
+        assert_planes(gbuffer_planes(r, fi, MOTION_PLANES), picture, label)
 
     for label, entries, n, text in lists:
         m_, a_ = models[: len(s0.instances)], aabbs[: len(s0.instances)]
@@ -428,7 +302,7 @@ def test_refusals_leave_the_context_usable():
     rc, msg = _raw_set(r, good, n_good, set1, n1, None, aabbs)
     assert rc == _abi.HK_ERR_INVALID and "null pointer" in msg
     unchanged("null pointers")
-    _assert_planes(_gbuffer_planes(r, fi), picture, "after the refusals")
+    assert_planes(gbuffer_planes(r, fi, MOTION_PLANES), picture, "after the refusals")
     assert_mesh_arrays(r, s0.desc, [])
     _step_and_check(r, name, 1)
     r.close()
@@ -436,18 +310,14 @@ def test_refusals_leave_the_context_usable():
 
 # ------------------------------------------------------------------ stream, plugin
 def test_set_on_a_caller_stream():
-    """replace_across_lds with set_meshes(..., stream=s) on a stream of the caller's, created in the HIP runtime the
-    library loads (parity.hip_runtime): the call waits for its stream, so the arrays are complete when it returns; the
-    test synchronises s all the same."""
+    """replace_across_lds with set_meshes(..., stream=s) on a stream of the caller's (scene_edits.caller_stream): the
+    call waits for its stream, so the arrays are complete when it returns; the test synchronises s all the same."""
     name = "replace_across_lds"
     r = renderer(sc.case(name).scenes[0])
-    hip = hip_runtime()
-    s = ctypes.c_void_p()
-    assert hip.hipStreamCreate(ctypes.byref(s)) == 0
-    _step_and_check(r, name, 1, stream=s)
-    assert hip.hipStreamSynchronize(s) == 0
-    r.close()
-    assert hip.hipStreamDestroy(s) == 0
+    with caller_stream() as (s, sync):
+        _step_and_check(r, name, 1, stream=s)
+        sync()
+        r.close()
 
 
 def test_plugin_forwards_set_meshes():
@@ -456,6 +326,6 @@ def test_plugin_forwards_set_meshes():
     c = sc.case(name)
     p = HikariPlugin(c.scenes[0])
     got = p.set_meshes(c.scenes[1], sc.entries(name, 1), previous=c.previous[1])
-    assert got == _host_slices(name, 1)
+    assert got == sc.host_slices(name, 1)
     assert_scene_is(p.renderer, sc.built(name, 1), got)
     p.renderer.close()

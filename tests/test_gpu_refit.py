@@ -14,6 +14,7 @@ What each case exists for in csrc/hk_dynamic.hip:
   one_of_three                 the unlisted slices keep their bytes
   neg_zero, coincident_300     zeros of both signs under an unordered fold; the `halves` tree
   folded                       a deformation far from the pose the tree was built for
+The shared checks (arrays, frames, planes, rays, stream, raw calls) are tests/scene_edits.py's.
 """
 import ctypes
 
@@ -23,10 +24,11 @@ import pytest
 import mesh_cases as mc
 import refit_cases as rc
 import skin_cases as sc
-from parity import RACY, canon_plane, compare_frame, hip_runtime, host_scene_array, passes
-from parity import renderer
-from test_gpu_mesh_update import NODE_DT, PRIM_DT, VERTEX_DT, _expected_asset_nodes, assert_mesh_rebuild_bitwise
-from test_gpu_skin import caller_aabbs
+from parity import NODE_DT, assert_rebuild_bitwise, host_scene_array, renderer
+from scene_edits import (EditFrames, assert_mesh_arrays, assert_mesh_rebuild_bitwise, assert_scene_is,
+                         assert_slices_kept, assert_traces_equal_fresh, caller_stream, models_and_aabbs, ptr, raw_call,
+                         raw_renderer)
+from skin_cases import caller_aabbs
 
 pytestmark = pytest.mark.gpu
 
@@ -51,14 +53,7 @@ def test_refit_arrays_match_the_refitted_scene(name):
     _refit(r, name)
     assert_mesh_rebuild_bitwise(r, rc.refitted(name))
     if name == "one_of_three":
-        want = _expected_asset_nodes(scene0.desc)
-        for i in (0, 2):
-            v, p, n0, nc = scene0.mesh_index(i)
-            nv, k = len(scene0.meshes[i].positions), (nc + 2) // 3
-            for idx, dt, a, n, host in ((0, VERTEX_DT, v, nv, None), (1, PRIM_DT, p, k, None), (2, NODE_DT, n0, nc, want)):
-                h = host_scene_array(scene0.desc, idx, dt) if host is None else host
-                g = r.scene_array(idx, dt, len(h))
-                assert h[a: a + n].tobytes() == g[a: a + n].tobytes(), (i, idx)
+        assert_slices_kept(r, scene0, (0, 2))
     r.close()
 
 
@@ -115,31 +110,14 @@ def test_no_meshes_is_update_instances():
 
 # ------------------------------------------------------------------ frames
 def _frames(name, options=None, wavefront=False):
-    from hikari_amd import HikariSettings, Upscale, frame_inputs, load_noise
-    from oracle import Oracle
     scene0, scene1 = rc.case(name)
     d1 = rc.refitted(name)
-    cam, lights = rc.camera_for(name)
-    w, h = rc.FRAME_SIZE
-    r = renderer(scene0, (w, h), options=options, wavefront=wavefront)
-    _refit(r, name)
-    assert_mesh_rebuild_bitwise(r, d1)
-    st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=False)
-    o = Oracle(scene0.desc, load_noise(), w, h, 1.0, threads=1)
-    o.set_scene(d1)
-    s = st.to_c()
-    errors = []
-    for f in range(2):
-        fi = frame_inputs(f, cam, lights, w, h)
-        for x in (r, o):
-            passes(x, s, fi)
-        compare_frame(r, o, f, errors, racy=RACY)
-    assert not errors, "\n".join(errors[:10])
-    assert r.counters() == o.counters()
-    depth = canon_plane(11, o.output(11)).view(np.float32).reshape(h, w, 4)[..., 3]
-    assert (depth > 0).mean() >= 0.2  # the view covers the mesh
-    o.close()
-    r.close()
+    # (the floor: "at least 0.2" and "more than 0.2" are one thing at 32 x 24, where 0.2 of the frame is 153.6 pixels)
+    with EditFrames(scene0, rc.camera_for(name), rc.FRAME_SIZE, floor=0.2, options=options, wavefront=wavefront) as fr:
+        _refit(fr.r, name)
+        assert_mesh_rebuild_bitwise(fr.r, d1)
+        fr.set_scene(d1)
+        fr.frames(2)
 
 
 @pytest.mark.parametrize("name", rc.FRAME_CASES)
@@ -161,34 +139,14 @@ def test_frames_with_the_wavefront_pass():
     _frames("emissive_mesh", wavefront=True)
 
 
-def _raw_renderer(desc, size):
-    """A context that uploaded a desc as it is."""
-    from hikari_amd import HikariRenderer
-    r = HikariRenderer(0)
-    r.set_noise()
-    assert r._L.hk_scene_upload(r.ctx, ctypes.byref(desc)) == 0
-    r.resize(*size, 1.0)
-    return r
-
-
 def test_traced_rays_after_the_refit_equal_a_fresh_context():
     """256 seeded rays through hk_trace after the refit, against a context that uploaded the refitted desc."""
     name = "shared_mesh"
     scene0, scene1 = rc.case(name)
-    rng = np.random.default_rng(rc.SEED)
-    n = 256
-    org = rng.uniform([-1.5, 0.0, 1.0], [1.5, 2.0, 4.0], (n, 3))
-    d = rng.uniform([-1.5, 0.0, -0.5], [1.5, 2.0, 0.2], (n, 3)) - org
-    d /= np.linalg.norm(d, axis=1, keepdims=True)
-    rays = np.concatenate([org, d], axis=1).astype(np.float32)
-    early = np.where(rng.random(n) < 0.5, 0.0, 65535.0).astype(np.float32)
-    excl = rng.integers(0, len(scene1.instances) + 1, n).astype(np.uint32)
     r = renderer(scene0, rc.FRAME_SIZE)
     _refit(r, name)
-    fresh = _raw_renderer(rc.refitted(name), rc.FRAME_SIZE)
-    a, b = r.trace(rays, None, early, excl), fresh.trace(rays, None, early, excl)
-    assert np.array_equal(a, b)
-    assert (b[:, 3] < len(scene1.instances)).mean() > 0.3  # many of them hit
+    fresh = raw_renderer(rc.refitted(name), rc.FRAME_SIZE)
+    assert_traces_equal_fresh(r, fresh, rc.SEED, len(scene1.instances))
     fresh.close()
     r.close()
 
@@ -209,29 +167,14 @@ def _pose(r, name, k=0, stream=None, refit=True):
 def test_skin_refit_arrays_and_frames(name):
     """Bind pose uploaded, skins registered, posed with refit=True: the arrays are refitted(bind desc, Scene.posed(...)),
     and two frames equal the oracle's on it."""
-    from hikari_amd import HikariSettings, Upscale, frame_inputs, load_noise
-    from oracle import Oracle
     c = sc.case(name)
-    w, h = mc.FRAME_SIZE
-    r = renderer(c.scene0, (w, h))
-    r.set_mesh_skins(c.scene0, c.skinned, c.keep_normals)
-    _pose(r, name)
     want = _skin_expect(name)
-    assert_mesh_rebuild_bitwise(r, want)
-    cam, lights = sc.camera_for(name)
-    o = Oracle(c.scene0.desc, load_noise(), w, h, 1.0, threads=1)
-    o.set_scene(want)
-    s = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=False).to_c()
-    errors = []
-    for f in range(2):
-        fi = frame_inputs(f, cam, lights, w, h)
-        for x in (r, o):
-            passes(x, s, fi)
-        compare_frame(r, o, f, errors, racy=RACY)
-    assert not errors, "\n".join(errors[:10])
-    assert r.counters() == o.counters()
-    o.close()
-    r.close()
+    with EditFrames(c.scene0, sc.camera_for(name), mc.FRAME_SIZE) as fr:
+        fr.r.set_mesh_skins(c.scene0, c.skinned, c.keep_normals)
+        _pose(fr.r, name)
+        assert_mesh_rebuild_bitwise(fr.r, want)
+        fr.set_scene(want)
+        fr.frames(2)
 
 
 def test_pose_a_refit_pose_b_refit_pose_b_rebuild():
@@ -255,20 +198,18 @@ def test_refit_of_a_mesh_appended_and_spawned():
     """mesh_add_cases' then_update: the mesh hk_add_meshes appended and hk_set_instances spawned, refit in its slice
     past the uploaded arrays."""
     import mesh_add_cases as ac
-    from test_gpu_mesh_add import _add, _added_so_far, _set, assert_mesh_arrays
-    from parity import assert_rebuild_bitwise
     name = "then_update"
     c = ac.case(name)
     r = renderer(c.scenes[0])
     last = len(c.scenes) - 1
     for k in list(ac.steps(name))[1:]:
-        _add(r, name, k)
-        _set(r, name, k)
+        ac.add(r, name, k)
+        ac.spawn(r, name, k)
     scene, ids = c.update
     r.update_meshes(scene, ids, local_aabbs=ac.local_aabbs(scene), refit=True)
     want = _expect(ac.built(name, last), scene, ids)
     assert_rebuild_bitwise(r, want)
-    assert_mesh_arrays(r, want, _added_so_far(name, last))
+    assert_mesh_arrays(r, want, ac.added_so_far(name, last))
     rebuilt = ac.built_update(name)
     assert host_scene_array(want, 2, NODE_DT).tobytes() != host_scene_array(rebuilt, 2, NODE_DT).tobytes()
     r.close()
@@ -277,29 +218,26 @@ def test_refit_of_a_mesh_appended_and_spawned():
 def test_refit_of_a_slice_moved_by_set_meshes():
     """mesh_set_cases' then_update: the mesh hk_set_meshes moved to another place in the arrays, refit there."""
     import mesh_set_cases as ms
-    from test_gpu_mesh_set import _host_slices, _step, assert_scene_is
     name = "then_update"
     c = ms.case(name)
     r = renderer(c.scenes[0])
     last = len(c.scenes) - 1
     for k in list(ms.steps(name))[1:]:
-        _step(r, name, k)
+        ms.step(r, name, k)
     kind, scene, ids = c.after
     assert kind == "update"
     r.update_meshes(scene, ids, local_aabbs=ms.local_aabbs(scene), refit=True)
-    assert_scene_is(r, _expect(ms.built(name, last), scene, ids), _host_slices(name, last))
+    assert_scene_is(r, _expect(ms.built(name, last), scene, ids), ms.host_slices(name, last))
     r.close()
 
 
 # ------------------------------------------------------------------ refusals
 def _raw_refit(r, scene, ups, count=None, models=True, aabbs=True):
     from hikari_amd import _abi
-    m = np.ascontiguousarray(scene.instance_models(), np.float32)
-    a = np.ascontiguousarray(mc.local_aabbs(scene), np.float32)
+    m, a = models_and_aabbs(scene)
     arr = (_abi.hk_mesh_update * max(1, len(ups)))(*ups) if ups is not None else None
-    rc_ = r._L.hk_refit_meshes(r.ctx, arr, 0 if ups is None else len(ups), m.ctypes.data if models else None,
-                               a.ctypes.data if aabbs else None, len(m) if count is None else count, None)
-    return rc_, r._L.hk_last_error(r.ctx).decode()
+    return raw_call(r, "hk_refit_meshes", arr, 0 if ups is None else len(ups), ptr(m, models), ptr(a, aabbs),
+                    len(m) if count is None else count, None)
 
 
 def test_refusals_leave_the_context_usable():
@@ -377,14 +315,11 @@ def test_refit_on_a_caller_stream():
     name = "tris_1281"
     scene0, scene1 = rc.case(name)
     r = renderer(scene0)
-    hip = hip_runtime()
-    s = ctypes.c_void_p()
-    assert hip.hipStreamCreate(ctypes.byref(s)) == 0
-    _refit(r, name, stream=s)
-    assert hip.hipStreamSynchronize(s) == 0
-    assert_mesh_rebuild_bitwise(r, rc.refitted(name))
-    r.close()
-    assert hip.hipStreamDestroy(s) == 0
+    with caller_stream() as (s, sync):
+        _refit(r, name, stream=s)
+        sync()
+        assert_mesh_rebuild_bitwise(r, rc.refitted(name))
+        r.close()
 
 
 def test_plugin_forwards_refit():

@@ -16,6 +16,7 @@ What each case exists for in csrc/hk_dynamic.hip:
   flat_zero                    zeros of both signs in shape boxes, sibling boxes and the posed Aabb
   keep_normals                 normals = NULL: MeshUpdate::has_normals = 0 on the device path
 The caller's local_aabbs rows of a posed mesh's instances are filled with a wrong box in every test: they are ignored.
+The shared checks (arrays, frames, planes, rays, stream, raw calls) are tests/scene_edits.py's.
 """
 import ctypes
 
@@ -24,21 +25,12 @@ import pytest
 
 import mesh_cases as mc
 import skin_cases as sc
-from parity import RACY, canon_plane, compare_frame, hip_runtime, host_scene_array, passes, renderer
-from test_gpu_mesh_update import NODE_DT, PRIM_DT, VERTEX_DT, _expected_asset_nodes, assert_mesh_rebuild_bitwise
+from parity import host_scene_array, renderer
+from scene_edits import (INST_DT, EditFrames, assert_mesh_rebuild_bitwise, assert_slices_kept,
+                         assert_traces_equal_fresh, caller_stream, models_and_aabbs, ptr, raw_call, raw_renderer)
+from skin_cases import caller_aabbs
 
 pytestmark = pytest.mark.gpu
-
-WRONG_BOX = np.array([9.0, -7.0, 5.0, 123.0, 0.5, 77.0], np.float32)
-
-
-def caller_aabbs(scene, posed_meshes):
-    """mesh_cases.local_aabbs of the scene as given (the bind pose), with WRONG_BOX in the rows the library derives."""
-    a = mc.local_aabbs(scene)
-    for i, (mesh, _, _) in enumerate(scene.instances):
-        if mesh in posed_meshes:
-            a[i] = WRONG_BOX
-    return a
 
 
 def _register(r, name, stream=None):
@@ -68,14 +60,7 @@ def test_posed_arrays_match_host_builder(name):
     r = _posed_renderer(name)
     assert_mesh_rebuild_bitwise(r, sc.posed(name)[1])
     if name == "one_of_three":
-        want = _expected_asset_nodes(c.scene0.desc)
-        for i in (0, 2):
-            v, p, n0, nc = c.scene0.mesh_index(i)
-            nv, k = len(c.scene0.meshes[i].positions), (nc + 2) // 3
-            for idx, dt, a, n, host in ((0, VERTEX_DT, v, nv, None), (1, PRIM_DT, p, k, None), (2, NODE_DT, n0, nc, want)):
-                h = host_scene_array(c.scene0.desc, idx, dt) if host is None else host
-                g = r.scene_array(idx, dt, len(h))
-                assert h[a: a + n].tobytes() == g[a: a + n].tobytes(), (i, idx)
+        assert_slices_kept(r, c.scene0, (0, 2))
     r.close()
 
 
@@ -136,19 +121,6 @@ def test_registering_again_with_another_rig():
     r.close()
 
 
-def _assert_rebuild_in_longer_arrays(r, desc):
-    """assert_mesh_rebuild_bitwise where arrays 0-2 hold an appended mesh behind the host scene's: their heads."""
-    from parity import assert_rebuild_bitwise
-    counts = r.scene_counts()
-    for idx, dt in ((0, VERTEX_DT), (1, PRIM_DT)):
-        h = host_scene_array(desc, idx, dt)
-        assert counts[idx] > len(h)
-        assert h.tobytes() == r.scene_array(idx, dt, counts[idx])[:len(h)].tobytes(), f"array {idx} differs"
-    want = _expected_asset_nodes(desc)
-    assert want.tobytes() == r.scene_array(2, NODE_DT, counts[2])[:len(want)].tobytes()
-    assert_rebuild_bitwise(r, desc)
-
-
 def test_add_meshes_keeps_the_skins_and_set_meshes_and_upload_drop_them():
     from hikari_amd import HikariError, plane_mesh
     name = "one_of_three"
@@ -158,7 +130,7 @@ def test_add_meshes_keeps_the_skins_and_set_meshes_and_upload_drop_them():
     _register(r, name)
     r.add_meshes([plane_mesh(0.3)])
     _pose(r, name)
-    _assert_rebuild_in_longer_arrays(r, sc.posed(name)[1])
+    assert_mesh_rebuild_bitwise(r, sc.posed(name)[1], longer=True)
     # the same list again, the appended mesh left out: the slices stay where they are, and the set is dropped all the same
     entries = [(s0.mesh_index(i), len(s0.meshes[i].positions)) for i in range(len(s0.meshes))]
     posed_scene = sc.posed(name)[0]
@@ -177,32 +149,14 @@ def test_add_meshes_keeps_the_skins_and_set_meshes_and_upload_drop_them():
 
 
 def _frames(name, options=None, wavefront=False):
-    from hikari_amd import HikariSettings, Upscale, frame_inputs, load_noise
-    from oracle import Oracle
-    c = sc.case(name)
     d1 = sc.posed(name)[1]
-    cam, lights = sc.camera_for(name)
-    w, h = sc.FRAME_SIZE
-    r = _posed_renderer(name, (w, h), options=options, wavefront=wavefront)
-    assert_mesh_rebuild_bitwise(r, d1)
-    st = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=False)
-    o = Oracle(c.scene0.desc, load_noise(), w, h, 1.0, threads=1)
-    o.set_scene(d1)
-    s = st.to_c()
-    errors = []
-    for f in range(2):
-        fi = frame_inputs(f, cam, lights, w, h)
-        for x in (r, o):
-            passes(x, s, fi)
-        compare_frame(r, o, f, errors, racy=RACY)
-    assert not errors, "\n".join(errors[:10])
-    assert r.counters() == o.counters()
-    depth = canon_plane(11, o.output(11)).view(np.float32).reshape(h, w, 4)[..., 3]
-    assert (depth > 0).mean() > 0.1  # the view covers the mesh
-    lit = canon_plane(10, o.output(10)).view(np.float16).astype(np.float32)
-    assert np.isfinite(lit).all()
-    o.close()
-    r.close()
+    with EditFrames(sc.case(name).scene0, sc.camera_for(name), sc.FRAME_SIZE, floor=0.1, finite=True, options=options,
+                     wavefront=wavefront) as fr:
+        _register(fr.r, name)
+        _pose(fr.r, name)
+        assert_mesh_rebuild_bitwise(fr.r, d1)
+        fr.set_scene(d1)
+        fr.frames(2)
 
 
 @pytest.mark.parametrize("name", sc.FRAME_CASES)
@@ -225,19 +179,9 @@ def test_traced_rays_after_a_pose_equal_a_fresh_context():
     name = "shared_mesh"
     c = sc.case(name)
     s1 = sc.posed(name)[0]
-    rng = np.random.default_rng(sc.SEED)
-    n = 256
-    org = rng.uniform([-1.5, 0.0, 1.0], [1.5, 2.0, 4.0], (n, 3))
-    d = rng.uniform([-1.5, 0.0, -0.5], [1.5, 2.0, 0.2], (n, 3)) - org
-    d /= np.linalg.norm(d, axis=1, keepdims=True)
-    rays = np.concatenate([org, d], axis=1).astype(np.float32)
-    early = np.where(rng.random(n) < 0.5, 0.0, 65535.0).astype(np.float32)
-    excl = rng.integers(0, len(s1.instances) + 1, n).astype(np.uint32)
     r = _posed_renderer(name, sc.FRAME_SIZE)
     fresh = renderer(s1, sc.FRAME_SIZE)
-    a, b = r.trace(rays, None, early, excl), fresh.trace(rays, None, early, excl)
-    assert np.array_equal(a, b)
-    assert (b[:, 3] < len(s1.instances)).mean() > 0.3  # many of them hit
+    assert_traces_equal_fresh(r, fresh, sc.SEED, len(s1.instances))
     fresh.close()
     r.close()
 
@@ -252,19 +196,15 @@ def _index(scene, i, index=None):
 def _raw_skins(r, skins, n=None):
     from hikari_amd import _abi
     arr = (_abi.hk_mesh_skin * max(1, len(skins)))(*skins) if skins is not None else None
-    rc = r._L.hk_set_mesh_skins(r.ctx, arr, (0 if skins is None else len(skins)) if n is None else n, None)
-    return rc, r._L.hk_last_error(r.ctx).decode()
+    return raw_call(r, "hk_set_mesh_skins", arr, (0 if skins is None else len(skins)) if n is None else n, None)
 
 
 def _raw_pose(r, scene, poses, n=None, count=None, models=True, aabbs=True):
     from hikari_amd import _abi
-    m = np.ascontiguousarray(scene.instance_models(), np.float32)
-    a = np.ascontiguousarray(mc.local_aabbs(scene), np.float32)
+    m, a = models_and_aabbs(scene)
     arr = (_abi.hk_skin_pose * max(1, len(poses)))(*poses) if poses is not None else None
-    rc = r._L.hk_skin_meshes(r.ctx, arr, (0 if poses is None else len(poses)) if n is None else n,
-                             m.ctypes.data if models else None, a.ctypes.data if aabbs else None,
-                             len(m) if count is None else count, None)
-    return rc, r._L.hk_last_error(r.ctx).decode()
+    return raw_call(r, "hk_skin_meshes", arr, (0 if poses is None else len(poses)) if n is None else n, ptr(m, models),
+                    ptr(a, aabbs), len(m) if count is None else count, None)
 
 
 def test_refusals_leave_the_context_and_the_skin_set_as_they_were():
@@ -359,19 +299,17 @@ def test_refusals_leave_the_context_and_the_skin_set_as_they_were():
 
 def test_a_mesh_whose_nodes_are_not_3k_minus_2_cannot_be_skinned():
     """A scene uploaded with a mesh slice of one node less than 3k - 2: its skin is refused, another mesh's is taken."""
-    from hikari_amd import HikariRenderer, _abi
+    from hikari_amd import _abi
     c = sc.case("one_of_three")
     s0 = c.scene0
     d0 = s0.desc
-    inst = np.frombuffer(host_scene_array(d0, 4, np.dtype((np.void, 176))).tobytes(), np.uint32).reshape(-1, 44).copy()
+    inst = np.frombuffer(host_scene_array(d0, 4, INST_DT).tobytes(), np.uint32).reshape(-1, 44).copy()
     v, pr, n0, nc = s0.mesh_index(1)
     assert inst[1, 40:44].tolist() == [v, pr, n0, nc]
     inst[1, 43] = nc - 1
     desc = _abi.hk_scene_desc.from_buffer_copy(d0)
     desc.instances.data = inst.ctypes.data
-    r = HikariRenderer(0)
-    r.set_noise()
-    assert r._L.hk_scene_upload(r.ctx, ctypes.byref(desc)) == 0
+    r = raw_renderer(desc)
     m = s0.meshes[1]
     p, ix = np.ascontiguousarray(m.positions, np.float32), np.ascontiguousarray(m.skin.joint_indices, np.uint16)
     w = np.ascontiguousarray(m.skin.joint_weights, np.float32)
@@ -399,20 +337,16 @@ def test_a_singular_model_fails_after_the_rebuild():
 
 
 def test_pose_on_a_caller_stream():
-    """tris_1281 registered and posed on a stream of the caller's, created in the HIP runtime the library loads
-    (parity.hip_runtime): both calls wait for their stream once, so the arrays are complete when hk_skin_meshes returns;
-    the test synchronises the stream all the same."""
+    """tris_1281 registered and posed on a stream of the caller's (scene_edits.caller_stream): both calls wait for their
+    stream once, so the arrays are complete when hk_skin_meshes returns; the test synchronises the stream all the same."""
     name = "tris_1281"
     r = renderer(sc.case(name).scene0)
-    hip = hip_runtime()
-    s = ctypes.c_void_p()
-    assert hip.hipStreamCreate(ctypes.byref(s)) == 0
-    _register(r, name, stream=s)
-    _pose(r, name, stream=s)
-    assert hip.hipStreamSynchronize(s) == 0
-    assert_mesh_rebuild_bitwise(r, sc.posed(name)[1])
-    r.close()
-    assert hip.hipStreamDestroy(s) == 0
+    with caller_stream() as (s, sync):
+        _register(r, name, stream=s)
+        _pose(r, name, stream=s)
+        sync()
+        assert_mesh_rebuild_bitwise(r, sc.posed(name)[1])
+        r.close()
 
 
 def test_kernel_timing_names_the_pose():

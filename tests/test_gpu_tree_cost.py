@@ -12,6 +12,7 @@ thread per node, 256 per workgroup, 64 per wave.
   86 / 87 triangles            256 and 259 nodes with nothing in front: one slice exactly fills workgroup 0, the next
                                starts on workgroup 1's first thread and crosses into workgroup 2
   many_large                   a TLAS of 5,998 nodes: most waves whole inside one slice (the register sum)
+The shared checks (arrays, frames, planes, rays, stream, raw calls) are tests/scene_edits.py's.
 """
 import ctypes
 
@@ -22,12 +23,11 @@ import instance_refit_cases as ic
 import mesh_cases as mc
 import refit_cases as rc
 import tree_cost_numpy as tc
-from parity import RACY, compare_frame, hip_runtime, host_scene_array, passes, renderer
+from parity import hip_runtime, host_scene_array, passes, renderer
+from scene_edits import INST_DT, EditFrames, caller_stream, device_arrays, raw_call
 
 pytestmark = pytest.mark.gpu
 
-INST_DT = np.dtype((np.void, 176))
-ELEM = (32, 48, 32, 8, 176, 32, 80, 32, 64)  # bytes per record of the nine arrays
 BLAS_REFIT_CASES = ["small_32", "small_35", "tris_1", "tris_2", "tris_2600", "deep_65", "folded", "many_meshes"]
 
 
@@ -59,15 +59,11 @@ def raw(r, ids=(), tlas=True, lights=True, meshes=True, stream=None, null_ids=Fa
     ids = np.ascontiguousarray(ids, np.uint32)
     fill = lambda: _abi.hk_tree_cost(11, 12, 13.0, 14)  # (what an untouched out still holds)
     t, l, m = fill(), fill(), (_abi.hk_tree_cost * max(len(ids), 1))(*[fill() for _ in range(max(len(ids), 1))])
-    code = r._L.hk_tree_costs(r.ctx, None if null_ids or not len(ids) else ids.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
-                              len(ids), t if tlas else None, l if lights else None, m if meshes else None, stream)
+    id_ptr = None if null_ids or not len(ids) else ids.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
+    code, msg = raw_call(r, "hk_tree_costs", id_ptr, len(ids), t if tlas else None, l if lights else None,
+                         m if meshes else None, stream)
     out = {"tlas": TreeCost.from_c(t), "lights": TreeCost.from_c(l), "meshes": [TreeCost.from_c(m[j]) for j in range(len(ids))]}
-    return code, r._L.hk_last_error(r.ctx).decode(), out
-
-
-def nine_arrays(r) -> list:
-    counts = r.scene_counts()
-    return [r.scene_array(k, np.dtype((np.void, ELEM[k])), counts[k]).tobytes() for k in range(9)]
+    return code, msg, out
 
 
 # ------------------------------------------------------------------ device equals host
@@ -192,12 +188,12 @@ def test_a_query_leaves_the_nine_arrays_and_the_capacities_alone():
     r = renderer(scene0, (w, h))
     s = HikariSettings(upscale=Upscale.SMAA_TU_1_0).to_c()
     passes(r, s, frame_inputs(0, cam, lights, w, h))
-    before, capacity = nine_arrays(r), r.scene_capacity()
+    before, capacity = device_arrays(r), r.scene_capacity()
     n = len(_slices(scene0.desc))
     assert_costs(r, scene0.desc)
-    assert nine_arrays(r) == before and r.scene_capacity() == capacity
+    assert device_arrays(r) == before and r.scene_capacity() == capacity
     passes(r, s, frame_inputs(1, cam, lights, w, h))
-    assert nine_arrays(r) == before
+    assert device_arrays(r) == before
     hip = hip_runtime()
     free, total = ctypes.c_size_t(), ctypes.c_size_t()
     hip.hipMemGetInfo.argtypes = [ctypes.POINTER(ctypes.c_size_t)] * 2
@@ -214,31 +210,20 @@ def test_a_query_leaves_the_nine_arrays_and_the_capacities_alone():
 def test_frames_with_a_query_before_each_equal_the_oracles():
     """moving at 64 x 48: two frames on scene0, the refit, two more, a query before every frame and one on a refitted
     context: the frames are the oracle's, which knows no query, and the ray counters too."""
-    from hikari_amd import HikariSettings, Upscale, frame_inputs, load_noise
-    from oracle import Oracle
     name = "moving"
     scene0, scene1 = ic.case(name)
     d1 = ic.refitted(name)
-    cam, lights = ic.camera_for(name)
-    w, h = ic.FRAME_SIZE
-    r = renderer(scene0, (w, h))
-    o = Oracle(scene0.desc, load_noise(), w, h, 1.0, threads=1)
-    s = HikariSettings(upscale=Upscale.SMAA_TU_1_0, indirect_spatial_reuse=False).to_c()
-    errors = []
-    for f in range(4):
-        if f == 2:
-            r.update_instances(scene1.instance_models(), scene1.instance_local_aabbs(), refit=True)
-            o.set_scene(d1)
-        assert_costs(r, scene0.desc if f < 2 else d1, label=f"frame {f}")
-        fi = frame_inputs(f, cam, lights, w, h)
-        passes(r, s, fi)
-        assert_costs(r, scene0.desc if f < 2 else d1, [0], label=f"after frame {f}")
-        passes(o, s, fi)
-        compare_frame(r, o, f, errors, racy=RACY)
-    assert not errors, "\n".join(errors[:10])
-    assert r.counters() == o.counters()
-    o.close()
-    r.close()
+    with EditFrames(scene0, ic.camera_for(name), ic.FRAME_SIZE) as fr:
+        for f in range(4):
+            if f == 2:
+                fr.r.update_instances(scene1.instance_models(), scene1.instance_local_aabbs(), refit=True)
+                fr.set_scene(d1)
+            assert_costs(fr.r, scene0.desc if f < 2 else d1, label=f"frame {f}")
+            fi = fr.inputs()
+            passes(fr.r, fr.s, fi)
+            assert_costs(fr.r, scene0.desc if f < 2 else d1, [0], label=f"after frame {f}")  # before the readback
+            passes(fr.o, fr.s, fi)
+            fr.compare()
 
 
 # ------------------------------------------------------------------ interface
@@ -255,7 +240,7 @@ def test_refusals_leave_the_context_as_it_was():
 
     r = renderer(scene0)
     n = len(_slices(scene0.desc))
-    before = nine_arrays(r)
+    before = device_arrays(r)
     untouched = TreeCost(11, 12, 13.0, 14)
     for ids in ([n], [0, 1, n + 7], [0xFFFFFFFF]):
         code, msg, got = raw(r, ids)
@@ -267,7 +252,7 @@ def test_refusals_leave_the_context_as_it_was():
     assert code == _abi.HK_ERR_INVALID and "hk_tree_costs" in msg
     with pytest.raises(HikariError, match="hk_tree_costs"):
         r.tree_costs([n])
-    assert nine_arrays(r) == before
+    assert device_arrays(r) == before
     assert_costs(r, scene0.desc)
     r.close()
 
@@ -275,17 +260,14 @@ def test_refusals_leave_the_context_as_it_was():
 def test_a_query_on_a_caller_stream():
     scene0, scene1 = ic.case("many_large")
     r = renderer(scene0)
-    hip = hip_runtime()
-    stream = ctypes.c_void_p()
-    assert hip.hipStreamCreate(ctypes.byref(stream)) == 0
-    want = host_costs(scene0.desc)
-    assert r.tree_costs(range(len(want["meshes"])), stream=stream) == want
-    r.update_instances(scene1.instance_models(), scene1.instance_local_aabbs(), stream, refit=True)
-    want = host_costs(ic.refitted("many_large"))
-    assert r.tree_costs(range(len(want["meshes"])), stream=stream) == want
-    assert r.tree_costs(range(len(want["meshes"]))) == want  # and on the context's own again
-    r.close()
-    assert hip.hipStreamDestroy(stream) == 0
+    with caller_stream() as (stream, _):
+        want = host_costs(scene0.desc)
+        assert r.tree_costs(range(len(want["meshes"])), stream=stream) == want
+        r.update_instances(scene1.instance_models(), scene1.instance_local_aabbs(), stream, refit=True)
+        want = host_costs(ic.refitted("many_large"))
+        assert r.tree_costs(range(len(want["meshes"])), stream=stream) == want
+        assert r.tree_costs(range(len(want["meshes"]))) == want  # and on the context's own again
+        r.close()
 
 
 def test_the_plugin_forwards_the_query():
