@@ -1,6 +1,7 @@
 // hk_dynamic.hip — dynamic instances, deforming meshes, changed instance sets
 // (DESIGN §0 f8), appended meshes, new mesh lists, skinned meshes, the
-// BLAS refit, the instance refit and the tree costs on the device.
+// BLAS refit, the instance refit, the tree costs and morph targets
+//  on the device.
 //
 // The reference re-runs `prepare_instances` on the CPU whenever a transform changes
 // (instance.rs:284-437: instance records with world AABBs and inverse-transpose models, the
@@ -17,6 +18,7 @@
 #include "hk_device.h"
 #include "hk_launch.h"
 #include "../../include/hk_skin.h"
+#include "../../include/hk_morph.h"
 #include "../../include/hk_refit.h"
 #include "../../include/hk_cost.h"
 
@@ -650,6 +652,32 @@ __global__ __launch_bounds__(256) void k_refit_large(const MeshUpdate* tab, uint
 // the posed position and normal stored into the staged streams at the vertex's place in list order, where
 // k_update_mesh_geometry and the BLAS build read them as if the host had sent them.  Every index was checked against
 // the skin's joint_count on the host (hk_set_mesh_skins), and the pose's joint_count is the skin's (hk_skin_meshes).
+// The skin step of one vertex, shared by k_skin_vertices and k_morph_vertices: the rig at `at` of the resident skin
+// streams, the four joint matrices of the palette at joint0, and hk_skin.h's matrix applied to p (and to nr) in place.
+HKD void skin_vertex(const uint2* joint_indices, const float4* joint_weights, const float4* palettes, size_t at,
+                     uint32_t joint0, bool has_normals, float* p, float* nr)
+{
+    const uint2 ix = joint_indices[at];
+    const float4 wt = joint_weights[at];
+    const uint32_t joint[4] = {ix.x & 0xFFFFu, ix.x >> 16, ix.y & 0xFFFFu, ix.y >> 16};
+    const float w[4] = {wt.x, wt.y, wt.z, wt.w};
+    float J[4][16];
+    for (int j = 0; j < 4; ++j) {
+        const float4* col = palettes + 4u * ((size_t)joint0 + joint[j]);
+        for (int c = 0; c < 4; ++c) {
+            const float4 q = col[c];
+            J[j][4 * c] = q.x, J[j][4 * c + 1] = q.y, J[j][4 * c + 2] = q.z, J[j][4 * c + 3] = q.w;
+        }
+    }
+    float M[12], o[3];
+    hk_skin_matrix(J[0], J[1], J[2], J[3], w, M);
+    hk_skin_position(M, p, o);
+    for (int a = 0; a < 3; ++a) p[a] = o[a];
+    if (has_normals) {
+        hk_skin_normal(M, nr, o);
+        for (int a = 0; a < 3; ++a) nr[a] = o[a];
+    }
+}
 __global__ __launch_bounds__(256) void k_skin_vertices(const MeshUpdate* tab, const SkinSource* sources,
                                                        uint32_t n_meshes, uint32_t n_vertices,
                                                        const float* bind_positions, const float* bind_normals,
@@ -664,28 +692,93 @@ __global__ __launch_bounds__(256) void k_skin_vertices(const MeshUpdate* tab, co
     if (v >= m.vertex_count) return;
     const SkinSource s = sources[k];
     const size_t at = (size_t)s.skin0 + v;
-    const uint2 ix = joint_indices[at];
-    const float4 wt = joint_weights[at];
-    const uint32_t joint[4] = {ix.x & 0xFFFFu, ix.x >> 16, ix.y & 0xFFFFu, ix.y >> 16};
-    const float w[4] = {wt.x, wt.y, wt.z, wt.w};
-    float J[4][16];
-    for (int j = 0; j < 4; ++j) {
-        const float4* col = palettes + 4u * ((size_t)s.joint0 + joint[j]);
-        for (int c = 0; c < 4; ++c) {
-            const float4 q = col[c];
-            J[j][4 * c] = q.x, J[j][4 * c + 1] = q.y, J[j][4 * c + 2] = q.z, J[j][4 * c + 3] = q.w;
-        }
-    }
-    float M[12], p[3], o[3];
-    hk_skin_matrix(J[0], J[1], J[2], J[3], w, M);
+    float p[3], nr[3] = {0.0f, 0.0f, 0.0f};
     for (int a = 0; a < 3; ++a) p[a] = bind_positions[3u * at + a];
-    hk_skin_position(M, p, o);
-    for (int a = 0; a < 3; ++a) positions[3u * (size_t)i + a] = o[a];
-    if (m.has_normals) {
-        for (int a = 0; a < 3; ++a) p[a] = bind_normals[3u * at + a];
-        hk_skin_normal(M, p, o);
-        for (int a = 0; a < 3; ++a) normals[3u * (size_t)i + a] = o[a];
+    if (m.has_normals)
+        for (int a = 0; a < 3; ++a) nr[a] = bind_normals[3u * at + a];
+    skin_vertex(joint_indices, joint_weights, palettes, at, s.joint0, m.has_normals != 0u, p, nr);
+    for (int a = 0; a < 3; ++a) positions[3u * (size_t)i + a] = p[a];
+    if (m.has_normals)
+        for (int a = 0; a < 3; ++a) normals[3u * (size_t)i + a] = nr[a];
+}
+
+// ---- morph targets (include/hk_morph.h: glTF 2.0's sum and Bevy 0.11's morph.wgsl as recalled, the
+// order pinned there; the host side is hk_scene.cpp hks_morph_vertices over the same header).  One thread per vertex of
+// the posed meshes, found by k_update_mesh_geometry's table search.  The base comes from the context's resident morph
+// block; the fold runs over the mesh's range of the ACTIVE LIST (the targets whose weight is not zero, compacted on the
+// host in ascending order), whose trip count is uniform per mesh.  Target t's delta of vertex v lies at record
+// delta0 + t x V + v, so consecutive lanes read consecutive 12-byte records.  The loads of a batch of MORPH_BATCH
+// targets are issued before the batch's first add (morph_batch: no condition around a load, so that the compiler need
+// not wait for one before it issues the next), so that their latencies overlap instead of adding up (each add depends
+// on the one before; the loads do not); whole batches first, then the rest one by one; the adds stay strictly in list
+// order.  Where the source names a skin,
+// skin_vertex then applies the vertex's skin matrix as k_skin_vertices does.  The results go into the staged streams at
+// the vertex's place in list order.  Vertices are independent: no fence, no atomics, plain vector loads and stores.
+// Every offset was checked on the host: the records against the registered set (hk_set_mesh_morphs), every list entry's
+// target below the registered target_count and the skin's vertex_count equal to the morph's (hk_morph_meshes).
+struct MorphFold {
+    const MorphActive* list;  // the mesh's range of the active list
+    const float* dp;          // its position deltas
+    const float* dn;          // its normal deltas (read where NORMALS)
+    uint32_t V, v;            // its vertex count, this thread's vertex
+};
+// N list entries from `first`: every load of the batch unconditionally and before the first add, then the adds in list
+// order
+template <int N, bool NORMALS>
+HKD void morph_batch(const MorphFold& F, uint32_t first, float* p, float* nr)
+{
+    float w[N], dp[N][3], dn[N][3];
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const MorphActive e = F.list[first + j];
+        const size_t rec = 3u * ((size_t)e.target * F.V + F.v);
+        w[j] = e.weight;
+        for (int a = 0; a < 3; ++a) dp[j][a] = F.dp[rec + a];
+        if (NORMALS)
+            for (int a = 0; a < 3; ++a) dn[j][a] = F.dn[rec + a];
     }
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        hk_morph_add(p, w[j], dp[j]);
+        if (NORMALS) hk_morph_add(nr, w[j], dn[j]);
+    }
+}
+__global__ __launch_bounds__(256) void k_morph_vertices(const MeshUpdate* tab, const MorphSource* sources,
+                                                        const MorphActive* active, uint32_t n_meshes,
+                                                        uint32_t n_vertices, const float* base_positions,
+                                                        const float* base_normals, const float* position_deltas,
+                                                        const float* normal_deltas, const uint2* joint_indices,
+                                                        const float4* joint_weights, const float4* palettes,
+                                                        float* positions, float* normals)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_vertices) return;
+    const uint32_t k = mesh_of(tab, n_meshes, i, false);
+    const MeshUpdate& m = tab[k];
+    const uint32_t v = i - m.vertex0;
+    if (v >= m.vertex_count) return;
+    const MorphSource s = sources[k];
+    const bool has_normals = m.has_normals != 0u, fold_normals = has_normals && s.normal_delta0 != MORPH_NONE;
+    const size_t at = (size_t)s.base0 + v;
+    float p[3], nr[3] = {0.0f, 0.0f, 0.0f};
+    for (int a = 0; a < 3; ++a) p[a] = base_positions[3u * at + a];
+    if (has_normals)
+        for (int a = 0; a < 3; ++a) nr[a] = base_normals[3u * at + a];
+    const MorphFold F{active + s.active0, position_deltas + 3u * (size_t)s.delta0,
+                      fold_normals ? normal_deltas + 3u * (size_t)s.normal_delta0 : nullptr, m.vertex_count, v};
+    uint32_t b = 0;
+    if (fold_normals) {  // (uniform per mesh, like both trip counts)
+        for (; b + (uint32_t)MORPH_BATCH <= s.active_count; b += (uint32_t)MORPH_BATCH) morph_batch<MORPH_BATCH, true>(F, b, p, nr);
+        for (; b < s.active_count; ++b) morph_batch<1, true>(F, b, p, nr);
+    } else {
+        for (; b + (uint32_t)MORPH_BATCH <= s.active_count; b += (uint32_t)MORPH_BATCH) morph_batch<MORPH_BATCH, false>(F, b, p, nr);
+        for (; b < s.active_count; ++b) morph_batch<1, false>(F, b, p, nr);
+    }
+    if (s.skin0 != MORPH_NONE)
+        skin_vertex(joint_indices, joint_weights, palettes, (size_t)s.skin0 + v, s.joint0, has_normals, p, nr);
+    for (int a = 0; a < 3; ++a) positions[3u * (size_t)i + a] = p[a];
+    if (has_normals)
+        for (int a = 0; a < 3; ++a) normals[3u * (size_t)i + a] = nr[a];
 }
 // One workgroup per posed mesh: the box of its staged (posed) positions by hk_skin.h's bounds rule, stated without an
 // order: each bound's value by fminf / fmaxf (exact in any order; a NaN loses, as in the host's fold), and a bound of 0
@@ -693,13 +786,15 @@ __global__ __launch_bounds__(256) void k_skin_vertices(const MeshUpdate* tab, co
 // is below 2^30, hk_skin_meshes' bound).  Then the Bevy Aabb (centre, half extents) over the rows of local_aabbs whose
 // instance record carries this mesh's slice: one thread per instance, strided.  The records are those before the
 // rebuild; k_update_instances leaves their mesh slices as they are.
-__global__ __launch_bounds__(256) void k_skin_bounds(const MeshUpdate* tab, const SkinSource* sources,
+// (slices: where the posed meshes' hk_mesh_index records lie, in a SkinSource or a MorphSource table)
+__global__ __launch_bounds__(256) void k_skin_bounds(const MeshUpdate* tab, PosedSlices slices,
                                                      const float* positions, const hk_instance* inst, uint32_t n_inst,
                                                      float* local_aabbs)
 {
     __shared__ CoopShared sh;
     const MeshUpdate m = tab[blockIdx.x];
-    const hk_mesh_index mesh = sources[blockIdx.x].mesh;
+    const hk_mesh_index mesh =
+        *reinterpret_cast<const hk_mesh_index*>((const char*)slices.first + (size_t)blockIdx.x * slices.stride);
     const float* p = positions + 3u * (size_t)m.vertex0;
     const float inf = __uint_as_float(0x7F800000u);
     float b[6] = {inf, inf, inf, -inf, -inf, -inf};
@@ -1499,11 +1594,17 @@ void launch_skin_vertices(const SkinArgs& K, hipStream_t st)
                        K.n_meshes, K.n_vertices, K.bind_positions, K.bind_normals, K.joint_indices, K.joint_weights,
                        K.palettes, K.positions, K.normals);
 }
-void launch_skin_bounds(const SkinArgs& K, const hk_instance* instances, uint32_t n_instances, float* local_aabbs,
-                        hipStream_t st)
+void launch_posed_bounds(const MeshUpdate* table, PosedSlices slices, uint32_t n_meshes, const float* positions,
+                         const hk_instance* instances, uint32_t n_instances, float* local_aabbs, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_skin_bounds, dim3(K.n_meshes), dim3(256), 0, st, K.table, K.sources, (const float*)K.positions,
-                       instances, n_instances, local_aabbs);
+    hipLaunchKernelGGL(k_skin_bounds, dim3(n_meshes), dim3(256), 0, st, table, slices, positions, instances, n_instances,
+                       local_aabbs);
+}
+void launch_morph_vertices(const MorphArgs& K, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_morph_vertices, dim3((K.n_vertices + 255u) / 256u), dim3(256), 0, st, K.table, K.sources,
+                       K.active, K.n_meshes, K.n_vertices, K.base_positions, K.base_normals, K.position_deltas,
+                       K.normal_deltas, K.joint_indices, K.joint_weights, K.palettes, K.positions, K.normals);
 }
 uint32_t mesh_lds_shapes() { return BVH_LDS_SHAPES; }
 

@@ -281,10 +281,60 @@ struct SkinArgs {
 };
 // one thread per vertex of the posed meshes: the posed position and normal into the staged streams (one launch)
 void launch_skin_vertices(const SkinArgs& K, hipStream_t st);
+// The posed meshes' slices as k_skin_bounds reads them: the hk_mesh_index of mesh k lies `stride` bytes after that of
+// mesh k - 1 (the `mesh` member of a table of SkinSource or of MorphSource records).
+struct PosedSlices {
+    const void* first;
+    uint32_t stride;
+};
 // one workgroup per posed mesh: its Bevy Aabb from the staged positions (include/hk_skin.h's bounds rule), written over
 // the rows of local_aabbs (n_instances x 6) whose instance record carries the mesh's slice (one launch)
-void launch_skin_bounds(const SkinArgs& K, const hk_instance* instances, uint32_t n_instances, float* local_aabbs,
-                        hipStream_t st);
+void launch_posed_bounds(const MeshUpdate* table, PosedSlices slices, uint32_t n_meshes, const float* positions,
+                         const hk_instance* instances, uint32_t n_instances, float* local_aabbs, hipStream_t st);
+inline void launch_skin_bounds(const SkinArgs& K, const hk_instance* instances, uint32_t n_instances, float* local_aabbs,
+                               hipStream_t st)
+{
+    launch_posed_bounds(K.table, PosedSlices{&K.sources->mesh, (uint32_t)sizeof(SkinSource)}, K.n_meshes, K.positions,
+                        instances, n_instances, local_aabbs, st);
+}
+
+// Morph targets (hk_morph_meshes, hk_dynamic.hip): beside each posed mesh's MeshUpdate record, where its
+// base and its deltas lie in the context's resident morph block, its range of the uploaded active list (the targets
+// whose weight is not zero, ascending), and its skin and palette when the pose gives joints.
+constexpr uint32_t MORPH_NONE = 0xFFFFFFFFu;
+// The targets whose delta loads k_morph_vertices issues before the first add of a batch (the adds stay in list order).
+// Tried on the device: see DESIGN §0 f15.
+constexpr int MORPH_BATCH = 4;
+struct MorphActive {
+    uint32_t target;
+    float weight;
+};
+struct MorphSource {
+    uint32_t base0;         // its first vertex in the resident base streams
+    uint32_t delta0;        // its first record in the resident position deltas: target t, vertex v at delta0 + t x V + v
+    uint32_t normal_delta0; // the same in the normal deltas; MORPH_NONE: the base normals as they are
+    uint32_t active0, active_count;  // its range of the active list
+    uint32_t skin0;         // its first vertex in the resident skin streams; MORPH_NONE: morph only
+    uint32_t joint0;        // its first matrix in the uploaded palettes
+    hk_mesh_index mesh;     // its slice, as its instances' records carry it (k_skin_bounds)
+};
+struct MorphArgs {
+    const MeshUpdate* table;        // n_meshes records in list order
+    const MorphSource* sources;     // beside them
+    const MorphActive* active;      // the uploaded active list
+    uint32_t n_meshes, n_vertices;  // n_vertices: the sum over the list
+    const float* base_positions;    // resident: x 3
+    const float* base_normals;      // resident: x 3 (read where MeshUpdate::has_normals)
+    const float* position_deltas;   // resident: x 3 per record
+    const float* normal_deltas;
+    const uint2* joint_indices;     // the resident skin streams (read where a source names a skin)
+    const float4* joint_weights;
+    const float4* palettes;
+    float* positions;               // the staged streams, n_vertices x 3
+    float* normals;
+};
+// one thread per vertex of the posed meshes: the morphed (and skinned) position and normal into the staged streams
+void launch_morph_vertices(const MorphArgs& K, hipStream_t st);
 
 // Appended meshes (hk_add_meshes, hk_dynamic.hip): beside each mesh's MeshUpdate record (its destination slices past
 // the arrays' ends, vertex0 / shape0 its place in the staged streams; has_normals is not read), where its indices lie

@@ -420,6 +420,19 @@ struct hk_ctx {
     std::vector<Skin> skins;
     void* skin_block = nullptr;
     size_t skin_cap = 0;
+    // hk_set_mesh_morphs: the registered morphs (slice, vertices, targets, where its base and its delta records lie)
+    // and one device block carved into the four resident streams at the set's own totals (base positions and base
+    // normals x 12 per vertex, position deltas and normal deltas x 12 per record); morph_cap: the block's bytes, which
+    // stay where a smaller set follows a larger one
+    struct Morph {
+        hk_mesh_index index;
+        uint32_t vertex_count, target_count, vertex0, delta0, normal_delta0;  // normal_delta0 MORPH_NONE: none
+        bool has_normals;
+    };
+    std::vector<Morph> morphs;
+    void* morph_block = nullptr;
+    size_t morph_cap = 0;
+    uint64_t morph_total[3] = {};  // the set's vertices, position delta records, normal delta records
     // GlobalTransformQueue[1] of every instance (transform.rs:32-44): the models as of the previous
     // k_gbuffer, read by its motion vectors; refreshed after a k_gbuffer that followed an update
     float* prev_models = nullptr;
@@ -1186,6 +1199,7 @@ void hk_destroy(hk_ctx* c)
     release(c->blas_aux);
     release(c->mesh_scratch);
     release(c->skin_block);
+    release(c->morph_block);
     release(c->prev_models);
     release(c->tex_desc);
     release(c->texels);
@@ -1482,6 +1496,7 @@ int hk_scene_upload(hk_ctx* c, const hk_scene_desc* d)
     }
     c->emissive = emissive_of((const hk_material*)d->materials.data, d->materials.count);
     c->skins.clear();  // (the slices are another scene's; the streams keep their capacity)
+    c->morphs.clear();
     // the instanced meshes: each distinct slice once, with the vertices its primitives index and its BLAS depth
     // (gb_blas_depth is the maximum of these)
     if (!host_registry(d, &c->meshes)) return fail(c, HK_ERR_INVALID, "instance mesh node range outside asset nodes");
@@ -2476,6 +2491,245 @@ int hk_skin_meshes_refit_all(hk_ctx* c, const hk_skin_pose* poses, uint32_t n, c
     return skin_meshes(c, "hk_skin_meshes_refit_all", true, true, poses, n, models, local_aabbs, count, stream);
 }
 
+// The four resident morph streams in one block, carved at the set's own totals (hk_ctx::morph_total), every stream
+// 256-aligned
+struct MorphStreams {
+    float* positions;
+    float* normals;
+    float* position_deltas;
+    float* normal_deltas;
+    size_t bytes;
+};
+static MorphStreams morph_streams(void* block, const uint64_t total[3])
+{
+    const size_t sz[4] = {(size_t)total[0] * 12, (size_t)total[0] * 12, (size_t)total[1] * 12, (size_t)total[2] * 12};
+    char* p = (char*)block;
+    MorphStreams s;
+    s.positions = (float*)p;
+    s.normals = (float*)(p + carve_bytes(sz, 1));
+    s.position_deltas = (float*)(p + carve_bytes(sz, 2));
+    s.normal_deltas = (float*)(p + carve_bytes(sz, 3));
+    s.bytes = carve_bytes(sz, 4);
+    return s;
+}
+static size_t find_morph(const std::vector<hk_ctx::Morph>& morphs, const hk_mesh_index& x)
+{
+    size_t k = 0;
+    while (k < morphs.size() && std::memcmp(&morphs[k].index, &x, sizeof(x)) != 0) ++k;
+    return k;
+}
+
+int hk_set_mesh_morphs(hk_ctx* c, const hk_mesh_morph* morphs, uint32_t n, void* stream)
+{
+    if (!c) return HK_ERR_INVALID;
+    if (!c->has_scene) return fail(c, HK_ERR_STATE, "no scene uploaded (hk_scene_upload)");
+    if (n && !morphs) return fail(c, HK_ERR_INVALID, "hk_set_mesh_morphs: null pointer");
+    // the whole list on the host first: a refusal leaves the set before as it was
+    std::vector<hk_ctx::Morph> set(n);
+    uint64_t total[3] = {0, 0, 0};
+    for (uint32_t k = 0; k < n; ++k) {
+        const hk_mesh_morph& s = morphs[k];
+        const std::string who = "hk_set_mesh_morphs: morph " + std::to_string(k);
+        if (!s.positions || !s.position_deltas)
+            return fail(c, HK_ERR_INVALID, who + " has a null pointer (positions, position_deltas)");
+        if (s.normal_deltas && !s.normals) return fail(c, HK_ERR_INVALID, who + " has normal_deltas without normals");
+        if (s.target_count == 0 || s.target_count > HK_MORPH_MAX_TARGETS)
+            return fail(c, HK_ERR_INVALID, who + ": target_count is outside 1 .. " + std::to_string(HK_MORPH_MAX_TARGETS));
+        const size_t at = find_slice(c->meshes, s.mesh);
+        if (at == c->meshes.size()) return fail(c, HK_ERR_INVALID, who + " is not a known mesh slice of the scene");
+        for (uint32_t j = 0; j < k; ++j)
+            if (std::memcmp(&set[j].index, &s.mesh, sizeof(s.mesh)) == 0)
+                return fail(c, HK_ERR_INVALID, who + " is listed twice");
+        HK_TRY(mesh_rewritable(c, who, at, s.vertex_count));
+        const uint64_t records = (uint64_t)s.target_count * s.vertex_count;
+        if (total[0] + s.vertex_count > 0x40000000u || total[1] + records > 0x40000000u)
+            return fail(c, HK_ERR_INVALID, "hk_set_mesh_morphs: too many vertices or target_count x vertex_count records");
+        set[k] = hk_ctx::Morph{s.mesh, s.vertex_count, s.target_count, (uint32_t)total[0], (uint32_t)total[1],
+                               s.normal_deltas ? (uint32_t)total[2] : MORPH_NONE, s.normals != nullptr};
+        total[0] += s.vertex_count;
+        total[1] += records;
+        if (s.normal_deltas) total[2] += records;
+    }
+    (void)hipSetDevice(c->device);
+    hipStream_t st = pick(c, stream);
+    const size_t bytes = morph_streams((void*)0, total).bytes;
+    if (bytes > c->morph_cap) {  // (the new block first: out of memory leaves the set before in place)
+        void* block = nullptr;
+        HK_HIP(c, hipMalloc(&block, bytes));
+        HK_HIP(c, hipStreamSynchronize(st));
+        release(c->morph_block);
+        c->morph_block = block;
+        c->morph_cap = bytes;
+    }
+    c->morphs.clear();  // (the streams are overwritten from here on)
+    std::memcpy(c->morph_total, total, sizeof(total));
+    const MorphStreams S = morph_streams(c->morph_block, total);
+    for (uint32_t k = 0; k < n; ++k) {
+        const hk_mesh_morph& s = morphs[k];
+        const size_t v0 = set[k].vertex0, nv = s.vertex_count, nr = nv * s.target_count;
+        if (!nv) continue;
+        HK_HIP(c, hipMemcpyAsync(S.positions + 3 * v0, s.positions, nv * 12, hipMemcpyHostToDevice, st));
+        if (s.normals) HK_HIP(c, hipMemcpyAsync(S.normals + 3 * v0, s.normals, nv * 12, hipMemcpyHostToDevice, st));
+        HK_HIP(c, hipMemcpyAsync(S.position_deltas + 3 * (size_t)set[k].delta0, s.position_deltas, nr * 12,
+                                 hipMemcpyHostToDevice, st));
+        if (s.normal_deltas)
+            HK_HIP(c, hipMemcpyAsync(S.normal_deltas + 3 * (size_t)set[k].normal_delta0, s.normal_deltas, nr * 12,
+                                     hipMemcpyHostToDevice, st));
+    }
+    HK_HIP(c, hipStreamSynchronize(st));
+    c->morphs = std::move(set);
+    return HK_OK;
+}
+
+// hk_morph_meshes (fn = "hk_morph_meshes"), hk_morph_meshes_refit and hk_morph_meshes_refit_all: one body, the BLAS step
+// apart (refit) and the instance trees kept or not (refit_trees), switched as skin_meshes switches them
+static int morph_meshes(hk_ctx* c, const std::string& fn, bool refit, bool refit_trees, const hk_morph_pose* poses,
+                        uint32_t n, const float* models, const float* local_aabbs, uint32_t count, void* stream)
+{
+    if (!c) return HK_ERR_INVALID;
+    if (!models || !local_aabbs || (n && !poses)) return fail(c, HK_ERR_INVALID, fn + ": null pointer");
+    HK_TRY(update_args_ok(c, count, fn.c_str()));
+    // every pose against the registered morphs, skins and the registry, before any device work: each a staged mesh with
+    // no host streams (k_morph_vertices fills its part of them); the active lists one after another
+    std::vector<hk_mesh_desc> descs(n);
+    std::vector<const hk_mesh_desc*> list(n);
+    std::vector<hk_mesh_index> slices(n);
+    std::vector<uint32_t> tris(n);
+    std::vector<size_t> morph_of(n);
+    std::vector<MorphSource> sources(n);
+    std::vector<MorphActive> active;
+    MeshLevels ml;
+    ml.slice.resize(n);
+    uint64_t n_vertices = 0, n_shapes = 0, n_joints = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+        const hk_morph_pose& p = poses[k];
+        const std::string who = fn + ": pose " + std::to_string(k);
+        if (!p.weights) return fail(c, HK_ERR_INVALID, who + " has a null pointer (weights)");
+        const size_t mk = find_morph(c->morphs, p.mesh);
+        if (mk == c->morphs.size())
+            return fail(c, HK_ERR_INVALID, who + " names a mesh with no registered morph (hk_set_mesh_morphs)");
+        for (uint32_t j = 0; j < k; ++j)
+            if (morph_of[j] == mk) return fail(c, HK_ERR_INVALID, who + " poses a mesh twice");
+        const hk_ctx::Morph& s = c->morphs[mk];
+        if (p.target_count != s.target_count)
+            return fail(c, HK_ERR_INVALID, who + ": target_count " + std::to_string(p.target_count) +
+                                               " differs from the registered morph's " + std::to_string(s.target_count));
+        uint32_t skin0 = MORPH_NONE;
+        if (p.joints) {
+            const size_t sk = find_skin(c->skins, p.mesh);
+            if (sk == c->skins.size())
+                return fail(c, HK_ERR_INVALID, who + " gives joints for a mesh with no registered skin (hk_set_mesh_skins)");
+            const hk_ctx::Skin& sn = c->skins[sk];
+            if (p.joint_count != sn.joint_count)
+                return fail(c, HK_ERR_INVALID, who + ": joint_count " + std::to_string(p.joint_count) +
+                                                   " differs from the registered skin's " + std::to_string(sn.joint_count));
+            if (sn.has_normals != s.has_normals)
+                return fail(c, HK_ERR_INVALID, who + ": its skin and its morph disagree on whether normals are rewritten");
+            if (sn.vertex_count != s.vertex_count)
+                return fail(c, HK_ERR_INVALID, who + ": its skin and its morph disagree on the vertex_count");
+            skin0 = sn.vertex0;
+        }
+        const size_t at = find_slice(c->meshes, s.index);
+        if (at == c->meshes.size()) return fail(c, HK_ERR_INVALID, who + " is not a known mesh slice of the scene");
+        HK_TRY(mesh_rewritable(c, who, at, s.vertex_count));
+        tris[k] = (s.index.node[1] + 2u) / 3u;
+        if (n_vertices + s.vertex_count > 0x40000000u || n_shapes + tris[k] > 0x40000000u)
+            return fail(c, HK_ERR_INVALID, fn + ": too many vertices or primitives in one call");
+        descs[k] = hk_mesh_desc{nullptr, nullptr, nullptr, s.vertex_count, nullptr, 0u, HKS_TRIANGLE_LIST};
+        list[k] = &descs[k];
+        slices[k] = s.index;
+        morph_of[k] = mk;
+        const uint32_t active0 = (uint32_t)active.size();
+        for (uint32_t t = 0; t < s.target_count; ++t)
+            if (p.weights[t] != 0.0f) active.push_back(MorphActive{t, p.weights[t]});  // (hk_morph.h: hk_morph_active)
+        sources[k] = MorphSource{s.vertex0, s.delta0, s.normal_delta0, active0, (uint32_t)active.size() - active0,
+                                 skin0,     (uint32_t)n_joints, s.index};
+        ml.slice[k] = (uint32_t)at;
+        n_vertices += s.vertex_count;
+        n_shapes += tris[k];
+        if (p.joints) n_joints += p.joint_count;
+    }
+    (void)hipSetDevice(c->device);
+    hipStream_t st = pick(c, stream);
+    if (n == 0) return rebuild_instances(c, models, local_aabbs, count, st, nullptr, nullptr, nullptr, refit_trees);
+    HK_TRY(c->sch.gb_join(st));
+    HK_TRY(c->sch.gb_serialize(false));
+    // the caller's part of the staging: the palettes one after another, the active list, then the MorphSource table
+    const size_t palette_bytes = ((size_t)n_joints * 64 + 255) & ~(size_t)255;
+    const size_t active_bytes = (active.size() * sizeof(MorphActive) + 255) & ~(size_t)255;
+    MeshStaging stage;
+    plan_mesh_staging(list, slices.data(), tris.data(), n_vertices, n_shapes, 0,
+                      palette_bytes + active_bytes + (size_t)n * sizeof(MorphSource), &stage, refit);
+    for (std::vector<MeshUpdate>* t : {&stage.tab, &stage.by_size})
+        for (MeshUpdate& m : *t) m.has_normals = c->morphs[morph_of[m.slot]].has_normals ? 1u : 0u;
+    MeshAddArgs A;
+    char* extra = nullptr;
+    HK_TRY(enqueue_mesh_staging(c, list, stage, st, &A, &extra));
+    for (uint32_t k = 0; k < n; ++k)
+        if (poses[k].joints)
+            HK_HIP(c, hipMemcpyAsync(extra + (size_t)sources[k].joint0 * 64, poses[k].joints,
+                                     (size_t)poses[k].joint_count * 64, hipMemcpyHostToDevice, st));
+    if (!active.empty())
+        HK_HIP(c, hipMemcpyAsync(extra + palette_bytes, active.data(), active.size() * sizeof(MorphActive),
+                                 hipMemcpyHostToDevice, st));
+    HK_HIP(c, hipMemcpyAsync(extra + palette_bytes + active_bytes, sources.data(), (size_t)n * sizeof(MorphSource),
+                             hipMemcpyHostToDevice, st));
+    const MorphStreams S = morph_streams(c->morph_block, c->morph_total);
+    const SkinStreams R = skin_streams(c->skin_block, c->skin_cap);
+    MorphArgs K;
+    K.table = A.M.table;
+    K.sources = (const MorphSource*)(extra + palette_bytes + active_bytes);
+    K.active = (const MorphActive*)(extra + palette_bytes);
+    K.n_meshes = n;
+    K.n_vertices = (uint32_t)n_vertices;
+    K.base_positions = S.positions;
+    K.base_normals = S.normals;
+    K.position_deltas = S.position_deltas;
+    K.normal_deltas = S.normal_deltas;
+    K.joint_indices = R.indices;
+    K.joint_weights = R.weights;
+    K.palettes = (const float4*)extra;
+    K.positions = const_cast<float*>(A.M.positions);
+    K.normals = const_cast<float*>(A.M.normals);
+    const PosedSlices posed{&K.sources->mesh, (uint32_t)sizeof(MorphSource)};
+    // after rebuild_instances' uploads, so that the posed boxes land on the device copy of local_aabbs
+    const std::function<void(float*)> work = [&](float* device_aabbs) {
+        const auto bounds = [&] {
+            launch_posed_bounds(K.table, posed, n, K.positions, (const hk_instance*)c->buf[4], count, device_aabbs, st);
+        };
+        if (refit) {
+            timed(c, "refit_morph_vertices", st, [&] { launch_morph_vertices(K, st); });
+            enqueue_mesh_refit(c, A.M, st);
+            timed(c, "refit_morph_bounds", st, bounds);
+            return;
+        }
+        timed(c, "morph_meshes", st, [&] {
+            launch_morph_vertices(K, st);
+            launch_mesh_update(A.M, st);
+            refresh_blas_derivatives(c, st, c->count[2]);
+            bounds();
+        });
+    };
+    ml.device = A.M.levels;
+    if (refit) ml.slice.clear();  // the topology stays, and so does every depth: no levels to read back
+    return rebuild_instances(c, models, local_aabbs, count, st, &ml, nullptr, &work, refit_trees);
+}
+int hk_morph_meshes(hk_ctx* c, const hk_morph_pose* poses, uint32_t n, const float* models, const float* local_aabbs,
+                    uint32_t count, void* stream)
+{
+    return morph_meshes(c, "hk_morph_meshes", false, false, poses, n, models, local_aabbs, count, stream);
+}
+int hk_morph_meshes_refit(hk_ctx* c, const hk_morph_pose* poses, uint32_t n, const float* models,
+                          const float* local_aabbs, uint32_t count, void* stream)
+{
+    return morph_meshes(c, "hk_morph_meshes_refit", true, false, poses, n, models, local_aabbs, count, stream);
+}
+int hk_morph_meshes_refit_all(hk_ctx* c, const hk_morph_pose* poses, uint32_t n, const float* models,
+                              const float* local_aabbs, uint32_t count, void* stream)
+{
+    return morph_meshes(c, "hk_morph_meshes_refit_all", true, true, poses, n, models, local_aabbs, count, stream);
+}
+
 // the checks hk_set_instances and hk_set_meshes share before the set is planned: the scene's BVHs can be rebuilt, and
 // the previous indices name the set before, each once
 static int set_args_ok(hk_ctx* c, const hk_instance_desc* set, uint32_t count, const char* who)
@@ -2864,6 +3118,7 @@ int hk_set_meshes(hk_ctx* c, const hk_mesh_entry* list, uint32_t mesh_count, hk_
     for (int i = 0; i < 3; ++i) c->count[i] = plan.after[i];
     c->meshes = plan.registry;
     c->skins.clear();  // (the slices moved: hk_set_mesh_skins registers the new ones)
+    c->morphs.clear();  // (and hk_set_mesh_morphs)
     std::memcpy(slices, plan.slices.data(), plan.slices.size() * sizeof(hk_mesh_index));
     return rebuild_instances(c, models, local_aabbs, count, st, nullptr, &change);
 }

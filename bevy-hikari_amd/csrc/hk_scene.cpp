@@ -10,6 +10,7 @@
 //   bvh 0.7.1 BVH::build + flatten_custom (third-party, restated from its published algorithm)
 #include "../../include/hikari_scene.h"
 #include "../../include/hk_skin.h"
+#include "../../include/hk_morph.h"
 #include "../../include/hk_refit.h"
 #include "../../include/hk_cost.h"
 
@@ -695,6 +696,43 @@ int hks_skin_vertices(const float* positions, const float* normals, const uint16
             for (int k = 0; k < 3; ++k) out_normals[3 * (size_t)v + k] = n[k];
         }
         for (int k = 0; k < 3; ++k) out_positions[3 * (size_t)v + k] = p[k];
+        box.grow(v3(p[0], p[1], p[2]));
+    }
+    if (out_aabb) {
+        const V3 center = box.center(), half = (box.max - box.min) * 0.5f;
+        const float a[6] = {center.x, center.y, center.z, half.x, half.y, half.z};
+        std::memcpy(out_aabb, a, sizeof(a));
+    }
+    return HK_OK;
+}
+
+// Morph targets by include/hk_morph.h's rule, vertex by vertex: the fold over the targets that take part, in ascending
+// order, and the morphed mesh's Aabb as hks_skin_vertices derives a posed mesh's.  Everything is checked before the
+// first store.
+int hks_morph_vertices(const float* positions, const float* normals, const float* position_deltas,
+                       const float* normal_deltas, uint32_t vertex_count, const float* weights, uint32_t target_count,
+                       float* out_positions, float* out_normals, float out_aabb[6])
+{
+    if (!positions || !position_deltas || !weights || !out_positions) return HK_ERR_INVALID;
+    if ((normals == nullptr) != (out_normals == nullptr) || (normal_deltas && !normals)) return HK_ERR_INVALID;
+    if (target_count == 0 || target_count > HK_MORPH_MAX_TARGETS) return HK_ERR_INVALID;
+    Aabb box = Aabb::empty();
+    for (uint32_t v = 0; v < vertex_count; ++v) {
+        float p[3], n[3] = {0.0f, 0.0f, 0.0f};
+        for (int k = 0; k < 3; ++k) {
+            p[k] = positions[3 * (size_t)v + k];
+            if (normals) n[k] = normals[3 * (size_t)v + k];
+        }
+        for (uint32_t t = 0; t < target_count; ++t) {
+            if (!hk_morph_active(weights[t])) continue;
+            const size_t at = 3 * ((size_t)t * vertex_count + v);
+            hk_morph_add(p, weights[t], position_deltas + at);
+            if (normal_deltas) hk_morph_add(n, weights[t], normal_deltas + at);
+        }
+        for (int k = 0; k < 3; ++k) {
+            out_positions[3 * (size_t)v + k] = p[k];
+            if (normals) out_normals[3 * (size_t)v + k] = n[k];
+        }
         box.grow(v3(p[0], p[1], p[2]));
     }
     if (out_aabb) {

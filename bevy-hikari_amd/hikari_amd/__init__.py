@@ -8,8 +8,8 @@ from ._abi import HikariError
 from .plugin import (HikariPlugin, HikariRenderer, PLAN_GBUFFER, PLAN_LIGHT, RESERVOIR_DTYPE, add_meshes_counts,
                      instance_descs, instance_set_counts, scene_gbuffer_stack, scene_indirect_lds, scene_stage_bytes,
                      set_meshes_counts, shared_transform)
-from .scene import (AmbientLight, Camera, DirectionalLight, Mesh, Scene, Skin, StandardMaterial, Texture, Transform,
-                    frame_inputs, jitter_mode, load_glb, load_noise, make_lights, plane_mesh, refit_boxes, refit_nodes, skin_vertices,
+from .scene import (AmbientLight, Camera, DirectionalLight, Mesh, Morph, Scene, Skin, StandardMaterial, Texture, Transform,
+                    frame_inputs, jitter_mode, load_glb, load_noise, make_lights, plane_mesh, refit_boxes, refit_nodes, skin_vertices, morph_vertices,
                     texture_array,
                     uv_sphere_mesh)
 from .cost import RefitPolicy, TreeCost, tree_cost
@@ -17,6 +17,6 @@ from .settings import HikariSettings, HikariUniversalSettings, PresentFormat, Ta
 
 __all__ = [
     "HikariError", "HikariPlugin", "HikariRenderer", "RESERVOIR_DTYPE", "AmbientLight", "Camera", "DirectionalLight",
-    "Mesh", "Scene", "Skin", "skin_vertices", "refit_nodes", "refit_boxes", "TreeCost", "tree_cost", "RefitPolicy", "StandardMaterial", "Texture", "texture_array", "Transform", "frame_inputs", "jitter_mode", "load_glb", "load_noise", "make_lights",
+    "Mesh", "Scene", "Skin", "skin_vertices", "Morph", "morph_vertices", "refit_nodes", "refit_boxes", "TreeCost", "tree_cost", "RefitPolicy", "StandardMaterial", "Texture", "texture_array", "Transform", "frame_inputs", "jitter_mode", "load_glb", "load_noise", "make_lights",
     "plane_mesh", "uv_sphere_mesh", "scene_stage_bytes", "scene_indirect_lds", "scene_gbuffer_stack", "shared_transform", "instance_descs", "instance_set_counts", "add_meshes_counts", "set_meshes_counts", "PLAN_LIGHT", "PLAN_GBUFFER", "HikariSettings", "HikariUniversalSettings", "PresentFormat", "Taa", "Upscale", "_abi",
 ]

@@ -95,6 +95,20 @@ class hk_skin_pose(C.Structure):
     _fields_ = [("mesh", hk_mesh_index), ("joints", C.c_void_p), ("joint_count", C.c_uint32)]
 
 
+class hk_mesh_morph(C.Structure):
+    """include/hikari_amd.h hk_mesh_morph (one mesh's base and target-major deltas for hk_set_mesh_morphs)."""
+    _fields_ = [("mesh", hk_mesh_index), ("vertex_count", C.c_uint32), ("positions", C.c_void_p),
+                ("normals", C.c_void_p), ("target_count", C.c_uint32), ("position_deltas", C.c_void_p),
+                ("normal_deltas", C.c_void_p)]
+
+
+class hk_morph_pose(C.Structure):
+    """include/hikari_amd.h hk_morph_pose (one mesh's target weights, and its joint palette or NULL, for hk_morph_meshes)."""
+    _fields_ = [("mesh", hk_mesh_index), ("weights", C.c_void_p), ("target_count", C.c_uint32), ("joints", C.c_void_p),
+                ("joint_count", C.c_uint32)]
+
+
+HK_MORPH_MAX_TARGETS = 256
 HK_INSTANCE_NEW = 0xFFFFFFFF
 
 
@@ -262,6 +276,10 @@ def lib() -> C.CDLL:
         "hk_refit_instances": (i32, [vp, vp, vp, u32, vp]),
         "hk_refit_meshes_all": (i32, [vp, C.POINTER(hk_mesh_update), u32, vp, vp, u32, vp]),
         "hk_skin_meshes_refit_all": (i32, [vp, C.POINTER(hk_skin_pose), u32, vp, vp, u32, vp]),
+        "hk_set_mesh_morphs": (i32, [vp, C.POINTER(hk_mesh_morph), u32, vp]),
+        "hk_morph_meshes": (i32, [vp, C.POINTER(hk_morph_pose), u32, vp, vp, u32, vp]),
+        "hk_morph_meshes_refit": (i32, [vp, C.POINTER(hk_morph_pose), u32, vp, vp, u32, vp]),
+        "hk_morph_meshes_refit_all": (i32, [vp, C.POINTER(hk_morph_pose), u32, vp, vp, u32, vp]),
         "hk_tree_costs": (i32, [vp, C.POINTER(u32), u32] + [C.POINTER(hk_tree_cost)] * 3 + [vp]),
         "hk_scene_shared_transform": (i32, [vp, C.POINTER(i32)]),
         "hk_instance_set_counts": (i32, [C.POINTER(hk_scene_desc), C.POINTER(hk_instance_desc), u32, vp, C.POINTER(u32)]),
@@ -303,6 +321,7 @@ def lib() -> C.CDLL:
         "hks_tone_rect": (i32, [C.POINTER(i32), C.POINTER(i32), i32, u32, C.POINTER(i32)]),
         "hks_keep_tiles": (i32, [C.POINTER(i32), C.POINTER(i32), i32, u32, C.POINTER(u32)]),
         "hks_skin_vertices": (i32, [vp, vp, vp, vp, u32, vp, u32, vp, vp, vp]),
+        "hks_morph_vertices": (i32, [vp, vp, vp, vp, u32, vp, u32, vp, vp, vp]),
         "hks_refit_nodes": (i32, [vp, u32, vp, u32]),
         "hks_refit_boxes": (i32, [vp, u32, vp, u32]),
         "hks_tree_cost": (i32, [vp, u32, C.POINTER(hk_tree_cost)]),
@@ -332,6 +351,7 @@ EXPORTED_SYMBOLS = [
     "hk_refit_meshes", "hk_skin_meshes_refit", "hks_refit_nodes",
     "hk_refit_instances", "hk_refit_meshes_all", "hk_skin_meshes_refit_all", "hks_refit_boxes",
     "hk_tree_costs", "hks_tree_cost",
+    "hk_set_mesh_morphs", "hk_morph_meshes", "hk_morph_meshes_refit", "hk_morph_meshes_refit_all", "hks_morph_vertices",
 ]
 
 

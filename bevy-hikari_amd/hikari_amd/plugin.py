@@ -432,6 +432,68 @@ class HikariRenderer:
         _check(self.ctx, getattr(self._L, name)(self.ctx, arr, len(poses), m.ctypes.data, a.ctypes.data, len(m),
                                                 _stream(stream)), name)
 
+    def set_mesh_morphs(self, scene: Scene, mesh_ids, keep_normals=(), stream=None) -> None:
+        """Register the morph targets of `scene.meshes[i]` for each i in `mesh_ids` (hk_set_mesh_morphs): the mesh's
+        positions and normals as the base and its `morph` (target-major position and normal deltas) are copied to the
+        device, where morph_meshes reads them.  The call replaces the whole set (an empty list drops it); the skin set
+        is another.  keep_normals: mesh ids registered without normals (and without normal deltas), whose uploaded
+        normals a pose leaves alone."""
+        arr = (_abi.hk_mesh_morph * max(1, len(mesh_ids)))()
+        keep = []
+        for s, i in zip(arr, mesh_ids):
+            mesh = scene.meshes[i]
+            if mesh.morph is None:
+                raise ValueError(f"mesh {i} has no morph")
+            p = np.ascontiguousarray(mesh.positions, np.float32).reshape(-1, 3)
+            n = None if mesh.normals is None or i in keep_normals else \
+                np.ascontiguousarray(mesh.normals, np.float32).reshape(-1, 3)
+            dp = np.ascontiguousarray(mesh.morph.position_deltas, np.float32).reshape(-1, len(p), 3)
+            dn = None if mesh.morph.normal_deltas is None or n is None else \
+                np.ascontiguousarray(mesh.morph.normal_deltas, np.float32).reshape(-1, len(p), 3)
+            if (n is not None and len(n) != len(p)) or (dn is not None and dn.shape != dp.shape):
+                raise ValueError("positions, normals, position_deltas and normal_deltas differ in length")
+            keep += [p, n, dp, dn]
+            v, pr, n0, nc = scene.mesh_index(i)
+            s.mesh = _abi.hk_mesh_index(v, pr, (C.c_uint32 * 2)(n0, nc))
+            s.vertex_count = len(p)
+            s.positions = p.ctypes.data
+            s.normals = None if n is None else n.ctypes.data
+            s.target_count = len(dp)
+            s.position_deltas = dp.ctypes.data
+            s.normal_deltas = None if dn is None else dn.ctypes.data
+        _check(self.ctx, self._L.hk_set_mesh_morphs(self.ctx, arr, len(mesh_ids), _stream(stream)), "hk_set_mesh_morphs")
+
+    def morph_meshes(self, scene: Scene, poses: dict, models=None, local_aabbs=None, stream=None,
+                     refit=False) -> None:
+        """Morph meshes on the GPU (hk_morph_meshes): poses = {mesh id: weights} or {mesh id: (weights, joints)} for
+        meshes registered by set_mesh_morphs (and, with joints, by set_mesh_skins); the GPU folds the targets whose
+        weight is not zero over the resident base, skins the result where joints are given, rebuilds the meshes'
+        primitives and BLAS and then everything update_instances rebuilds, with the posed meshes' boxes derived on the
+        device.  `scene` gives the slices and, by default, models and local_aabbs, as for skin_meshes.  refit=True
+        (hk_morph_meshes_refit): the posed meshes' BLAS are refit, not rebuilt; refit="all" (hk_morph_meshes_refit_all):
+        the TLAS and the light BVH too."""
+        m = np.ascontiguousarray(scene.instance_models() if models is None else models, np.float32).reshape(-1, 16)
+        a = np.ascontiguousarray(scene.instance_local_aabbs() if local_aabbs is None else local_aabbs,
+                                 np.float32).reshape(-1, 6)
+        if len(m) != len(a):
+            raise ValueError("models and local_aabbs differ in length")
+        arr = (_abi.hk_morph_pose * max(1, len(poses)))()
+        keep = []
+        for p, (i, pose) in zip(arr, poses.items()):
+            weights, joints = pose if isinstance(pose, tuple) else (pose, None)
+            w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+            j = None if joints is None else np.ascontiguousarray(joints, np.float32).reshape(-1, 16)
+            keep += [w, j]
+            v, pr, n0, nc = scene.mesh_index(i)
+            p.mesh = _abi.hk_mesh_index(v, pr, (C.c_uint32 * 2)(n0, nc))
+            p.weights = w.ctypes.data
+            p.target_count = len(w)
+            p.joints = None if j is None else j.ctypes.data
+            p.joint_count = 0 if j is None else len(j)
+        name = "hk_morph_meshes_refit_all" if refit == "all" else "hk_morph_meshes_refit" if refit else "hk_morph_meshes"
+        _check(self.ctx, getattr(self._L, name)(self.ctx, arr, len(poses), m.ctypes.data, a.ctypes.data, len(m),
+                                                _stream(stream)), name)
+
     def set_instances(self, scene: Scene, previous=None, materials: bool = False, stream=None, models=None,
                       local_aabbs=None) -> None:
         """A new instance set for the uploaded scene (hk_set_instances): entities spawned, despawned, hidden or given
@@ -796,6 +858,15 @@ class HikariPlugin:
                     refit=False) -> None:
         """HikariRenderer.skin_meshes: this frame's joint palettes (`SkinnedMeshJoints` x inverse bind poses)."""
         self.renderer.skin_meshes(scene, poses, models, local_aabbs, stream, refit=refit)
+
+    def set_mesh_morphs(self, scene: Scene, mesh_ids, keep_normals=(), stream=None) -> None:
+        """HikariRenderer.set_mesh_morphs: the meshes' morph targets (glTF blend shapes), resident on the device."""
+        self.renderer.set_mesh_morphs(scene, mesh_ids, keep_normals, stream)
+
+    def morph_meshes(self, scene: Scene, poses: dict, models=None, local_aabbs=None, stream=None,
+                     refit=False) -> None:
+        """HikariRenderer.morph_meshes: this frame's target weights (`MorphWeights`), and joint palettes under a skin."""
+        self.renderer.morph_meshes(scene, poses, models, local_aabbs, stream, refit=refit)
 
     def add_meshes(self, meshes, stream=None) -> list:
         """HikariRenderer.add_meshes: mesh assets created after the scene was uploaded (AssetEvent::Created)."""

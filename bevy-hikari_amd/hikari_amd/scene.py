@@ -251,6 +251,19 @@ class Skin:
 
 
 @dataclass
+class Morph:
+    """A mesh's morph targets (glTF blend shapes): per target a displacement of every vertex's position and, optionally,
+    normal.  TARGET-MAJOR: position_deltas[t, v] is target t's displacement of vertex v."""
+
+    position_deltas: np.ndarray  # (targets, n, 3) f32
+    normal_deltas: Optional[np.ndarray] = None  # (targets, n, 3) f32; None: the base normals as they are
+
+    @property
+    def target_count(self) -> int:
+        return len(self.position_deltas)
+
+
+@dataclass
 class Mesh:
     positions: np.ndarray  # (n, 3) f32
     normals: np.ndarray    # (n, 3) f32
@@ -258,6 +271,35 @@ class Mesh:
     indices: Optional[np.ndarray] = None  # u32
     topology: int = 0      # 0 = TriangleList, 1 = TriangleStrip
     skin: Optional[Skin] = None  # with it, positions and normals are the bind pose
+    morph: Optional[Morph] = None  # with it, positions and normals are the base the targets displace
+
+
+def morph_vertices(mesh: Mesh, weights, joints=None, aabb: bool = False):
+    """The mesh morphed on the host (hks_morph_vertices, include/hk_morph.h's rule): a copy of `mesh` whose positions
+    and normals (where it has any) are the base plus the weighted target deltas, folded in ascending target order over
+    the targets whose weight is not zero; with `joints` ((joint_count, 16) column-major matrices) the result is then
+    skinned (skin_vertices: glTF's order, morph then skin).  The skin and the morph stay.  aabb=True: (mesh, aabb)
+    with the final mesh's Bevy `Aabb` (centre xyz, half extents xyz) as the builder derives it."""
+    if mesh.morph is None:
+        raise ValueError("the mesh has no morph")
+    p = np.ascontiguousarray(mesh.positions, np.float32).reshape(-1, 3)
+    n = None if mesh.normals is None else np.ascontiguousarray(mesh.normals, np.float32).reshape(-1, 3)
+    w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+    dp = np.ascontiguousarray(mesh.morph.position_deltas, np.float32).reshape(-1, len(p), 3)
+    dn = None if mesh.morph.normal_deltas is None or n is None else \
+        np.ascontiguousarray(mesh.morph.normal_deltas, np.float32).reshape(-1, len(p), 3)
+    if len(w) != len(dp) or (dn is not None and dn.shape != dp.shape) or (n is not None and len(n) != len(p)):
+        raise ValueError("weights, position_deltas and normal_deltas differ in their target or vertex counts")
+    op, on, box = np.empty_like(p), None if n is None else np.empty_like(n), np.empty(6, np.float32)
+    rc = _abi.lib().hks_morph_vertices(p.ctypes.data, None if n is None else n.ctypes.data, dp.ctypes.data,
+                                       None if dn is None else dn.ctypes.data, len(p), w.ctypes.data, len(w),
+                                       op.ctypes.data, None if on is None else on.ctypes.data, box.ctypes.data)
+    if rc != 0:
+        raise _abi.HikariError(f"hks_morph_vertices refused its arguments ({rc}): target_count outside 1 .. 256?")
+    out = Mesh(op, on, mesh.uvs, mesh.indices, mesh.topology, mesh.skin, mesh.morph)
+    if joints is not None:
+        out, box = skin_vertices(out, joints, aabb=True)
+    return (out, box) if aabb else out
 
 
 def skin_vertices(mesh: Mesh, joints, aabb: bool = False):
@@ -282,7 +324,7 @@ def skin_vertices(mesh: Mesh, joints, aabb: bool = False):
                                       None if on is None else on.ctypes.data, box.ctypes.data)
     if rc != 0:
         raise _abi.HikariError(f"hks_skin_vertices refused its arguments ({rc}): a joint index >= joint_count?")
-    posed = Mesh(op, on, mesh.uvs, mesh.indices, mesh.topology, mesh.skin)
+    posed = Mesh(op, on, mesh.uvs, mesh.indices, mesh.topology, mesh.skin, mesh.morph)
     return (posed, box) if aabb else posed
 
 
@@ -505,10 +547,28 @@ class Scene:
         for i, joints in poses.items():
             m = self.meshes[i]
             if i in keep_normals:
-                p = skin_vertices(Mesh(m.positions, None, m.uvs, m.indices, m.topology, m.skin), joints)
-                s.meshes[i] = Mesh(p.positions, m.normals, m.uvs, m.indices, m.topology, m.skin)
+                p = skin_vertices(Mesh(m.positions, None, m.uvs, m.indices, m.topology, m.skin, m.morph), joints)
+                s.meshes[i] = Mesh(p.positions, m.normals, m.uvs, m.indices, m.topology, m.skin, m.morph)
             else:
                 s.meshes[i] = skin_vertices(m, joints)
+        s.materials, s.instances, s.textures = self.materials, self.instances, self.textures
+        return s
+
+    def morphed(self, poses: dict, keep_normals: Sequence[int] = ()) -> "Scene":
+        """A copy of the scene whose meshes `poses` names ({mesh id: weights} or {mesh id: (weights, joints)}) are
+        morphed, and with joints then skinned, on the host (morph_vertices): the host scene of
+        HikariRenderer.morph_meshes.  keep_normals: mesh ids whose normals stay as they are (a morph registered without
+        normals).  The other meshes, the materials, instances and textures are shared."""
+        s = Scene()
+        s.meshes = list(self.meshes)
+        for i, pose in poses.items():
+            weights, joints = pose if isinstance(pose, tuple) else (pose, None)
+            m = self.meshes[i]
+            if i in keep_normals:
+                p = morph_vertices(Mesh(m.positions, None, m.uvs, m.indices, m.topology, m.skin, m.morph), weights, joints)
+                s.meshes[i] = Mesh(p.positions, m.normals, m.uvs, m.indices, m.topology, m.skin, m.morph)
+            else:
+                s.meshes[i] = morph_vertices(m, weights, joints)
         s.materials, s.instances, s.textures = self.materials, self.instances, self.textures
         return s
 

@@ -546,6 +546,74 @@ int hk_refit_meshes_all(hk_ctx* ctx, const hk_mesh_update* meshes, uint32_t mesh
 int hk_skin_meshes_refit_all(hk_ctx* ctx, const hk_skin_pose* poses, uint32_t n, const float* models,
                              const float* local_aabbs, uint32_t count, void* stream);
 
+/* Morph targets.  The other way glTF animates geometry: blend shapes, usually a face under a skeleton.
+ * The reference does not morph and Bevy 0.9 has no morph targets; include/hk_morph.h states the rule (glTF 2.0's sum and
+ * Bevy 0.11's morph.wgsl, both recalled) and pins its evaluation order: per component acc = base, then
+ * acc = acc + w[t] * d[t] in f32, never contracted, for t ascending over the targets with w[t] != 0; normals by the same
+ * fold, not normalised; under a skin the morphed position and normal are what hk_skin.h's matrix is applied to.  The
+ * base and the deltas are resident on the device; a pose costs the host one weight vector (and a joint palette when
+ * the mesh is also skinned) and one call.
+ *
+ * hk_set_mesh_morphs replaces the context's WHOLE morph set (n == 0 drops it): for each listed mesh the base positions,
+ * base normals (NULL: the array's normals stay as they are) and the TARGET-MAJOR deltas (target_count x vertex_count x
+ * 3 floats; normal_deltas NULL: a pose copies the base normals) are copied into ONE device block the context owns:
+ * 12 B per vertex of base positions, 12 B of base normals, and 12 B (24 B with normal deltas) per vertex per target.
+ * The block keeps a capacity beside its size: re-registering as many bytes or fewer allocates nothing; a failed
+ * allocation leaves the former set in place.  Every check is made on the host before any device work, and a refusal
+ * leaves the context, its former morph set included, as it was.  It renders nothing and changes no scene array.  The
+ * set is independent of the skin set; it is dropped by hk_scene_upload and hk_set_meshes (slices move) and kept by
+ * hk_add_meshes, hk_set_instances and the updates.  Waits for the stream once.
+ * HK_ERR_INVALID with a message: a null list with n != 0; a null positions or position_deltas; normal_deltas without
+ * normals; target_count outside 1 .. HK_MORPH_MAX_TARGETS; `mesh` and vertex_count failing hk_set_mesh_skins' checks
+ * (not a known slice; a BLAS that is not 3k - 2 nodes; vertex_count not covering the stored vertex indices, or reaching
+ * past the vertex slice); a mesh listed twice; more than 0x40000000 vertices, or target_count x vertex_count records,
+ * in the set.  HK_ERR_STATE without a scene. */
+#ifndef HK_MORPH_MAX_TARGETS
+#define HK_MORPH_MAX_TARGETS 256u
+#endif
+typedef struct hk_mesh_morph {
+    hk_mesh_index mesh;           /* a known slice (instanced, registered, or appended by hk_add_meshes) */
+    uint32_t vertex_count;        /* as hk_mesh_update's */
+    const float* positions;       /* base, vertex_count x 3 */
+    const float* normals;         /* base; NULL: the array's normals stay as they are */
+    uint32_t target_count;        /* 1 .. HK_MORPH_MAX_TARGETS */
+    const float* position_deltas; /* target_count x vertex_count x 3, target-major */
+    const float* normal_deltas;   /* the same shape; NULL: no normal deltas (needs normals otherwise) */
+} hk_mesh_morph;
+int hk_set_mesh_morphs(hk_ctx* ctx, const hk_mesh_morph* morphs, uint32_t n, void* stream);
+
+/* hk_morph_meshes morphs the listed meshes ON THE GPU and rebuilds what depends on them, as hk_skin_meshes does for a
+ * skin: one thread per vertex folds the deltas of the targets whose weight is not zero (the host compacts them into a
+ * list, in ascending target order) over the resident base, applies the registered skin's matrix where the pose gives
+ * joints (hk_set_mesh_skins' indices and weights; the base is the MORPH set's: the skin's bind positions and normals
+ * are not read), and writes the position and normal where hk_update_meshes stages the host's.  From there the call IS
+ * hk_update_meshes, with each posed mesh's Bevy `Aabb` derived on the device for every instance of that mesh: the
+ * caller's local_aabbs rows of those instances are ignored (they must still be readable).  After the call all nine
+ * arrays are byte for byte what hks_build + hk_scene_upload give for the scene whose posed meshes hold
+ * hks_morph_vertices' output, passed through hks_skin_vertices with the registered skin's indices and weights where
+ * joints are given; meshes not posed in this call keep their bytes.  hk_morph_meshes_refit / _refit_all: the same with
+ * each posed BLAS refit (hk_refit_meshes' contract) / the TLAS and the light BVH refit as well (hk_refit_meshes_all's).
+ * States, waits and the treatment of n == 0 (hk_update_instances / hk_refit_instances for _refit_all) are
+ * hk_skin_meshes' and its refits'.
+ * HK_ERR_INVALID with a message, the context unchanged and usable: a null pointer (poses with n != 0, a pose's weights,
+ * models, local_aabbs); count other than the instance count; a pose for a mesh with no registered morph; target_count
+ * other than the registered one; joints for a mesh with no registered skin; joint_count other than the skin's; a skin
+ * and a morph that disagree on whether normals are rewritten (one registered with normals, the other without), or on
+ * the vertex_count; a mesh posed twice; hk_update_meshes' checks, made again.  HK_ERR_STATE without a scene. */
+typedef struct hk_morph_pose {
+    hk_mesh_index mesh;
+    const float* weights;  /* target_count floats */
+    uint32_t target_count; /* the registered morph's */
+    const float* joints;   /* NULL: morph only; else joint_count column-major 4 x 4 matrices, as hk_skin_pose's */
+    uint32_t joint_count;  /* the registered skin's (ignored without joints) */
+} hk_morph_pose;
+int hk_morph_meshes(hk_ctx* ctx, const hk_morph_pose* poses, uint32_t n, const float* models, const float* local_aabbs,
+                    uint32_t count, void* stream);
+int hk_morph_meshes_refit(hk_ctx* ctx, const hk_morph_pose* poses, uint32_t n, const float* models,
+                          const float* local_aabbs, uint32_t count, void* stream);
+int hk_morph_meshes_refit_all(hk_ctx* ctx, const hk_morph_pose* poses, uint32_t n, const float* models,
+                              const float* local_aabbs, uint32_t count, void* stream);
+
 /* Tree costs: how expensive the resident trees are to walk, by the rule of include/hk_cost.h, computed ON
  * THE GPU from the nodes as they stand: what a caller that refits (hk_refit_instances, hk_refit_meshes, the _all calls)
  * decides a rebuild with.  The reference has no such query (it never refits); the rule is this library's own.

@@ -89,6 +89,26 @@ int hks_skin_vertices(const float* positions, const float* normals, const uint16
                       const float* joint_weights, uint32_t vertex_count, const float* joints, uint32_t joint_count,
                       float* out_positions, float* out_normals, float out_aabb[6]);
 
+/* Morph targets (blend shapes) of a mesh's vertices on the host, by the rule of include/hk_morph.h (glTF 2.0's
+ * morph-target sum and Bevy 0.11's morph.wgsl as recalled, the evaluation order pinned there): the host side of
+ * hk_morph_meshes' contract, and what a caller without a device uses.  positions / normals: the base, vertex_count x 3;
+ * position_deltas / normal_deltas: TARGET-MAJOR, target_count x vertex_count x 3; weights: target_count.  Per component,
+ * f32, never contracted: acc = base, then acc = acc + w[t] * d[t] for t ascending over the targets with w[t] != 0 (a
+ * zero weight of either sign is skipped, so a base of -0.0 stays -0.0 and a zero weight on an infinite delta is not
+ * NaN; a NaN weight takes part).  The normals take the same fold over normal_deltas and are NOT normalised;
+ * normal_deltas == NULL copies the base normals word for word.  normals and out_normals are both NULL or both set.
+ * out_aabb (may be NULL): the morphed mesh's Bevy `Aabb` as hks_skin_vertices derives a posed mesh's.  Under a skin the
+ * outputs are hks_skin_vertices' positions and normals (glTF's order: morph, then skin).  Returns 0, or HK_ERR_INVALID
+ * with nothing written for a null required pointer (positions, position_deltas, weights, out_positions), normals
+ * without out_normals or the reverse, normal_deltas without normals, or target_count outside
+ * 1 .. HK_MORPH_MAX_TARGETS.  Needs no device. */
+#ifndef HK_MORPH_MAX_TARGETS
+#define HK_MORPH_MAX_TARGETS 256u
+#endif
+int hks_morph_vertices(const float* positions, const float* normals, const float* position_deltas,
+                       const float* normal_deltas, uint32_t vertex_count, const float* weights, uint32_t target_count,
+                       float* out_positions, float* out_normals, float out_aabb[6]);
+
 /* A BLAS refit on the host, by the rule of include/hk_refit.h: the host side of hk_refit_meshes' and
  * hk_skin_meshes_refit's contract, and what a caller without a device uses.  nodes: one mesh's slice of the asset nodes,
  * a bvh-0.7.1 flatten of node_count = 3 x primitive_count - 2 nodes with slice-relative indices; primitives: the mesh's
